@@ -2,6 +2,8 @@
 """Benchmark of the libcluster E-step hot path on MI355X.
 
     python bench.py --gpus 1 --steps 10 --warmup 1
+    python bench.py --gpus 1 --steps 10 --warmup 1 --dump-outputs DIR   # + the last step's results as DIR/*.npy
+    python bench.py --gpus 1 --full       # + CPU baseline, parity legs, other configurations, model selection, drop-in call
     python bench.py --gpus 8 ...          # starts the 8 ranks itself (torch.distributed.run, one process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -12,6 +14,11 @@ suff-stat kernel (updateSS/addobs) -> [N>1: RCCL all-reduce] -> host M-step ->
 E-step kernel (vbexpectation) -> [N>1: all-reduce of Fz] -> free energy.
 Nothing is skipped inside the timed region.  value = rows processed by all
 ranks per second (weak scaling: every GPU holds `N` rows).
+
+A plain run sets up, warms up, times the K steps and prints the line (throughput, per-kernel times and roofline of
+the same timed steps).  Everything that takes runs of its own -- the CPU baseline, the parity legs against the
+oracle, the other configurations, model selection and the drop-in call -- runs only with --full.
+--dump-outputs DIR writes what the timed path returned after its last step (see dump_outputs) as float64 .npy files.
 
 Default workload: the configuration BASELINE.json's north_star quotes the
 metric on -- BGMM, N=10M rows per GPU, D=64, K=32 (configs[3] is the same
@@ -132,6 +139,48 @@ def summary_of(line):
     if isinstance(dc, dict) and "seconds" in dc:
         out["dropin_call_s"] = r4(dc["seconds"])
     return out
+
+
+DUMP_QZ_ROWS = 65536          # rows of qZ in a dump: a seeded sample (the whole qZ of the north-star shape is 2.6 GB)
+DUMP_QZ_BLOCK = 512           # ... taken as blocks of consecutive rows
+DUMP_QZ_BYTES = 32 << 20
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(ctx, model, F, rows_per_group, outdir):
+    """--dump-outputs: what a caller of the timed path (lc_vbem at fixed K) receives after its last step, as float64
+    DIR/<name>.npy -- free_energy [1]; the weights of every group (weights_Elogpi, weights_N: [J, K]); every cluster's
+    posterior (cluster_<field>: [K, ...], the fields of Model.cluster); and the responsibilities of a fixed sample of
+    rows (qz_sample [n, K]: blocks of DUMP_QZ_BLOCK consecutive rows, drawn without replacement by a fixed seed over the
+    groups in order, at most DUMP_QZ_ROWS rows and DUMP_QZ_BYTES).  The workload is seeded, so two builds of the
+    library run with the same arguments can be compared file by file."""
+    _, _, _, K = ctx.dims()
+    J, KM, _ = model.dims()
+    arrays = {"free_energy": np.array([F], dtype=np.float64)}
+    w = [model.weights(j) for j in range(J)]
+    arrays["weights_Elogpi"] = np.stack([e for e, _ in w])
+    arrays["weights_N"] = np.stack([n for _, n in w])
+    cl = [model.cluster(k) for k in range(KM)]
+    for key in cl[0]:
+        arrays["cluster_" + key] = np.stack([np.asarray(c[key], dtype=np.float64) for c in cl])
+    B = max(1, min(DUMP_QZ_BLOCK, min(rows_per_group)))
+    nblk = [n // B for n in rows_per_group]
+    starts = np.concatenate([[0], np.cumsum(nblk)])
+    want = max(1, min(int(starts[-1]), DUMP_QZ_ROWS // B, DUMP_QZ_BYTES // (8 * K * B)))
+    pick = np.sort(np.random.default_rng(20261016).choice(int(starts[-1]), want, replace=False))
+    q = []
+    for b in pick:
+        j = int(np.searchsorted(starts, b, side="right") - 1)
+        q.append(ctx.get_qz_rows(j, int(b - starts[j]) * B, B))
+    arrays["qz_sample"] = np.vstack(q)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    out = Path(outdir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
 
 
 def alg_flops(N, D, K):
@@ -687,6 +736,9 @@ def main_inproc(args):
         print(f"bench --inproc failed: {first[0]!r}", file=sys.stderr)
         return 1
     res = errs[0][0]
+    if args.dump_outputs:
+        J = cfg.get("J", 1)
+        dump_outputs(errs[0][1], errs[0][2], res["free_energy"], [cfg["N"] // J] * J, args.dump_outputs)
     res["config"]["parallelism"] += f"; ONE process, {world} host threads (one context per GPU)"
     line = {
         "metric": "E-step data-points/sec (full VBEM iteration: suff-stats + M-step + E-step)",
@@ -712,6 +764,12 @@ def main():
     ap.add_argument("--config", default="northstar", choices=sorted(CONFIGS))
     ap.add_argument("--rows", type=int, default=0, help="override rows per GPU")
     ap.add_argument("--groups", type=int, default=0, help="override groups per GPU (grouped configurations)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the parity legs, the other configurations, model selection and the "
+                         "drop-in call (single-rank runs; the --no-* options below drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they returned (free energy, weights, cluster posteriors, "
+                         "a seeded sample of qZ rows) as float64 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
@@ -785,6 +843,9 @@ def main():
 
     res, ctx, model, (wkind, ckind, mu, L, family) = measure(capi, cfg, args.steps, args.warmup, rank, world,
                                                               local_rank, stream, nthreads, comm, dist, torch)
+    if rank == 0 and args.dump_outputs:
+        J = cfg.get("J", 1)
+        dump_outputs(ctx, model, res["free_energy"], [cfg["N"] // J] * J, args.dump_outputs)
     if rank == 0:
         # HBM bytes per launch from the committed PMC passes (not live): the newest profiles/rNN_pmc_traffic.json, which
         # tools/pmc_traffic.py GENERATES from the rocprofv3 summaries next to it (tests/test_host.py checks that)
@@ -811,10 +872,10 @@ def main():
             **({"check": res["check"]} if "check" in res else {}),
         }
         N, D, K = cfg["N"], cfg["D"], cfg["K"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = (cpu_baseline(ctx, model, cfg, args.cpu_sample_rows) if family == "GaussWish" else
                                     cpu_baseline_family(ctx, cfg, min(args.cpu_sample_rows, 400_000)))
-        if world == 1 and not args.no_parity:
+        if world == 1 and args.full and not args.no_parity:
             if family == "GaussWish" and cfg.get("J", 1) == 1:
                 sys.path.insert(0, str(ROOT / "oracle"))
                 import lc_oracle_c as oc
@@ -825,7 +886,7 @@ def main():
                 line["parity_overlap"] = parity_c(capi, cfg, wkind, local_rank, rows, 3, True, nt)
             else:
                 line["parity"] = parity_numpy(capi, cfg, wkind, mu, L, local_rank, ckind=ckind)
-        if world == 1 and args.config == "northstar" and not args.rows and not args.no_other_configs:
+        if world == 1 and args.full and args.config == "northstar" and not args.rows and not args.no_other_configs:
             # the other BASELINE configurations and the separable families, 5 timed steps each: driver-visible
             # ms_per_step / roofline of the kernels that are NOT on the headline line
             if model is not None:
