@@ -168,6 +168,103 @@ const char* suffstat_kernel_name(int DP, int K, int DC = 0);  // "suffstat_kerne
 // chunk, laid out after the K regular ones ([row class - 1][cluster of the last slice]).  Returns extra (0: no split);
 // klast0 = first cluster of the last slice.  launch_fold_extra adds them into their clusters after the reduction.
 int suffstat_extra_records(int DP, int K, bool skip_or_items, int* klast0, int DC = 0);
+
+// ---- tile plan of the feature-GEMM statistics kernel (suffstat_feat_kernel, lc_kernels_suffstat.hip) ----------------
+// Features of the active width DC, one per lane of a 16-feature tile (lane (lo2, blk) of tile T holds feature
+// 16 T + lo2 + 4 blk), in this order:
+//   the off-diagonal 4 x 4 patches (ia < ja, ja-major) whole: u = 4 ia + lo2, w = 4 ja + blk (same LDS reads as the
+//     patch deal had);
+//   the 10 distinct products x_i x_j (i <= j) of each diagonal 4 x 4 block, packed;
+//   the DC linear features x_i * 1;
+//   N_k = 1 * 1.
+// Spare slots of the last tile read 1 * 1 and are not stored.  D = 64: 120 x 16 + 160 + 64 + 1 = 2145 features in 135
+// tiles (the patch deal took 141: whole diagonal patches, whole 16-column s_k blocks, a tile of its own for N_k).
+__host__ __device__ constexpr int ft_offdiag(int DC) { return (DC / 4) * (DC / 4 - 1) / 2; }
+__host__ __device__ constexpr int ft_features(int DC) { return 16 * ft_offdiag(DC) + 10 * (DC / 4) + DC + 1; }
+__host__ __device__ constexpr int ft_tiles(int DC) { return (ft_features(DC) + 15) / 16; }
+enum FtKind { FT_PRODUCT = 0, FT_LINEAR = 1, FT_COUNT = 2, FT_SPARE = 3 };
+struct FtFeature {
+  int u, w, kind;  // staged columns of the two factors (`one`: the column of ones)
+};
+__host__ __device__ constexpr FtFeature ft_feature(int DC, int one, int f) {
+  const int noff = 16 * ft_offdiag(DC), ndiag = 10 * (DC / 4);
+  if (f < noff) {
+    const int p = f / 16, r = f % 16;
+    int ja = 1;
+    while ((ja + 1) * ja / 2 <= p) ++ja;
+    return {4 * (p - ja * (ja - 1) / 2) + (r & 3), 4 * ja + (r >> 2), FT_PRODUCT};
+  }
+  f -= noff;
+  if (f < ndiag) {  // (i, j) of a diagonal block: (0,0) (0,1) (0,2) (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3)
+    const int b = 4 * (f / 10), e = f % 10;
+    const int i = e < 4 ? 0 : e < 7 ? 1 : e < 9 ? 2 : 3, i0 = e < 4 ? 0 : e < 7 ? 4 : e < 9 ? 7 : 9;
+    return {b + i, b + i + (e - i0), FT_PRODUCT};
+  }
+  f -= ndiag;
+  if (f < DC) return {f, one, FT_LINEAR};
+  return {one, one, f == DC ? FT_COUNT : FT_SPARE};
+}
+// Waves per block.  The waves of a block share one staged batch, so 8 waves (one block per CU, longer batches) halve
+// the staging instructions and barriers per MFMA against 4 waves (two blocks per CU): D = 64, N = 10M, K = 32:
+// 22.03 -> 21.70 ms.
+// (round 5: D = 80, 96, 112 as 8-wave blocks too -- half the staging registers per thread, and with them every instance
+//  but <80, 6> free of scratch, where the 4-wave instances spilled 64 ... 136 bytes into the step loop: the feature GEMM
+//  now runs at these widths, N = 4M, K = 32: D = 96 22.9 -> 19.1 ms (0.67 -> 0.81 of the fp64 peak), D = 80 15.0 -> 13.7,
+//  D = 112 (N = 3M) 21.9 -> 19.9)
+#ifndef LC_FT_WAVES64
+#define LC_FT_WAVES64 8
+#endif
+#ifndef LC_FT_WAVES128
+#define LC_FT_WAVES128 8
+#endif
+__host__ __device__ constexpr int ft_waves(int DP) { return DP == 64 ? LC_FT_WAVES64 : DP == 128 ? LC_FT_WAVES128 : DP > 64 ? 8 : 4; }
+// tiles per wave: as many as the accumulators allow (72 doubles; 64 for 8 quads at D = 80, 96, 112, where 72 spill) -- 9 tiles
+// with 8 cluster quads, 12 with 6, 14 with 5: a launch with fewer quads keeps its MFMAs per step (and has fewer blocks
+// re-staging the same rows)
+__host__ __device__ constexpr int ft_tpw_max(int DP, int NQ) {
+  const int t = (NQ >= 8 && DP > 64 && DP < 128 ? 64 : 72) / NQ;
+  return t < 14 ? t : 14;  // (two address registers per tile)
+}
+__host__ __device__ constexpr int ft_nslice(int DP, int DC, int NQ) {  // blocks per row chunk
+  return (ft_tiles(DC) + ft_waves(DP) * ft_tpw_max(DP, NQ) - 1) / (ft_waves(DP) * ft_tpw_max(DP, NQ));
+}
+__host__ __device__ constexpr int ft_tpw(int DP, int DC, int NQ) {  // tiles of the fuller waves
+  return (ft_tiles(DC) + ft_waves(DP) * ft_nslice(DP, DC, NQ) - 1) / (ft_waves(DP) * ft_nslice(DP, DC, NQ));
+}
+// The tiles of wave `wave` of block `slice` of a chunk: [*t0, *t0 + *nt).
+// 8 waves: dealt per SIMD.  A block's waves go to the four SIMDs of its CU in cyclic order, so waves w and w + 4 share
+// one matrix pipe, and with one barrier per staged batch a block lasts as long as its busiest SIMD: the 4 x nslice SIMDs
+// of a chunk take ceil or floor of TILES / (4 nslice) tiles each, split ceil / floor between the two waves (D = 64, 8
+// quads: 17 17 17 17 | 17 17 17 16 = waves of 9 + 8, the last 8 + 8).  A per-wave deal (the first TILES % 16 waves of
+// one tile more) put 9 + 9 on one SIMD or more of every block: 18 tile-streams where 17 do.
+// 4 waves (two blocks per CU, the partners belong to different blocks): TPW everywhere, the last waves of a chunk carry
+// idle tiles -- a second instance of the batch body costs more there than the idle tiles do (D = 128, 4 waves: 72.9 ->
+// 77.2 ms with an uneven deal; both bodies compete for the instruction cache).
+__host__ __device__ constexpr void ft_deal(int DP, int DC, int NQ, int slice, int wave, int* t0, int* nt) {
+  const int tiles = ft_tiles(DC), nsl = ft_nslice(DP, DC, NQ);
+  if (ft_waves(DP) == 8) {
+    const int ns = 4 * nsl, s = slice * 4 + (wave & 3), l = tiles / ns, r = tiles % ns;
+    const int load = l + (s < r ? 1 : 0), first = s * l + (s < r ? s : r);
+    *t0 = first + (wave < 4 ? 0 : (load + 1) / 2);
+    *nt = wave < 4 ? (load + 1) / 2 : load / 2;
+  } else {
+    const int tpw = ft_tpw(DP, DC, NQ), t = (slice * 4 + wave) * tpw;
+    *t0 = t;
+    *nt = tiles - t < tpw ? (tiles - t > 0 ? tiles - t : 0) : tpw;
+  }
+}
+// the smallest tile count of any wave (the 8-wave deal: ft_tpw or one fewer)
+__host__ __device__ constexpr int ft_nt_min(int DP, int DC, int NQ) {
+  int m = ft_tpw(DP, DC, NQ);
+  for (int sl = 0; sl < ft_nslice(DP, DC, NQ); ++sl)
+    for (int w = 0; w < ft_waves(DP); ++w) {
+      int t0 = 0, nt = 0;
+      ft_deal(DP, DC, NQ, sl, w, &t0, &nt);
+      m = nt < m ? nt : m;
+    }
+  return m;
+}
+
 hipError_t launch_fold_extra(double* rec, int64_t SS, int K, int klast0, int extra, hipStream_t stream);
 hipError_t launch_reduce_records(const double* partial, int64_t n, int K, const int* kptr, const int* krec, double* out,
                                  hipStream_t stream);

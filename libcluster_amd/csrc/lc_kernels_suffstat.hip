@@ -528,37 +528,19 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? (HALF != 0 ? 3 : 2) : (HALF !
 // stream of fp64 MFMAs costs the matrix pipe about 11 clocks (tools/mfma_mix_probe.hip) -- its ceiling is ~81 % of the
 // pipe, and it sits there.  Here the cluster index moves into the MFMA:  T = Q^T Phi(x), Phi(x) = [x_i x_j (i <= j) | x_i | 1]:
 //   A operand = q[row 4 st + hi][cluster k0 + 4 c + lo2]     (one LDS read per cluster quad and step, all tiles share it)
-//   B operand = x[row][4 ia + lo2] * x[row][4 ja + blk]      (ONE multiply per 16 features, shared by ALL cluster quads)
-//   D[i = hi][j = lo2] of block blk = S_{k0 + 4c + hi}[4 ia + lo2][4 ja + blk]
+//   B operand = x[row][u] * x[row][w]                         (ONE multiply per 16 features, shared by ALL cluster quads)
+//   D[i = hi][lane (lo2, blk)] = sum over the rows of q_{k0 + 4c + hi} x_u x_w
 // i.e. one v_mul_f64 per NQ MFMAs (NQ = cluster quads per launch, up to 8: 1 : 8 against 1 : 4) and nothing else on the
 // VALU: s_k and N_k are the features x_i * 1 and 1 * 1 (a column of ones rides in the staged X rows).  A "tile" is 16
-// features: the 4 x 4 patches (ia <= ja) of the symmetric matrix, DP / 16 tiles of s_k, one of N_k (141 at D = 64); a
-// wave owns up to 9 tiles x NQ quads (<= 72 accumulators), nslice blocks of four waves cover a row chunk (as the cluster
-// slices of suffstat_kernel do).  Every tile reads its two operand fragments itself (LDS broadcast reads cost the
-// matrix pipe nothing; no operand sharing to schedule).  More than 32 clusters: one launch per range of <= 32.
-// Same partial records, same reduction, deterministic; the patch on the diagonal computes both halves of its 4 x 4
-// block from commuted products, so S_k comes out exactly symmetric.
-// (DC: the ACTIVE width, estep_active_width in lc_kernels.h -- the patches of the columns past it are products of zeros
-//  and are not dealt out at all; the s_k tiles cover whole 16-column blocks, their idle columns read the staged zeros)
-__host__ __device__ constexpr int ft_tiles(int DC) { return (DC / 4) * (DC / 4 + 1) / 2 + (DC + 15) / 16 + 1; }
-// tiles per wave: as many as the accumulators allow (72 doubles; 64 for 8 quads at D = 80, 96, 112, where 72 spill) -- 9 tiles
-// with 8 cluster quads, 12 with 6, 14 with 5: a launch with fewer quads keeps its MFMAs per step (and has fewer blocks
-// re-staging the same rows)
-__host__ __device__ constexpr int ft_tpw_max(int DP, int NQ) {
-  const int t = (NQ >= 8 && DP > 64 && DP < 128 ? 64 : 72) / NQ;
-  return t < 14 ? t : 14;  // (two address registers per tile)
-}
-// Waves per block.  The waves of a block share one staged batch, so 8 waves (one block per CU, longer batches) halve
-// the staging instructions and barriers per MFMA against 4 waves (two blocks per CU): D = 64, N = 10M, K = 32:
-// 22.03 -> 21.70 ms.  With 8 waves the tiles are dealt out unevenly -- the first TILES % NW of a chunk's NW = waves x
-// nslice waves take one tile more than the others (ft_tpw is the larger count) -- so no wave carries idle tiles (D = 128:
-// 537 tiles = 25 waves x 9 + 39 x 8; with 9 everywhere 64 waves would carry 39 idle ones: 73.0 -> 77.2 ms).
-#ifndef LC_FT_WAVES64
-#define LC_FT_WAVES64 8
-#endif
-#ifndef LC_FT_WAVES128
-#define LC_FT_WAVES128 8
-#endif
+// features, each the product of one lane's own two columns (u, w): the features of the active width, packed (ft_feature
+// in lc_kernels.h: 135 tiles at D = 64); a wave owns up to 9 tiles x NQ quads (<= 72 accumulators), nslice blocks cover a
+// row chunk (as the cluster slices of suffstat_kernel do), and the tiles are dealt so that no SIMD carries more than its
+// share (ft_deal).  Every tile reads its two operand fragments itself (LDS broadcast reads cost the matrix pipe nothing;
+// no operand sharing to schedule).  More than 32 clusters: one launch per range of <= 32.  Same partial records, same
+// reduction, deterministic; a feature's accumulator sees the same MFMAs over the same rows wherever in a tile it sits,
+// and the one accumulator of x_i x_j is written to S[i][j] and S[j][i], so S_k comes out exactly symmetric.
+// (DC: the ACTIVE width, estep_active_width in lc_kernels.h -- the features of the columns past it are products of zeros
+//  and are not dealt out at all; their record entries are never written)
 #ifndef LC_FT_BR
 #define LC_FT_BR 32
 #endif
@@ -571,17 +553,6 @@ __host__ __device__ constexpr int ft_tpw_max(int DP, int NQ) {
 // tiles whose products are formed together in front of their MFMAs (suffstat_feat_kernel's step loop)
 // (round 5, K = 20 / 40 at D = 64: threes and fours for the launches of <= 6 quads measure the same as pairs, gpurun_out/r05y2)
 __host__ __device__ constexpr int ft_group(int DP) { return DP >= 48 && DP <= 112 ? 2 : 1; }
-// (round 5: D = 80, 96, 112 as 8-wave blocks too -- half the staging registers per thread, and with them every instance
-//  but <80, 6> free of scratch, where the 4-wave instances spilled 64 ... 136 bytes into the step loop: the feature GEMM
-//  now runs at these widths, N = 4M, K = 32: D = 96 22.9 -> 19.1 ms (0.67 -> 0.81 of the fp64 peak), D = 80 15.0 -> 13.7,
-//  D = 112 (N = 3M) 21.9 -> 19.9; gpurun_out/r05l)
-__host__ __device__ constexpr int ft_waves(int DP) { return DP == 64 ? LC_FT_WAVES64 : DP == 128 ? LC_FT_WAVES128 : DP > 64 ? 8 : 4; }
-__host__ __device__ constexpr int ft_nslice(int DP, int DC, int NQ) {  // blocks per row chunk
-  return (ft_tiles(DC) + ft_waves(DP) * ft_tpw_max(DP, NQ) - 1) / (ft_waves(DP) * ft_tpw_max(DP, NQ));
-}
-__host__ __device__ constexpr int ft_tpw(int DP, int DC, int NQ) {  // tiles of the fuller waves
-  return (ft_tiles(DC) + ft_waves(DP) * ft_nslice(DP, DC, NQ) - 1) / (ft_waves(DP) * ft_nslice(DP, DC, NQ));
-}
 // (160 KB of LDS per CU: two blocks of 4 waves or one of 8)
 __host__ __device__ constexpr int ft_batch_rows(int DP) {
   return DP == 128 && ft_waves(DP) == 8 ? LC_FT_BR128 : DP > 96 ? 24 : DP == 64 && ft_waves(DP) == 8 ? LC_FT_BR64 : LC_FT_BR;
@@ -620,8 +591,7 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
   static_assert(DC % 4 == 0 && DC <= DP && DC > DP - 16, "active width");
   constexpr int FTW = ft_waves(DP);
   constexpr int BR = ft_batch_rows(DP), LD = lds_row_stride(DP), QLD = ft_qld(NQ), XBUF = BR * LD, QBUF = BR * QLD;
-  constexpr int TPW = ft_tpw(DP, DC, NQ), TILES = ft_tiles(DC), NPATCH = (DC / 4) * (DC / 4 + 1) / 2, NSL = ft_nslice(DP, DC, NQ);
-  constexpr int NLIN = (DC + 15) / 16;  // s_k tiles
+  constexpr int TPW = ft_tpw(DP, DC, NQ), NSL = ft_nslice(DP, DC, NQ);
   constexpr int ONE = DP;  // column of the staged rows that holds 1.0
   static_assert(LD > DP, "the staged rows need a spare column");
   static_assert(TPW * NQ <= 72, "accumulators");
@@ -647,33 +617,21 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
   }
   const int64_t r0 = (int64_t)chunk * a.chunk_rows;
   const int64_t r1 = (r0 + a.chunk_rows) < a.NP ? (r0 + a.chunk_rows) : a.NP;
-  // this wave's tiles and, per lane, where their two operand fragments sit in a staged batch (in doubles, step 0)
-  // 8 waves: NFULL waves of TPW tiles, then TPW - 1 (two instances of the batch body).  4 waves: TPW everywhere, the
-  // last waves of a chunk carry idle tiles -- the second instance costs more there than the idle tiles do (D = 128,
-  // 4 waves: 72.9 -> 77.2 ms with the uneven deal; both bodies compete for the instruction cache)
-  constexpr bool UNEVEN = FTW == 8;
-  constexpr int NW = FTW * NSL, TPWL = UNEVEN ? TILES / NW : TPW, NFULL = UNEVEN ? TILES - TPWL * NW : 0;
-  static_assert(TPWL >= 1 && (NFULL == 0 ? TPWL : TPWL + 1) == TPW, "tile deal");
-  const int gw = slice * FTW + wave;
-  const int T0 = UNEVEN ? gw * TPWL + (gw < NFULL ? gw : NFULL) : gw * TPW;
-  const int nt = UNEVEN ? TPWL + (gw < NFULL ? 1 : 0) : (TILES - T0 < TPW ? (TILES - T0 > 0 ? TILES - T0 : 0) : TPW);
+  // this wave's tiles (ft_deal) and, per lane, where their two operand fragments sit in a staged batch (in doubles,
+  // step 0).  8 waves: TPW or TPW - 1 tiles (two instances of the batch body); 4 waves: TPW everywhere, the tiles past
+  // the last one (idle) read 1 * 1 and are not stored
+  constexpr bool UNEVEN = FTW == 8 && ft_nt_min(DP, DC, NQ) < TPW;
+  constexpr int TPWL = UNEVEN ? TPW - 1 : TPW;
+  static_assert(FTW != 8 || (TPWL >= 1 && ft_nt_min(DP, DC, NQ) == TPWL), "tile deal");
+  int T0 = 0, nt = 0;
+  ft_deal(DP, DC, NQ, slice, wave, &T0, &nt);
   const double* pu[TPW];
   const double* pw[TPW];
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
-    const int T = T0 + t;
-    int cu = ONE, cw = ONE;  // N_k tile (and the idle ones): 1 * 1
-    if (T < NPATCH) {
-      int ja = 0;
-      while ((ja + 1) * (ja + 2) / 2 <= T) ++ja;
-      const int ia = T - ja * (ja + 1) / 2;
-      cu = 4 * ia + lo2;
-      cw = 4 * ja + blk;
-    } else if (T < NPATCH + NLIN) {
-      cu = 16 * (T - NPATCH) + 4 * blk + lo2;
-    }
-    pu[t] = xbuf + hi * LD + cu;
-    pw[t] = xbuf + hi * LD + cw;
+    const FtFeature f = ft_feature(DC, ONE, 16 * (T0 + t) + lo2 + 4 * blk);
+    pu[t] = xbuf + hi * LD + f.u;
+    pw[t] = xbuf + hi * LD + f.w;
   }
   double acc[TPW][NQ];
 #pragma unroll
@@ -863,13 +821,13 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
   for (int64_t b0 = r0; b0 < r1; b0 += 2 * BR) {  // two batches per trip: the buffer index is a compile-time constant
     const bool more1 = b0 + BR < r1, more2 = b0 + 2 * BR < r1;
     if (more1) gload(b0 + BR);
-    if (NFULL == 0 || nt == TPW) batch(std::integral_constant<int, 0>{}, std::integral_constant<int, TPW>{});
+    if (!UNEVEN || nt == TPW) batch(std::integral_constant<int, 0>{}, std::integral_constant<int, TPW>{});
     else batch(std::integral_constant<int, 0>{}, std::integral_constant<int, TPWL>{});
     if (more1) lstore(1);
     __syncthreads();
     if (!more1) break;
     if (more2) gload(b0 + 2 * BR);
-    if (NFULL == 0 || nt == TPW) batch(std::integral_constant<int, 1>{}, std::integral_constant<int, TPW>{});
+    if (!UNEVEN || nt == TPW) batch(std::integral_constant<int, 1>{}, std::integral_constant<int, TPW>{});
     else batch(std::integral_constant<int, 1>{}, std::integral_constant<int, TPWL>{});
     if (more2) lstore(0);
     __syncthreads();
@@ -877,29 +835,29 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
 
   // ---- partial records: [N_k, s_k[DP], S_k[DP x DP]] per (chunk, cluster), as suffstat_kernel writes them
   const int64_t SS = 1 + (int64_t)DP + (int64_t)DP * DP;
+  // (the deal and the features are worked out again here, not kept: an opaque copy of the slice keeps the compiler from
+  //  hoisting them in front of the step loop, where their results would sit in registers next to the accumulators)
+  int sle = slice, T0e = 0, nte = 0;
+  asm volatile("" : "+v"(sle));
+  ft_deal(DP, DC, NQ, sle, wave, &T0e, &nte);
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
-    if (t >= nt) continue;
-    const int T = T0 + t;
-    int ia = 0, ja = 0;
-    if (T < NPATCH) {
-      while ((ja + 1) * (ja + 2) / 2 <= T) ++ja;
-      ia = T - ja * (ja + 1) / 2;
-    }
+    if (t >= nte) continue;
+    const FtFeature f = ft_feature(DC, ONE, 16 * (T0e + t) + lo2 + 4 * blk);
+    if (f.kind == FT_SPARE) continue;
 #pragma unroll
     for (int c = 0; c < NQ; ++c) {
       const int kk = 4 * c + hi;
       if (kk >= KC) continue;
       double* out = a.partial + ((int64_t)chunk * a.KR + k0 + kk) * SS;
       const double v = acc[t][c];
-      if (T < NPATCH) {
-        const int gi = 4 * ia + lo2, gj = 4 * ja + blk;
+      if (f.kind == FT_PRODUCT) {
         double* S = out + 1 + DP;
-        S[(int64_t)gi * DP + gj] = v;
-        S[(int64_t)gj * DP + gi] = v;
-      } else if (T < NPATCH + NLIN) {
-        out[1 + 16 * (T - NPATCH) + 4 * blk + lo2] = v;
-      } else if (blk == 0 && lo2 == 0) {
+        S[(int64_t)f.u * DP + f.w] = v;
+        S[(int64_t)f.w * DP + f.u] = v;
+      } else if (f.kind == FT_LINEAR) {
+        out[1 + f.u] = v;
+      } else {
         out[0] = v;
       }
     }
