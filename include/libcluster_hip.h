@@ -288,6 +288,33 @@ int lc_model_cluster(lc_model* m, int k, double* N, double* mean, double* cov, d
                      double* logdW);
 int lc_model_fenergy(lc_model* m, double* Fw /*[J]*/, double* Fc /*[K]*/);
 
+/* ---- prediction on new observations (nothing in the reference corresponds: its users call
+ * clusters[k].Eloglike(Xnew), distributions.cpp:356-370 / 483-492 / 568-572, and do vbexpectation's log-sum-exp,
+ * cluster.cpp:91-138, themselves).  The new rows live in ctx (lc_ctx_set_data / lc_ctx_synth); block b of ctx is scored
+ * with the weights of learned group groups[b] (NULL: group 0).  Per row:
+ *   qZ    (keep_qz != 0: the context's qZ, K columns) vbexpectation with the model's final posteriors and Elogweight()
+ *         of the group; sparse models use the same Kful rule, getNk() >= ZEROCUTOFF (cluster.cpp:107-112)
+ *   logZ  log sum_{k in Kful} exp(E[log pi_jk] + Eloglike_k(x)): the row's term of Fxz = -sum logZ (cluster.cpp:121-137)
+ *   label argmax_k of E[log pi_jk] + Eloglike_k(x) (the largest responsibility), lowest k on ties
+ *   logp  log p(x | training data) = log(sum_k E[pi_jk] P_k(x) + E[pi_rest] P_0(x)), P_k the posterior predictive of
+ *         cluster k (multivariate Student-t / product of Student-t / product of Lomax), P_0 that of the cluster prior
+ *         (StickBreak only: the mass beyond the truncation)
+ * Works for models of lc_learn / lc_learn_w (sharded ones included), lc_vbem and lc_cluster, on the device of ctx.
+ * LC_EINVAL: D mismatch ("Mismatched dims. of cluster params and obs.!"), a group index outside [0, J), a negative
+ * observation for ExpGamma clusters ("X has to be in the range [0, inf)!", cluster.cpp:742), a freed model.
+ * Without keep_qz the context's qZ holds intermediate values afterwards. */
+int lc_model_predict(lc_model* m, lc_ctx* ctx, const int* groups /* [J of ctx] or NULL */, int keep_qz);
+/* rows [row0, row0+n) of block j of the last prediction on ctx (like lc_ctx_get_qz_rows); any output may be NULL */
+int lc_ctx_get_predictions(lc_ctx* ctx, int j, int64_t row0, int64_t n, int32_t* label, double* logZ, double* logp);
+/* free the training observations and qZ (and shards) of a model; its parameters stay, so lc_model_predict still works
+ * while the qZ accessors return LC_EINVAL.  A borrowed context (lc_vbem, lc_cluster) is left to its owner. */
+int lc_model_release_data(lc_model* m);
+/* expected weights of WeightDist::update(Nk) (distributions.cpp:124-168, 186-196, 242-256): Epi[K] = E[pi_k],
+ * *Erest (may be NULL) = E[pi_rest], the mass beyond the truncation.  Dirichlet: alpha_k / sum(alpha), rest 0.
+ * StickBreak: E[v_k] prod_{i before k} E[1 - v_i], E[v] = a1 / (a1 + a2), "before" in ordvec order (:139-165), rest
+ * prod_i E[1 - v_i].  GDirichlet: the last stick of ordvec has v = 1 (:184-194), rest 0. */
+int lc_weights_predictive(int wkind, double wprior, const double* Nk, int K, double* Epi, double* Erest);
+
 /* ======================================================================== *
  * Two-level models: learnSCM (libcluster.h:583-596, scluster.cpp:578-605) and
  * learnMCM (libcluster.h:661-676, mcluster.cpp:613-642).

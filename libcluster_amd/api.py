@@ -10,8 +10,10 @@ precision, libclusterpy.h:74-135).
 Additive keyword-only extras: ``return_info=True`` appends a dict (rounds with every free energy, cluster
 posteriors, E[log weights]), ``device`` picks the GPU, ``concentration`` / ``alpha`` set the weight prior the C++ API
 takes through its ``weights`` argument, ``qY0`` gives learnSCM / learnMCM a reproducible start, ``nthreads`` is an
-alias of ``threads``.  learnDGMM / learnBEMM / learnDGMC / learnEGMC are not in the reference's Python module
-(they are in its C++ API, include/libcluster.h:262-315, 462-523) and follow the same conventions."""
+alias of ``threads``, ``return_model=True`` (the eight flat and grouped learners) appends the open ``capi.Model`` as
+the last element, whose ``predict(Xnew)`` scores new observations (labels, responsibilities, log density).
+learnDGMM / learnBEMM / learnDGMC / learnEGMC are not in the reference's Python module (they are in its C++ API,
+include/libcluster.h:262-315, 462-523) and follow the same conventions."""
 from __future__ import annotations
 
 import os
@@ -33,7 +35,7 @@ def _threads(threads, nthreads):
     return max(1, min(32, os.cpu_count() or 1))  # omp_get_max_threads() in the reference
 
 
-def _result(F, model, rows, grouped, return_info):
+def _result(F, model, rows, grouped, return_info, return_model=False):
     J, K, D = model.dims()
     qZ = model.qz_all(rows)
     w = [np.exp(model.weights(j)[0]).reshape(-1, 1) for j in range(J)]  # ArrayXd -> (K, 1)
@@ -43,71 +45,81 @@ def _result(F, model, rows, grouped, return_info):
     covs = [c.get("cov") if c.get("cov") is None or c["cov"].ndim == 2 else c["cov"].reshape(1, -1) for c in cl]
     info = {"K": K, "N": [c["N"] for c in cl], "rounds": model.rounds(), "clusters": cl,
             "Elogweight": [model.weights(j)[0] for j in range(J)]}
-    model.close()
+    if not return_model:
+        model.close()
     out = (F, qZ, w, means, covs) if grouped else (F, qZ[0], w[0], means, covs)
-    return out + (info,) if return_info else out
+    out = out + (info,) if return_info else out
+    return out + (model,) if return_model else out
 
 
-def _flat(algo, X, wprior, prior, maxclusters, verbose, threads, nthreads, device, return_info):
+def _flat(algo, X, wprior, prior, maxclusters, verbose, threads, nthreads, device, return_info, return_model):
     F, m, rows = capi.learn(algo, np.asarray(X, dtype=np.float64), wprior, _f32(prior), maxclusters, False, verbose,
                             _threads(threads, nthreads), device)
-    return _result(F, m, rows, False, return_info)
+    return _result(F, m, rows, False, return_info, return_model)
 
 
-def _grouped(algo, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info):
+def _grouped(algo, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info, return_model):
     F, m, rows = capi.learn(algo, [np.asarray(x, dtype=np.float64) for x in X], 1.0, _f32(prior), maxclusters,
                             sparse, verbose, _threads(threads, nthreads), device)
-    return _result(F, m, rows, True, return_info)
+    return _result(F, m, rows, True, return_info, return_model)
 
 
 def learnVDP(X, prior=1.0, maxclusters=-1, verbose=False, threads=None, *, nthreads=None, concentration=1.0,
-             device=0, return_info=False):
+             device=0, return_info=False, return_model=False):
     """libclusterpy.h:300-320 / include/libcluster.h:177-186.  Returns (f, qZ, w, mu, cov)."""
-    return _flat(capi.ALGO_VDP, X, concentration, prior, maxclusters, verbose, threads, nthreads, device, return_info)
+    return _flat(capi.ALGO_VDP, X, concentration, prior, maxclusters, verbose, threads, nthreads, device, return_info,
+                 return_model)
 
 
 def learnBGMM(X, prior=1.0, maxclusters=-1, verbose=False, threads=None, *, nthreads=None, alpha=1.0, device=0,
-              return_info=False):
+              return_info=False, return_model=False):
     """libclusterpy.h:322-342 / include/libcluster.h:218-227.  Returns (f, qZ, w, mu, cov)."""
-    return _flat(capi.ALGO_BGMM, X, alpha, prior, maxclusters, verbose, threads, nthreads, device, return_info)
+    return _flat(capi.ALGO_BGMM, X, alpha, prior, maxclusters, verbose, threads, nthreads, device, return_info,
+                 return_model)
 
 
 def learnGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads=None, *, nthreads=None, device=0,
-             return_info=False):
+             return_info=False, return_model=False):
     """libclusterpy.h:344-368 / include/libcluster.h:356-366.  X: list of (N_j, D) arrays.
     Returns (f, qZ, w, mu, cov) with qZ and w lists over the groups."""
-    return _grouped(capi.ALGO_GMC, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info)
+    return _grouped(capi.ALGO_GMC, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info,
+                    return_model)
 
 
 def learnSGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads=None, *, nthreads=None, device=0,
-              return_info=False):
+              return_info=False, return_model=False):
     """libclusterpy.h:370-395 / include/libcluster.h:409-419 (one Dirichlet per group)."""
-    return _grouped(capi.ALGO_SGMC, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info)
+    return _grouped(capi.ALGO_SGMC, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info,
+                    return_model)
 
 
 def learnDGMM(X, prior=1.0, maxclusters=-1, verbose=False, threads=None, *, nthreads=None, alpha=1.0, device=0,
-              return_info=False):
+              return_info=False, return_model=False):
     """include/libcluster.h:262-271 (diagonal Gaussians, NormGamma).  cov holds the (1, D) vectors getcov() returns."""
-    return _flat(capi.ALGO_DGMM, X, alpha, prior, maxclusters, verbose, threads, nthreads, device, return_info)
+    return _flat(capi.ALGO_DGMM, X, alpha, prior, maxclusters, verbose, threads, nthreads, device, return_info,
+                 return_model)
 
 
 def learnBEMM(X, prior=1.0, maxclusters=-1, verbose=False, threads=None, *, nthreads=None, alpha=1.0, device=0,
-              return_info=False):
+              return_info=False, return_model=False):
     """include/libcluster.h:306-315 (exponential mixture).  ValueError if X has a negative entry; mu holds the
     clusters' getrate(), cov is a list of None."""
-    return _flat(capi.ALGO_BEMM, X, alpha, prior, maxclusters, verbose, threads, nthreads, device, return_info)
+    return _flat(capi.ALGO_BEMM, X, alpha, prior, maxclusters, verbose, threads, nthreads, device, return_info,
+                 return_model)
 
 
 def learnDGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads=None, *, nthreads=None, device=0,
-              return_info=False):
+              return_info=False, return_model=False):
     """include/libcluster.h:462-472.  X is a list of (N_j, D) arrays."""
-    return _grouped(capi.ALGO_DGMC, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info)
+    return _grouped(capi.ALGO_DGMC, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info,
+                    return_model)
 
 
 def learnEGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads=None, *, nthreads=None, device=0,
-              return_info=False):
+              return_info=False, return_model=False):
     """include/libcluster.h:513-523.  X is a list of non-negative (N_j, D) arrays."""
-    return _grouped(capi.ALGO_EGMC, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info)
+    return _grouped(capi.ALGO_EGMC, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info,
+                    return_model)
 
 
 def _topic_result(F, m, mcm, return_info):

@@ -6,6 +6,7 @@ from __future__ import annotations
 import ctypes as C
 import re
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 
@@ -26,6 +27,14 @@ c_int_p = C.POINTER(C.c_int)
 c_ubyte_p = C.POINTER(C.c_ubyte)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
 COMM_ID_BYTES = 128
+
+
+class Prediction(NamedTuple):
+    """Per-row outputs of Model.predict (lc_model_predict): label (int32), logZ, logp, qZ ((N, K) or None)."""
+    label: np.ndarray
+    logZ: np.ndarray
+    logp: np.ndarray
+    qZ: np.ndarray | None
 
 
 def comm_unique_id() -> bytes:
@@ -212,6 +221,11 @@ def lib() -> C.CDLL:
                               c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
     L.lc_eg_mstep.argtypes = [C.c_double, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p,
                               c_double_p, c_double_p]
+    c_int32_p = C.POINTER(C.c_int32)
+    L.lc_model_predict.argtypes = [C.c_void_p, C.c_void_p, c_int_p, C.c_int]
+    L.lc_ctx_get_predictions.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_int32_p, c_double_p, c_double_p]
+    L.lc_model_release_data.argtypes = [C.c_void_p]
+    L.lc_weights_predictive.argtypes = [C.c_int, C.c_double, c_double_p, C.c_int, c_double_p, c_double_p]
     _lib = L
     return L
 
@@ -517,6 +531,16 @@ class Context:
         check(fn(self._h, out, len(self.TIMING_FIELDS)))
         return {k: (int(v) if k.endswith(("_calls", "_iters")) else float(v)) for k, v in zip(self.TIMING_FIELDS, out)}
 
+    def get_predictions(self, j, row0, n, logp=True):
+        """Rows [row0, row0+n) of block j of the last Model.predict_context on this context -> (label int32, logZ,
+        logp) arrays (logp None when logp=False)."""
+        label, logZ = np.zeros(n, dtype=np.int32), np.zeros(n)
+        lp = np.zeros(n) if logp else None
+        if n:
+            check(lib().lc_ctx_get_predictions(self._h, j, row0, n, label.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               dptr(logZ), dptr(lp)))
+        return label, logZ, lp
+
     def synchronize(self):
         check(lib().lc_ctx_synchronize(self._h))
 
@@ -634,6 +658,37 @@ class Model:
         check(lib().lc_model_fenergy(self._h, dptr(Fw), dptr(Fc)))
         return Fw, Fc
 
+    # -- prediction ----------------------------------------------------------------------------------
+    def predict_context(self, ctx, groups=None, keep_qz=False):
+        """Score the observations resident in ctx (lc_model_predict): block b with the weights of learned group
+        groups[b] (None: 0).  Nothing is downloaded: read the rows with ctx.get_predictions / ctx.get_qz."""
+        g = None
+        if groups is not None:
+            garr = np.ascontiguousarray(groups, dtype=np.int32)
+            if garr.shape != (ctx.dims()[0],):
+                raise ValueError("groups needs one learned group index per block of the context")
+            g = garr.ctypes.data_as(C.POINTER(C.c_int))
+        check(lib().lc_model_predict(self._h, ctx._h, g, int(keep_qz)))
+
+    def predict(self, X, groups=None, qz=False, device=0):
+        """Prediction(label, logZ, logp, qZ) for the host rows X ((N, D) array), or a list of them for a list of
+        blocks (block b scored with learned group groups[b], default 0).  qZ is None unless qz=True."""
+        blocks = isinstance(X, (list, tuple))
+        Xs = list(X) if blocks else [X]
+        Xs = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, self.dims()[2])) for x in Xs]
+        with Context(device) as ctx:
+            ctx.set_data(Xs)
+            self.predict_context(ctx, groups, keep_qz=qz)
+            rows = [x.shape[0] for x in Xs]
+            qs = ctx.get_qz(rows) if qz else [None] * len(Xs)
+            out = [Prediction(*ctx.get_predictions(j, 0, n), None if q is None else q.copy())
+                   for j, (n, q) in enumerate(zip(rows, qs))]
+        return out if blocks else out[0]
+
+    def release_data(self):
+        """Free the training observations and qZ; the parameters (and predict) stay."""
+        check(lib().lc_model_release_data(self._h))
+
 
 def learn(algo, X, wprior=1.0, clusterprior=1.0, maxclusters=-1, sparse=False, verbose=False, nthreads=1, device=0,
           wprior_j=None):
@@ -658,6 +713,14 @@ def learn(algo, X, wprior=1.0, clusterprior=1.0, maxclusters=-1, sparse=False, v
 def trim_cache():
     """Return every cached device / page-locked block to the driver."""
     check(lib().lc_trim_cache())
+
+
+def weights_predictive(wkind, Nk, wprior=1.0):
+    """E[pi_k] of the weights updated with Nk, and the mass beyond the truncation (StickBreak; 0 otherwise)."""
+    Nk = np.ascontiguousarray(Nk, dtype=np.float64)
+    e, r = np.zeros(Nk.size), C.c_double()
+    check(lib().lc_weights_predictive(wkind, wprior, dptr(Nk), Nk.size, dptr(e), C.byref(r)))
+    return e, r.value
 
 
 def weights_update(wkind, Nk, wprior=1.0):

@@ -22,6 +22,25 @@
 #include "lc_engine.hpp"
 #include "lc_topic.hpp"
 #include "lc_host.hpp"
+#include "lc_predict.hpp"
+
+#include <mutex>
+#include <unordered_set>
+
+namespace {
+// every lc_model that exists: lc_model_predict / lc_model_release_data answer LC_EINVAL for a handle that was freed
+std::mutex g_models_mu;
+std::unordered_set<const void*> g_models;
+void model_registry(const void* m, bool add) {
+  std::lock_guard<std::mutex> g(g_models_mu);
+  if (add) g_models.insert(m);
+  else g_models.erase(m);
+}
+bool model_alive(const void* m) {
+  std::lock_guard<std::mutex> g(g_models_mu);
+  return g_models.count(m) != 0;
+}
+}  // namespace
 
 struct lc_ctx {
   lcc::Context impl;
@@ -29,6 +48,10 @@ struct lc_ctx {
 };
 
 struct lc_model {
+  lc_model() { model_registry(this, true); }
+  ~lc_model() { model_registry(this, false); }
+  lc_model(const lc_model&) = delete;
+  lc_model& operator=(const lc_model&) = delete;
   std::unique_ptr<lc_ctx> owned_ctx;  // set by lc_learn
   lc_ctx* ctx = nullptr;              // context holding qZ (owned or borrowed)
   lce::Model model;
@@ -53,6 +76,7 @@ struct lc_model {
   std::vector<std::unique_ptr<Shard>> shards;
   bool rows_sharded = false;
   std::vector<int64_t> Nj;  // global group sizes
+  bool sparse = false;      // learned in sparse mode: prediction applies the same Kful rule (cluster.cpp:107-112)
 };
 
 struct lc_tmodel {
@@ -743,6 +767,7 @@ int lc_vbem(lc_ctx* ctx, lc_model** model, int wkind, int ckind, double wprior, 
       throw std::invalid_argument("model was created with other distribution kinds");
     }
     m->ctx = ctx;
+    m->sparse = sparse != 0;
     std::vector<double> tr;
     lce::VbemOptions vo;
     vo.clusterprior = clusterprior;
@@ -801,6 +826,7 @@ int lc_learn_w(int algo, int J, const double* const* Xj, const int64_t* Nj, int 
     }
     std::unique_ptr<lc_model> m(new lc_model());
     m->D = D;
+    m->sparse = !single && sparse;  // (the single-matrix learners pass sparse=false)
     bool same_device = false;
     const int ngpu = requested_gpus(&same_device);
     // LIBCLUSTER_FORCE_SHARDED=1 (tests): take the sharded path with a single shard too (ncclCommInitAll on one device)
@@ -847,6 +873,7 @@ int lc_cluster(lc_ctx* ctx, int wkind, int ckind, double wprior, double clusterp
     m->D = ctx->impl.D();
     m->model.wkind = wkind;
     m->model.ckind = ckind;
+    m->sparse = sparse != 0;
     if (ctx->impl.J() == 1 && wkind != lch::W_GDIRICHLET) m->model.weights.emplace_back(wkind, wprior);
     lce::ClusterOptions co;
     co.clusterprior = clusterprior;
@@ -1052,6 +1079,55 @@ int lc_model_fenergy(lc_model* m, double* Fw, double* Fc) {
       for (size_t j = 0; j < m->model.weights.size(); ++j) Fw[j] = m->model.weights[j].fenergy();
     if (Fc)
       for (size_t k = 0; k < m->model.clusters.size(); ++k) Fc[k] = m->model.clusters[k].fenergy();
+  });
+}
+
+// ---- prediction ------------------------------------------------
+// vbexpectation (cluster.cpp:91-138) with the model's final posteriors on new observations, plus the posterior
+// predictive density; the reference's users call clusters[k].Eloglike(Xnew) (distributions.cpp:356-370) per cluster.
+int lc_model_predict(lc_model* m, lc_ctx* ctx, const int* groups, int keep_qz) {
+  return guarded([&] {
+    need(m, "model");
+    need(ctx, "ctx");
+    if (!model_alive(m)) throw std::invalid_argument("the model was freed");
+    if (ctx->impl.D() != m->D) throw std::invalid_argument("Mismatched dims. of cluster params and obs.!");  // vbem, :193
+    const int J = (int)m->model.weights.size();
+    for (int b = 0; b < ctx->impl.J(); ++b) {
+      const int j = groups ? groups[b] : 0;
+      if (j < 0 || j >= J) throw std::invalid_argument("group index out of range");
+    }
+    lcp::predict(ctx->impl, m->model, m->sparse, groups, keep_qz != 0);
+  });
+}
+
+int lc_ctx_get_predictions(lc_ctx* ctx, int j, int64_t row0, int64_t n, int32_t* label, double* logZ, double* logp) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.get_predictions(j, row0, n, label, logZ, logp);
+  });
+}
+
+int lc_model_release_data(lc_model* m) {
+  return guarded([&] {
+    need(m, "model");
+    if (!model_alive(m)) throw std::invalid_argument("the model was freed");
+    m->shards.clear();
+    m->owned_ctx.reset();
+    m->ctx = nullptr;  // (a borrowed context stays with its owner)
+  });
+}
+
+int lc_weights_predictive(int wkind, double wprior, const double* Nk, int K, double* Epi, double* Erest) {
+  return guarded([&] {
+    need(Nk, "Nk");
+    need(Epi, "Epi");
+    if (wkind < 0 || wkind > 2) throw std::invalid_argument("unknown weight kind");
+    if (K < 1) throw std::invalid_argument("K must be >= 1");
+    lch::WeightState w(wkind, wprior);
+    w.update(Nk, K);
+    double rest = 0.0;
+    lcp::weights_predictive(w, Epi, &rest);
+    if (Erest) *Erest = rest;
   });
 }
 

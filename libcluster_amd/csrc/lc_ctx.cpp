@@ -13,15 +13,6 @@
 
 namespace lcc {
 
-#define LC_HIP(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess)                                                                              \
-      throw HipFailure(std::string("HIP error: ") + hipGetErrorString(e_) + " in " #expr " (" __FILE__ \
-                                                                            ":" +                      \
-                       std::to_string(__LINE__) + ")");                                                \
-  } while (0)
-
 // Freed device / page-locked blocks are kept for re-use: the split search builds and tears down a sub-context per
 // attempt, and hipFree / hipHostFree (50-340 us each, the former also a device-wide synchronisation) were 6 % of a
 // model-selection run.  Blocks are matched best-fit within 2x; the device cache is capped at 16 GiB per process
@@ -270,6 +261,7 @@ void Context::build_layout(int J, const int64_t* Nj, int D) {
   // (the responsibility buffers are sized by rows x columns: a new row count means new buffers)
   qz_[0].K = qz_[1].K = 0;
   qz_[0].cap = qz_[1].cap = 0;
+  pred_vb_ = pred_logp_ = false;  // (the per-row prediction outputs belong to the old rows)
   LC_HIP(hipSetDevice(device_));
   X_.reserve((size_t)std::max<int64_t>(NP_, 1) * DP_);
   goff_d_.reserve(J + 1);

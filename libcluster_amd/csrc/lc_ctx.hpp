@@ -19,6 +19,14 @@ namespace lcc {
 struct HipFailure : std::runtime_error {
   explicit HipFailure(const std::string& s) : std::runtime_error(s) {}
 };
+// a failing HIP call throws HipFailure with the call's text and place (every translation unit of the context)
+#define LC_HIP(expr)                                                                                          \
+  do {                                                                                                        \
+    hipError_t e_ = (expr);                                                                                   \
+    if (e_ != hipSuccess)                                                                                     \
+      throw ::lcc::HipFailure(std::string("HIP error: ") + hipGetErrorString(e_) + " in " #expr " (" __FILE__ \
+                              ":" + std::to_string(__LINE__) + ")");                                          \
+  } while (0)
 // hipMalloc said no (after the block cache was trimmed): optional accelerations catch this one and take their ordinary path
 struct AllocFailure : HipFailure {
   explicit AllocFailure(const std::string& s) : HipFailure(s) {}
@@ -244,6 +252,19 @@ class Context {
   // N_k, x_s = sum q x [K*D], xx_s = sum q x^2 [K*D] (elementwise), Njk[J*K]
   void suffstat_diag(const unsigned char* smask, double* Nk, double* xs, double* xxs, double* Njk);
 
+  // ---- prediction (lc_predict.cpp) -------------------------------------------------------------------
+  // After a raw E-step with zero constants left at least max(K, Kp) columns in qZ: per row the label, logZ and (Kp > 0,
+  // Gauss-Wishart) logp into the context's per-row outputs (lck::PredictRowsLaunch for the tables: c, pc J x K / J x Kp
+  // row-major, ps, pe Kp).  keep_q: the K columns become the responsibilities.  qZ is left K columns wide.
+  void predict_rows(int K, int Kp, const double* c, const double* pc, const double* ps, const double* pe, bool keep_q);
+  // Separable families: logp per row (lck::PredictDiagLaunch; mode 0 NormGamma, 1 ExpGamma; a, w: Kp x D host arrays,
+  // pc: J x Kp, pe: Kp).  Returns false, when mode 1 met a negative observation.
+  bool predict_diag(int mode, int Kp, const double* a, const double* w, const double* pc, const double* pe);
+  // rows [row0, row0+n) of group j of the last prediction (any output may be null)
+  void get_predictions(int j, int64_t row0, int64_t n, int32_t* label, double* logZ, double* logp) const;
+  // no prediction is readable until the next one completes (a prediction that fails leaves none behind)
+  void predict_clear() { pred_vb_ = pred_logp_ = false; }
+
   // Host work to run while the NEXT normalising E-step is on the device: the E-step calls it once, after its last
   // launch and before it waits for the stream (vbem hands over the free-energy terms that depend on the posteriors
   // only).  A hook that is still pending when the E-step returns was not called; the owner runs it itself.
@@ -376,6 +397,10 @@ class Context {
   DevBuf<int> selcnt_;
   DevBuf<int64_t> seloff_;
   DevBuf<double> mv_;
+  // per-row outputs of the last prediction ([NP] each; valid until the observations change) and its small tables
+  DevBuf<int> plabel_, pflag_;
+  DevBuf<double> plogz_, plogp_, ptab_;
+  bool pred_vb_ = false, pred_logp_ = false;
   PinnedBuf hpack_, hred_, hss_, hmask_;
   std::function<void()> overlap_;
 

@@ -1,0 +1,287 @@
+// Prediction with a learned mixture: the host arithmetic (expected weights, the per-cluster predictive
+// constants of the three families, the zero-constant parameter sets of the raw E-step) and the context's side of the
+// pass.  Kernels: lc_kernels_predict.hip.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "lc_ctx.hpp"
+#include "lc_engine.hpp"
+#include "lc_host.hpp"
+#include "lc_predict.hpp"
+
+namespace lcc {
+
+void Context::predict_rows(int K, int Kp, const double* c, const double* pc, const double* ps, const double* pe,
+                           bool keep_q) {
+  use_device();
+  if (K < 1 || Kp < 0) throw std::invalid_argument("K must be >= 1");
+  pred_vb_ = false;
+  if (NP_ == 0) {
+    qz_[cur_].K = K;
+    pred_vb_ = true;
+    pred_logp_ = pred_logp_ || Kp > 0;
+    return;
+  }
+  if (qz_[cur_].cap < std::max(K, Kp) || !qz_[cur_].buf.p) throw std::logic_error("predict_rows: no raw E-step columns");
+  plabel_.reserve((size_t)NP_);
+  plogz_.reserve((size_t)NP_);
+  if (Kp > 0) plogp_.reserve((size_t)NP_);
+  // tables: [c J x K | pc J x Kp | ps Kp | pe Kp]
+  const size_t nc = (size_t)J_ * K, np = (size_t)J_ * Kp;
+  hpack_.resize(nc + np + 2 * (size_t)Kp);
+  std::copy(c, c + nc, hpack_.data());
+  if (Kp > 0) {
+    std::copy(pc, pc + np, hpack_.data() + nc);
+    std::copy(ps, ps + Kp, hpack_.data() + nc + np);
+    std::copy(pe, pe + Kp, hpack_.data() + nc + np + Kp);
+  }
+  ptab_.reserve(hpack_.size());
+  LC_HIP(hipMemcpyAsync(ptab_.p, hpack_.data(), hpack_.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+  lck::PredictRowsLaunch a;
+  a.col = qz_[cur_].buf.p;
+  a.qcol = qz_[cur_].buf.p;
+  a.ldq = NP_;
+  a.K = K;
+  a.Kp = Kp;
+  a.nrg = NP_ / lck::RG;
+  a.rginfo = J_ > 1 ? rginfo_.p : nullptr;
+  a.nrows = Nj_[0];
+  a.ctab = ptab_.p;
+  a.ptab = ptab_.p + nc;
+  a.pscale = ptab_.p + nc + np;
+  a.pexp = ptab_.p + nc + np + Kp;
+  a.keep_q = keep_q ? 1 : 0;
+  a.label = plabel_.p;
+  a.logZ = plogz_.p;
+  a.logp = Kp > 0 ? plogp_.p : nullptr;
+  LC_HIP(lck::launch_predict_rows(a, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ and ptab_ are free again)
+  qz_[cur_].K = K;
+  qz_[cur_].hash_ok = false;
+  pred_vb_ = true;
+  pred_logp_ = pred_logp_ || Kp > 0;
+}
+
+bool Context::predict_diag(int mode, int Kp, const double* av, const double* w, const double* pc, const double* pe) {
+  use_device();
+  if (Kp < 1) throw std::invalid_argument("K must be >= 1");
+  pred_logp_ = false;
+  if (NP_ == 0) {
+    pred_logp_ = true;
+    return true;
+  }
+  const int D = D_, DP = DP_;
+  plogp_.reserve((size_t)NP_);
+  pflag_.reserve(1);
+  // tables: [a Kp x DP | w Kp x DP | pc J x Kp | pe Kp], pad columns zero (a factor of exactly one)
+  const size_t nw = (size_t)Kp * DP, np = (size_t)J_ * Kp;
+  hpack_.assign(2 * nw + np + (size_t)Kp, 0.0);
+  for (int k = 0; k < Kp; ++k) {
+    std::copy(av + (size_t)k * D, av + (size_t)(k + 1) * D, hpack_.data() + (size_t)k * DP);
+    std::copy(w + (size_t)k * D, w + (size_t)(k + 1) * D, hpack_.data() + nw + (size_t)k * DP);
+  }
+  std::copy(pc, pc + np, hpack_.data() + 2 * nw);
+  std::copy(pe, pe + Kp, hpack_.data() + 2 * nw + np);
+  ptab_.reserve(hpack_.size());
+  LC_HIP(hipMemcpyAsync(ptab_.p, hpack_.data(), hpack_.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+  LC_HIP(hipMemsetAsync(pflag_.p, 0, sizeof(int), stream_));
+  lck::PredictDiagLaunch a;
+  a.mode = mode;
+  a.X = X_.p;
+  a.DP = DP;
+  a.nrg = NP_ / lck::RG;
+  a.rginfo = J_ > 1 ? rginfo_.p : nullptr;
+  a.nrows = Nj_[0];
+  a.Kp = Kp;
+  a.a = ptab_.p;
+  a.w = ptab_.p + nw;
+  a.ptab = ptab_.p + 2 * nw;
+  a.pexp = ptab_.p + 2 * nw + np;
+  a.logp = plogp_.p;
+  a.flag = pflag_.p;
+  LC_HIP(lck::launch_predict_diag(a, stream_));
+  int flag = 0;
+  LC_HIP(hipMemcpyAsync(&flag, pflag_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+  if (flag) return false;
+  pred_logp_ = true;
+  return true;
+}
+
+void Context::get_predictions(int j, int64_t row0, int64_t n, int32_t* label, double* logZ, double* logp) const {
+  use_device();
+  if (j < 0 || j >= J_ || row0 < 0 || n < 0 || row0 + n > Nj_[j]) throw std::invalid_argument("row range out of bounds");
+  if (!pred_vb_) throw std::invalid_argument("the context holds no prediction (lc_model_predict)");
+  if (logp && !pred_logp_) throw std::invalid_argument("the context's prediction has no log density");
+  if (n == 0) return;
+  const size_t at = (size_t)(goff_[j] + row0);
+  if (label) LC_HIP(hipMemcpyAsync(label, plabel_.p + at, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, stream_));
+  if (logZ) LC_HIP(hipMemcpyAsync(logZ, plogz_.p + at, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  if (logp) LC_HIP(hipMemcpyAsync(logp, plogp_.p + at, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+}
+
+}  // namespace lcc
+
+namespace lcp {
+
+void weights_predictive(const lch::WeightState& w, double* Epi, double* Erest) {
+  const int K = (int)w.alpha1.size();
+  if (w.kind == lch::W_DIRICHLET) {
+    double asum = 0.0;
+    for (int k = 0; k < K; ++k) asum += w.alpha1[(size_t)k];
+    for (int k = 0; k < K; ++k) Epi[k] = w.alpha1[(size_t)k] / asum;
+    *Erest = 0.0;
+    return;
+  }
+  // the sticks in ordvec order (equal counts in the order of the reference's sort, which update() repeats)
+  double rest = 1.0;
+  for (size_t idx = 0; idx < w.ordvec.size(); ++idx) {
+    const int k = w.ordvec[idx].first;
+    const double a1 = w.alpha1[(size_t)k], a2 = w.alpha2[(size_t)k];
+    if (w.kind == lch::W_GDIRICHLET && idx + 1 == w.ordvec.size()) {  // v = 1 (distributions.cpp:184-194)
+      Epi[k] = rest;
+      rest = 0.0;
+      break;
+    }
+    Epi[k] = a1 / (a1 + a2) * rest;
+    rest *= a2 / (a1 + a2);
+  }
+  *Erest = rest;
+}
+
+namespace {
+
+// the family's predictive of one cluster: log P(x) = lc - e * sum_d log1p(term_d(x)) (Gauss-Wishart: term = s d^2)
+struct Predictive {
+  double lc = 0.0, e = 0.0, s = 0.0;
+  std::vector<double> a, w;  // separable families: term_d = w_d (x_d - a_d)^2 (NormGamma) / w_d x_d (ExpGamma)
+};
+
+Predictive gw_predictive(const lch::GaussWishState& g) {
+  const int D = g.D;
+  const double nup = g.nu + 1 - D;  // Student-t degrees of freedom
+  Predictive p;
+  p.lc = lch::lgam((g.nu + 1) / 2) - lch::lgam(nup / 2) - 0.5 * D * std::log(nup * lch::PI) +
+         0.5 * (D * std::log(nup * g.beta / (1 + g.beta)) + g.logdW);
+  p.s = g.beta / ((1 + g.beta) * g.nu);  // d^2 = nu maha_W(x): the distance the E-step forms
+  p.e = (g.nu + 1) / 2;
+  return p;
+}
+
+Predictive ng_predictive(const lch::NormGammaState& g) {
+  const int D = g.D;
+  Predictive p;
+  p.lc = D * (lch::lgam(g.nu + 0.5) - lch::lgam(g.nu) - 0.5 * std::log(2 * lch::PI * (1 + g.beta) / g.beta)) -
+         0.5 * g.logL;
+  p.e = g.nu + 0.5;
+  p.a = g.m;
+  p.w.resize((size_t)D);
+  for (int d = 0; d < D; ++d) p.w[(size_t)d] = g.beta / (2 * (1 + g.beta) * g.L[(size_t)d]);
+  return p;
+}
+
+Predictive eg_predictive(const lch::ExpGammaState& g) {
+  Predictive p;
+  p.lc = g.D * std::log(g.a) - g.logb;
+  p.e = g.a + 1;
+  p.a.assign((size_t)g.D, 0.0);
+  p.w = g.ib;
+  return p;
+}
+
+Predictive predictive(const lch::ClusterAny& c) {
+  return c.kind == lch::C_GAUSSWISH ? gw_predictive(c.gw) : c.kind == lch::C_NORMGAMMA ? ng_predictive(c.ng)
+                                                                                        : eg_predictive(c.eg);
+}
+
+}  // namespace
+
+void predict(lcc::Context& ctx, const lce::Model& model, bool sparse, const int* groups, bool keep_qz) {
+  const int K = (int)model.clusters.size(), J = (int)model.weights.size(), D = ctx.D(), Jc = ctx.J();
+  if (K < 1) throw std::invalid_argument("the model has no clusters");
+  ctx.predict_clear();  // (whatever an earlier prediction left must not outlive a failure of this one)
+  const int ck = model.ckind;
+  // expected weights of every learned group; the prior component takes the mass beyond the truncation (StickBreak)
+  std::vector<double> Epi((size_t)J * K), Erest((size_t)J);
+  bool rest = false;
+  for (int j = 0; j < J; ++j) {
+    if ((int)model.weights[(size_t)j].alpha1.size() != K) throw std::invalid_argument("weights and clusters disagree");
+    weights_predictive(model.weights[(size_t)j], Epi.data() + (size_t)j * K, &Erest[(size_t)j]);
+    rest = rest || Erest[(size_t)j] > 0.0;
+  }
+  const int Kp = K + (rest ? 1 : 0);
+  std::vector<Predictive> pr((size_t)Kp);
+  std::vector<double> cst((size_t)K);
+  for (int k = 0; k < K; ++k) {
+    pr[(size_t)k] = predictive(model.clusters[(size_t)k]);
+    cst[(size_t)k] = model.clusters[(size_t)k].eloglike_const();
+  }
+  const lch::ClusterAny prior(ck, model.clusters[0].prior(), D);  // clearobs state: a cluster that saw no data
+  if (rest) pr[(size_t)K] = predictive(prior);
+
+  // per block of the context: VB constants c (vbexpectation, cluster.cpp:91-138) and predictive constants pc
+  constexpr double NINF = -std::numeric_limits<double>::infinity();
+  std::vector<double> c((size_t)Jc * K), pc((size_t)Jc * Kp), pe((size_t)Kp), ps((size_t)Kp);
+  for (int b = 0; b < Jc; ++b) {
+    const int j = groups ? groups[b] : 0;
+    const lch::WeightState& w = model.weights[(size_t)j];
+    for (int k = 0; k < K; ++k) {
+      const bool active = !sparse || w.Nk[(size_t)k] >= lch::ZEROCUTOFF;  // Kful, cluster.cpp:107-112
+      c[(size_t)b * K + k] = active ? w.Elogpi[(size_t)k] + cst[(size_t)k] : NINF;
+      pc[(size_t)b * Kp + k] = std::log(Epi[(size_t)j * K + k]) + pr[(size_t)k].lc;
+    }
+    if (rest) pc[(size_t)b * Kp + K] = std::log(Erest[(size_t)j]) + pr[(size_t)K].lc;
+  }
+  for (int k = 0; k < Kp; ++k) {
+    pe[(size_t)k] = pr[(size_t)k].e;
+    ps[(size_t)k] = pr[(size_t)k].s;
+  }
+
+  if (ck == lch::C_GAUSSWISH) {
+    // one raw E-step over the K clusters (+ the prior's whitener): -d^2 / 2 per column
+    std::vector<double> A((size_t)Kp * D * D), m((size_t)Kp * D), zero((size_t)Jc * Kp, 0.0);
+    for (int k = 0; k < Kp; ++k) {
+      const lch::GaussWishState& g = k < K ? model.clusters[(size_t)k].gw : prior.gw;
+      const std::vector<double> Ak = g.whitener();
+      std::copy(Ak.begin(), Ak.end(), A.begin() + (size_t)k * D * D);
+      std::copy(g.m.begin(), g.m.end(), m.begin() + (size_t)k * D);
+    }
+    ctx.estep(Kp, A.data(), m.data(), zero.data(), nullptr, nullptr, /*raw=*/true);
+    ctx.predict_rows(K, Kp, c.data(), pc.data(), ps.data(), pe.data(), keep_qz);
+    return;
+  }
+  // separable families: the predictive first (it also checks ExpGamma's domain), then the raw E-step's data terms
+  std::vector<double> av((size_t)Kp * D), wv((size_t)Kp * D);
+  for (int k = 0; k < Kp; ++k) {
+    std::copy(pr[(size_t)k].a.begin(), pr[(size_t)k].a.end(), av.begin() + (size_t)k * D);
+    std::copy(pr[(size_t)k].w.begin(), pr[(size_t)k].w.end(), wv.begin() + (size_t)k * D);
+  }
+  if (!ctx.predict_diag(ck == lch::C_NORMGAMMA ? 0 : 1, Kp, av.data(), wv.data(), pc.data(), pe.data()))
+    throw std::invalid_argument("X has to be in the range [0, inf)!");  // cluster.cpp:742
+  std::vector<double> ra((size_t)K * D), rw2((size_t)K * D), rw1((size_t)K * D), zero((size_t)Jc * K, 0.0);
+  for (int k = 0; k < K; ++k)
+    for (int d = 0; d < D; ++d) {  // the E-step parameters of vbem (lc_engine.cpp), distributions.cpp:486-491, 570-571
+      const size_t i = (size_t)k * D + d;
+      if (ck == lch::C_NORMGAMMA) {
+        const lch::NormGammaState& g = model.clusters[(size_t)k].ng;
+        ra[i] = g.m[(size_t)d];
+        rw2[i] = -0.5 * g.nu / g.L[(size_t)d];
+        rw1[i] = 0.0;
+      } else {
+        const lch::ExpGammaState& g = model.clusters[(size_t)k].eg;
+        ra[i] = 0.0;
+        rw2[i] = 0.0;
+        rw1[i] = -g.a * g.ib[(size_t)d];
+      }
+    }
+  ctx.estep_diag(K, ra.data(), rw2.data(), rw1.data(), zero.data(), nullptr, nullptr, /*raw=*/true);
+  ctx.predict_rows(K, 0, c.data(), nullptr, nullptr, nullptr, keep_qz);
+}
+
+}  // namespace lcp
