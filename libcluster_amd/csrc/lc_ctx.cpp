@@ -249,6 +249,7 @@ void Context::build_layout(int J, const int64_t* Nj, int D) {
   DP_ = DP;
   DC_ = lck::estep_active_width(D, DP);
   if (lck::test_switch("LC_FULL_WIDTH")) DC_ = DP;  // (tests, libcluster_hip_testhooks.so only: every kernel walks the padded width)
+  sspart_clean_ = false;  // (other idle columns: what was cleared for the old active width says nothing about this one)
   Nj_.assign(Nj, Nj + J);
   goff_.assign(J + 1, 0);
   Ntot_ = 0;
@@ -813,25 +814,83 @@ void Context::qz_split_from(const Context& sub, const RowSelection& sel, int k) 
 // ---------------------------------------------------------------------------
 // hot path
 // ---------------------------------------------------------------------------
+template <class F>
+void Context::timed(Timed kind, F&& launch) {
+  if (!timing_) return launch();
+  EvPair ev{timing_event(), timing_event(), kind};
+  LC_HIP(hipEventRecord(ev.a, stream_));
+  launch();
+  LC_HIP(hipEventRecord(ev.b, stream_));
+  pending_.push_back(ev);
+}
+
 void Context::allreduce(double* dbuf, int64_t count) {
   if (!comm_ && !ar_fn_) return;
-  EvPair ev{};
-  if (timing_) {  // events around the exchange step: the sum plus the wait for the slowest rank
-    ev.a = timing_event();
-    ev.b = timing_event();
-    ev.kind = 3;
-    LC_HIP(hipEventRecord(ev.a, stream_));
-  }
-  if (comm_) {  // RCCL / host-staged sum on this context's stream
-    comm_->allreduce_sum(dbuf, count, stream_);
+  timed(Timed::Allreduce, [&] {  // events around the exchange step: the sum plus the wait for the slowest rank
+    if (comm_) {  // RCCL / host-staged sum on this context's stream
+      comm_->allreduce_sum(dbuf, count, stream_);
+    } else {
+      const int rc = ar_fn_(ar_user_, dbuf, count, (void*)stream_);
+      if (rc != 0) throw std::runtime_error("all-reduce hook failed with status " + std::to_string(rc));
+    }
+  });
+}
+
+// F_z and LL_k of a normalising pass.  On one rank, with rows, nothing is summed over ranks: the folds write straight
+// into the page-locked host buffer (device-visible; complete when the stream synchronises) -- no fill and no copy-back
+// command, which count where a pass lasts 0.1 ms (the copy-back form measured slower).  Otherwise the
+// folds (or zeros, on a rank without rows) go to red_, which is summed over ranks and copied back: always 1 + K values,
+// the LL_k part zeros when it is not wanted, so every rank issues the same collective whatever it holds.
+void Context::enqueue_sums(int64_t grid, int K, bool want_ll) {
+  const size_t n = (size_t)1 + K;
+  const bool direct = !distributed() && grid > 0;
+  hred_.resize(n);  // (before a fold is pointed at it: growing moves the block)
+  if (!direct) red_.reserve(n);
+  double* dst = direct ? hred_.data() : red_.p;
+  if (grid > 0) {
+    redtmp_.reserve((size_t)lck::REDUCE_TMP_ELEMS * 64);
+    LC_HIP(lck::launch_reduce_partials(fzpart_.p, (int)grid, 1, dst, stream_, redtmp_.p));
+    if (want_ll) LC_HIP(lck::launch_reduce_partials(llpart_.p, (int)grid, K, dst + 1, stream_, redtmp_.p));
+    else if (!direct) LC_HIP(hipMemsetAsync(red_.p + 1, 0, (size_t)K * sizeof(double), stream_));
   } else {
-    const int rc = ar_fn_(ar_user_, dbuf, count, (void*)stream_);
-    if (rc != 0) throw std::runtime_error("all-reduce hook failed with status " + std::to_string(rc));
+    LC_HIP(hipMemsetAsync(red_.p, 0, n * sizeof(double), stream_));
   }
-  if (timing_) {
-    LC_HIP(hipEventRecord(ev.b, stream_));
-    pending_.push_back(ev);
+  if (!direct) {
+    allreduce(red_.p, (int64_t)n);
+    LC_HIP(hipMemcpyAsync(hred_.data(), red_.p, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
   }
+}
+
+void Context::read_sums(int K, double* Fz, double* LLk) const {
+  if (Fz) *Fz = hred_[0];
+  if (LLk) std::copy(hred_.data() + 1, hred_.data() + 1 + K, LLk);
+}
+
+// K Gauss-Wishart records in host memory ([N_k | x_s: DP | S: DP x DP], stride stat_stride(DP)) -> the caller's arrays
+// (any may be null)
+static void unpack_gw_records(const double* recs, int K, int D, int DP, double* Nk, double* xs, double* xxs) {
+  const int64_t SS = lck::stat_stride(DP);
+  for (int k = 0; k < K; ++k) {
+    const double* rec = recs + (size_t)k * SS;
+    if (Nk) Nk[k] = rec[0];
+    if (xs) std::copy(rec + 1, rec + 1 + D, xs + (size_t)k * D);
+    if (xxs) {
+      const double* S = rec + 1 + DP;
+      double* o = xxs + (size_t)k * D * D;
+      // the lower triangle is authoritative; mirror it so the result is exactly symmetric
+      for (int i = 0; i < D; ++i)
+        for (int j = 0; j <= i; ++j) o[(size_t)i * D + j] = o[(size_t)j * D + i] = S[(size_t)i * DP + j];
+    }
+  }
+}
+
+// N_jk from the J x K block of a column-sum pass, or (counts == null: one group, whose qZ.colwise().sum() is the N_k just
+// reduced) from the first entry of the K records of stride SS
+static void unpack_counts(const double* recs, int64_t SS, int K, const double* counts, int J, double* Njk) {
+  if (!Njk) return;
+  if (counts) std::copy(counts, counts + (size_t)J * K, Njk);
+  else
+    for (int k = 0; k < K; ++k) Njk[k] = recs[(size_t)k * SS];
 }
 
 double Context::allreduce_value(double v) {
@@ -900,6 +959,34 @@ void Context::pack_estep_params(int K, const double* A, const double* m, const d
   std::memcpy(hpack_.data() + (size_t)K * PS, c, (size_t)J_ * K * sizeof(double));
 }
 
+lck::EstepLaunch Context::gw_estep_launch(int K, const double* A, const double* m, const double* c, const double* X,
+                                          int64_t rows, int64_t nrows, double* out, bool raw, bool want_ll) {
+  pack_estep_params(K, A, m, c);
+  params_.reserve(hpack_.size());
+  LC_HIP(hipMemcpyAsync(params_.p, hpack_.data(), hpack_.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+  lck::EstepLaunch a;
+  a.DP = DP_;
+  a.DC = DC_;
+  a.X = X;
+  a.nrg = rows / lck::RG;
+  a.rginfo = J_ > 1 ? rginfo_.p : nullptr;
+  a.nrows = nrows;
+  a.params = params_.p;
+  a.ctab = params_.p + (size_t)K * lck::estep_pstride(DP_, DC_);  // (also the wide layout beyond DP = 128)
+  a.K = K;
+  a.qZ = out;
+  a.ldq = rows;
+  a.raw = raw ? 1 : 0;
+  for (size_t t = 0; t < (size_t)J_ * K && !a.sparse; ++t)
+    if (c[t] == -std::numeric_limits<double>::infinity()) a.sparse = 1;
+  const int64_t grid = lck::estep_grid(a);  // (a function of the whole launch: shape, raw, sparse)
+  fzpart_.reserve((size_t)std::max<int64_t>(grid, 1));
+  if (want_ll) llpart_.reserve((size_t)std::max<int64_t>(grid, 1) * K);
+  a.fz_part = fzpart_.p;
+  a.ll_part = want_ll ? llpart_.p : nullptr;
+  return a;
+}
+
 void Context::estep(int K, const double* A, const double* m, const double* c, double* Fz, double* LLk, bool raw,
                     double* target) {
   if (K < 1) throw std::invalid_argument("K must be >= 1");
@@ -912,81 +999,21 @@ void Context::estep(int K, const double* A, const double* m, const double* c, do
     return;
   }
   LC_HIP(hipSetDevice(device_));
-  const int DP = DP_;
-  const int64_t PS = lck::estep_pstride(DP, DC_);
-  pack_estep_params(K, A, m, c);
-  params_.reserve(hpack_.size());
-  LC_HIP(hipMemcpyAsync(params_.p, hpack_.data(), hpack_.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
-
   if (!target) {
     ensure_qz(qz_[cur_], K, false);  // E-step overwrites every column
     qz_[cur_].K = K;
   }
-  const int64_t nrg = NP_ / lck::RG;
-  lck::EstepLaunch a;
-  a.DP = DP;
-  a.DC = DC_;
-  a.X = X_.p;
-  a.nrg = nrg;
-  a.rginfo = J_ > 1 ? rginfo_.p : nullptr;
-  a.nrows = Nj_[0];
-  a.params = params_.p;
-  a.ctab = params_.p + (size_t)K * PS;
-  a.K = K;
-  a.qZ = target ? target : qz_[cur_].buf.p;
-  a.ldq = NP_;
-  a.raw = raw ? 1 : 0;
-  for (size_t t = 0; t < (size_t)J_ * K && !a.sparse; ++t)
-    if (c[t] == -std::numeric_limits<double>::infinity()) a.sparse = 1;
-  const int64_t grid = lck::estep_grid(a);  // (a function of the whole launch: shape, raw, sparse)
-  fzpart_.reserve((size_t)std::max<int64_t>(grid, 1));
-  llpart_.reserve((size_t)std::max<int64_t>(grid, 1) * K);
-  red_.reserve((size_t)1 + K);
-  a.fz_part = fzpart_.p;
-  a.ll_part = LLk ? llpart_.p : nullptr;
-  EvPair ev{};
-  if (timing_) {
-    ev.a = timing_event();
-    ev.b = timing_event();
-    ev.kind = 0;
-    LC_HIP(hipEventRecord(ev.a, stream_));
-  }
-  LC_HIP(lck::launch_estep(a, stream_));
-  if (timing_) {
-    LC_HIP(hipEventRecord(ev.b, stream_));
-    pending_.push_back(ev);
-  }
+  const lck::EstepLaunch a =
+      gw_estep_launch(K, A, m, c, X_.p, NP_, Nj_[0], target ? target : qz_[cur_].buf.p, raw, LLk != nullptr);
+  timed(Timed::Estep, [&] { LC_HIP(lck::launch_estep(a, stream_)); });
   if (raw) {
     LC_HIP(hipStreamSynchronize(stream_));
     return;
   }
-  hred_.resize((size_t)1 + K);
-  constexpr bool direct_env = true;  // (the copy-back command instead: measured slower)
-  if (direct_env && !distributed() && grid > 0) {
-    // nothing to sum over ranks: the folds write F_z (and LL_k) straight into the page-locked host buffer
-    redtmp_.reserve((size_t)lck::REDUCE_TMP_ELEMS * 64);
-    LC_HIP(lck::launch_reduce_partials(fzpart_.p, (int)grid, 1, hred_.data(), stream_, redtmp_.p));
-    if (LLk) LC_HIP(lck::launch_reduce_partials(llpart_.p, (int)grid, K, hred_.data() + 1, stream_, redtmp_.p));
-    run_overlap();
-    LC_HIP(hipStreamSynchronize(stream_));
-    if (Fz) *Fz = hred_[0];
-    if (LLk) std::copy(hred_.begin() + 1, hred_.end(), LLk);
-    return;
-  }
-  if (grid > 0) {
-    redtmp_.reserve((size_t)lck::REDUCE_TMP_ELEMS * 64);
-    LC_HIP(lck::launch_reduce_partials(fzpart_.p, (int)grid, 1, red_.p, stream_, redtmp_.p));
-    if (LLk) LC_HIP(lck::launch_reduce_partials(llpart_.p, (int)grid, K, red_.p + 1, stream_, redtmp_.p));
-    else LC_HIP(hipMemsetAsync(red_.p + 1, 0, (size_t)K * sizeof(double), stream_));
-  } else {
-    LC_HIP(hipMemsetAsync(red_.p, 0, (size_t)(1 + K) * sizeof(double), stream_));
-  }
-  allreduce(red_.p, 1 + K);
-  LC_HIP(hipMemcpyAsync(hred_.data(), red_.p, (size_t)(1 + K) * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  enqueue_sums(lck::estep_grid(a), K, LLk != nullptr);
   run_overlap();
   LC_HIP(hipStreamSynchronize(stream_));
-  if (Fz) *Fz = hred_[0];
-  if (LLk) std::copy(hred_.begin() + 1, hred_.end(), LLk);
+  read_sums(K, Fz, LLk);
 }
 
 bool Context::estep_suffstat_fused(int K, const double* A, const double* m, const double* c, double* Fz, double* LLk,
@@ -1009,8 +1036,8 @@ bool Context::estep_suffstat_fused(int K, const double* A, const double* m, cons
   // one buffer for everything that is summed over ranks and copied back: [K records | Fz | LL_k | J x K counts]
   // (the first three are the fold of the kernel's per-block records: one reduction launch)
   // (single group without group sharding: the counts ARE the N_k of the records -- no count block at all)
-  const bool own_counts = J_ > 1 || group_sharded();
-  const size_t nrec = (size_t)W, nout = nrec + (own_counts ? (size_t)J_ * K : 0);
+  const bool counts = own_counts(false);
+  const size_t nrec = (size_t)W, nout = nrec + (counts ? (size_t)J_ * K : 0);
   const size_t ofz = (size_t)K * SS, oll = ofz + 1;
   ssout_.reserve(nout);
   double* njk_d = ssout_.p + nrec;
@@ -1030,27 +1057,18 @@ bool Context::estep_suffstat_fused(int K, const double* A, const double* m, cons
   a.want_ll = LLk != nullptr;
   a.grid = grid;
   a.ngroups = J_;
-  EvPair ev{};
-  if (timing_) {
-    ev.a = timing_event();
-    ev.b = timing_event();
-    ev.kind = 2;
-    LC_HIP(hipEventRecord(ev.a, stream_));
-  }
-  if (grid > 0) LC_HIP(lck::launch_fused(a, stream_));
-  if (timing_) {
-    LC_HIP(hipEventRecord(ev.b, stream_));
-    pending_.push_back(ev);
-  }
+  timed(Timed::Fused, [&] {  // (a rank without rows still counts a fused call)
+    if (grid > 0) LC_HIP(lck::launch_fused(a, stream_));
+  });
   hss_.resize(nout);
   // nothing to sum over ranks: the fold writes straight into the pinned host buffer (coherent, device-visible
-  // memory) and the copy-back command drops off the iteration's critical path
-  constexpr bool direct_env = true;  // (the copy-back command instead: 0.258 against 0.247 ms per iteration in round 2)
-  const bool direct = direct_env && !distributed() && grid > 0;
+  // memory) and the copy-back command drops off the iteration's critical path (with it: 0.258 against 0.247 ms per
+  // iteration in round 2)
+  const bool direct = !distributed() && grid > 0;
   double* dst = direct ? hss_.data() : ssout_.p;
   if (grid > 0) {
     LC_HIP(lck::launch_reduce_partials(sspart_.p, grid, W, dst, stream_));
-    if (own_counts) {
+    if (counts) {
       redtmp_.reserve((size_t)lck::REDUCE_TMP_ELEMS * 64);
       LC_HIP(lck::launch_group_colsum(qz_[cur_].buf.p, NP_, K, goff_d_.p, J_, direct ? dst + nrec : njk_d, stream_,
                                       redtmp_.p, NP_));
@@ -1065,27 +1083,8 @@ bool Context::estep_suffstat_fused(int K, const double* A, const double* m, cons
   }
   run_overlap();
   LC_HIP(hipStreamSynchronize(stream_));
-  for (int k = 0; k < K; ++k) {
-    const double* rec = hss_.data() + (size_t)k * SS;
-    if (Nk) Nk[k] = rec[0];
-    if (xs)
-      for (int d = 0; d < D; ++d) xs[(size_t)k * D + d] = rec[1 + d];
-    if (xxs) {
-      const double* S = rec + 1 + DP;
-      double* o = xxs + (size_t)k * D * D;
-      for (int i = 0; i < D; ++i)
-        for (int j = 0; j <= i; ++j) {  // the lower triangle is authoritative
-          o[(size_t)i * D + j] = S[(size_t)i * DP + j];
-          o[(size_t)j * D + i] = S[(size_t)i * DP + j];
-        }
-    }
-  }
-  if (Njk) {
-    if (!own_counts)
-      for (int k = 0; k < K; ++k) Njk[k] = hss_[(size_t)k * SS];
-    else
-      std::copy(hss_.begin() + nrec, hss_.begin() + nout, Njk);
-  }
+  unpack_gw_records(hss_.data(), K, D, DP, Nk, xs, xxs);
+  unpack_counts(hss_.data(), SS, K, counts ? hss_.data() + nrec : nullptr, J_, Njk);
   if (Fz) *Fz = hss_[ofz];
   if (LLk) std::copy(hss_.begin() + oll, hss_.begin() + oll + K, LLk);
   return true;
@@ -1171,12 +1170,11 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
   const size_t nout = (size_t)K * SS + (size_t)J_ * K;
   ssout_.reserve(nout);
   double* njk_d = ssout_.p + (size_t)K * SS;
-  const bool own_counts = J_ > 1 || group_sharded() || smask != nullptr;  // N_jk from a column-sum pass of their own
+  const bool counts = own_counts(smask != nullptr);
   // Nothing to sum over ranks, one group, no mask: the fold of the per-chunk records writes straight into the page-locked
   // host buffer (device-visible; complete when the stream synchronises) -- no fill and no copy-back command, which
   // count where a pass lasts 0.1 ms (the sub-problems of the split search run thousands of them)
-  constexpr bool direct_env = true;  // (the copy-back command instead: measured slower)
-  const bool direct = direct_env && !distributed() && !own_counts && NP_ > 0;
+  const bool direct = !distributed() && !counts && NP_ > 0;
   hss_.resize(nout);
   if (NP_ > 0) {
     int64_t chunk_rows = 0;
@@ -1239,18 +1237,7 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
     a.partial = sspart_.p;
     a.nchunks = nchunks;
     a.chunk_rows = chunk_rows;
-    EvPair ev{};
-    if (timing_) {
-      ev.a = timing_event();
-      ev.b = timing_event();
-      ev.kind = 1;
-      LC_HIP(hipEventRecord(ev.a, stream_));
-    }
-    LC_HIP(lck::launch_suffstat(a, stream_));
-    if (timing_) {
-      LC_HIP(hipEventRecord(ev.b, stream_));
-      pending_.push_back(ev);
-    }
+    timed(Timed::Suffstat, [&] { LC_HIP(lck::launch_suffstat(a, stream_)); });
     if (listed)
       LC_HIP(lck::launch_reduce_records(sspart_.p, SS, K, sskptr_, sskrec_, ssout_.p, stream_));
     else if (extra > 0) {
@@ -1262,7 +1249,7 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
       LC_HIP(lck::launch_reduce_partials(sspart_.p, nchunks, (int64_t)K * SS, direct ? hss_.data() : ssout_.p, stream_));
     // per-group counts N_jk: with one group they are the N_k just reduced (filled in on the host below) -- unless the
     // records are about to be summed over ranks that hold OTHER groups, or a mask removes clusters from them
-    if (own_counts) {
+    if (counts) {
       redtmp_.reserve((size_t)lck::REDUCE_TMP_ELEMS * 64);
       LC_HIP(lck::launch_group_colsum(qz_[cur_].buf.p, NP_, K, goff_d_.p, J_, njk_d, stream_, redtmp_.p, NP_));
     }
@@ -1280,30 +1267,9 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
     LC_HIP(hipMemcpyAsync(hss_.data(), ssout_.p, nout * sizeof(double), hipMemcpyDeviceToHost, stream_));
   }
   LC_HIP(hipStreamSynchronize(stream_));
-  for (int k = 0; k < K; ++k) {
-    const double* rec = hss_.data() + (size_t)k * SS;
-    const bool off = false;  // (a single group's masked clusters were zeroed on the device, before the sum over ranks)
-    if (Nk) Nk[k] = off ? 0.0 : rec[0];
-    if (xs)
-      for (int d = 0; d < D; ++d) xs[(size_t)k * D + d] = off ? 0.0 : rec[1 + d];
-    if (xxs) {
-      const double* S = rec + 1 + DP;
-      double* o = xxs + (size_t)k * D * D;
-      // lower triangle is authoritative; mirror it so the result is exactly symmetric
-      for (int i = 0; i < D; ++i)
-        for (int j = 0; j <= i; ++j) {
-          const double v = off ? 0.0 : S[(size_t)i * DP + j];
-          o[(size_t)i * D + j] = v;
-          o[(size_t)j * D + i] = v;
-        }
-    }
-  }
-  if (Njk) {
-    if (!own_counts)  // qZ.colwise().sum() of the only group == the N_k record
-      for (int k = 0; k < K; ++k) Njk[k] = hss_[(size_t)k * SS];
-    else
-      std::copy(hss_.begin() + (size_t)K * SS, hss_.end(), Njk);
-  }
+  // (a single group's masked clusters were zeroed on the device, before the sum over ranks)
+  unpack_gw_records(hss_.data(), K, D, DP, Nk, xs, xxs);
+  unpack_counts(hss_.data(), SS, K, counts ? hss_.data() + (size_t)K * SS : nullptr, J_, Njk);
 }
 
 bool Context::dcache_eligible(int K) const {
@@ -1540,40 +1506,10 @@ bool Context::recompute_bounded(int K, const std::vector<int>& changed, const st
       std::copy(m + (size_t)changed[(size_t)t] * D, m + (size_t)(changed[(size_t)t] + 1) * D, m2.begin() + (size_t)t * D);
     }
     const std::vector<double> zero((size_t)nch, 0.0);
-    const int64_t PS = lck::estep_pstride(DP_, DC_);  // (the wide layout beyond DP = 128: ADVICE r5, high)
-    pack_estep_params(nch, A2.data(), m2.data(), zero.data());
-    params_.reserve(hpack_.size());
-    LC_HIP(hipMemcpyAsync(params_.p, hpack_.data(), hpack_.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
-    const int64_t nrg = Mp / lck::RG;
-    lck::EstepLaunch a;
-    a.DP = DP_;
-    a.DC = DC_;
-    a.X = bs_x_.p;
-    a.nrg = nrg;
-    a.rginfo = nullptr;
-    a.nrows = sel.M;
-    a.params = params_.p;
-    a.ctab = params_.p + (size_t)nch * PS;
-    a.K = nch;
-    a.qZ = bs_out_.p;
-    a.ldq = Mp;
-    a.ll_part = nullptr;
-    a.raw = 1;
-    const int64_t grid = lck::estep_grid(a);
-    fzpart_.reserve((size_t)std::max<int64_t>(grid, 1));
-    a.fz_part = fzpart_.p;
-    EvPair ev{};
-    if (timing_) {
-      ev.a = timing_event();
-      ev.b = timing_event();
-      ev.kind = 0;
-      LC_HIP(hipEventRecord(ev.a, stream_));
-    }
-    LC_HIP(lck::launch_estep(a, stream_));
-    if (timing_) {
-      LC_HIP(hipEventRecord(ev.b, stream_));
-      pending_.push_back(ev);
-    }
+    // (one group -- bound_static_ok -- so Mp padded rows, sel.M of them valid, are a data set of the context's own kind)
+    const lck::EstepLaunch a =
+        gw_estep_launch(nch, A2.data(), m2.data(), zero.data(), bs_x_.p, Mp, sel.M, bs_out_.p, /*raw=*/true, /*want_ll=*/false);
+    timed(Timed::Estep, [&] { LC_HIP(lck::launch_estep(a, stream_)); });
     double* dp[lck::BOUND_MAX_COLS];
     for (int t = 0; t < nch; ++t) dp[t] = b.dest[t];
     LC_HIP(lck::launch_scatter_cols(bs_out_.p, Mp, nch, dp, sel.idx.p, sel.M, stream_));
@@ -1828,12 +1764,7 @@ int Context::estep_cache(int K, const double* A, const double* m, const double* 
   const int64_t grid = lck::softmax_cached_grid(NP_);
   fzpart_.reserve((size_t)std::max<int64_t>(grid, 1));
   if (LLk) llpart_.reserve((size_t)std::max<int64_t>(grid, 1) * K);
-  red_.reserve((size_t)1 + K);
   const bool delta = delta_tol >= 0.0 && have_old;
-  const int nred = LLk ? 1 + K : 1;
-  hred_.resize((size_t)nred);
-  constexpr bool direct_env = true;  // (the copy-back command instead: measured slower)
-  const bool direct = direct_env && !distributed() && NP_ > 0;
   if (NP_ > 0) {
     // [c_jk table | the K slots of the clusters' columns (ints)] in one upload
     hpack_.assign((size_t)J_ * K + (size_t)(K + 1) / 2, 0.0);
@@ -1898,29 +1829,9 @@ int Context::estep_cache(int K, const double* A, const double* m, const double* 
         if (trace) std::cerr << "[cache] sweep K " << K << ", fingerprints " << (hashed_old ? "compared" : "written") << std::endl;
       }
     }
-    EvPair ev{};
-    if (timing_) {
-      ev.a = timing_event();
-      ev.b = timing_event();
-      ev.kind = 0;
-      LC_HIP(hipEventRecord(ev.a, stream_));
-    }
-    LC_HIP(lck::launch_softmax_cached(a, stream_));
-    if (timing_) {
-      LC_HIP(hipEventRecord(ev.b, stream_));
-      pending_.push_back(ev);
-    }
-    redtmp_.reserve((size_t)lck::REDUCE_TMP_ELEMS * 64);
-    double* dst = direct ? hred_.data() : red_.p;  // (single rank: the folds write into the page-locked host buffer)
-    LC_HIP(lck::launch_reduce_partials(fzpart_.p, (int)grid, 1, dst, stream_, redtmp_.p));
-    if (LLk) LC_HIP(lck::launch_reduce_partials(llpart_.p, (int)grid, K, dst + 1, stream_, redtmp_.p));
-  } else {
-    LC_HIP(hipMemsetAsync(red_.p, 0, (size_t)(1 + K) * sizeof(double), stream_));
+    timed(Timed::Estep, [&] { LC_HIP(lck::launch_softmax_cached(a, stream_)); });
   }
-  if (!direct) {
-    allreduce(red_.p, nred);
-    LC_HIP(hipMemcpyAsync(hred_.data(), red_.p, (size_t)nred * sizeof(double), hipMemcpyDeviceToHost, stream_));
-  }
+  enqueue_sums(grid, K, LLk != nullptr);  // (no rows: no blocks, and zeros join the sums)
   dq_mask_ok_ = false;
   if (delta && NP_ > 0) {
     hmask_.resize(2);
@@ -1932,8 +1843,7 @@ int Context::estep_cache(int K, const double* A, const double* m, const double* 
     std::memcpy(dq_mask_, hmask_.data(), sizeof(dq_mask_));
     dq_mask_ok_ = true;
   }
-  if (Fz) *Fz = hred_[0];
-  if (LLk) std::copy(hred_.begin() + 1, hred_.begin() + 1 + K, LLk);
+  read_sums(K, Fz, LLk);
   if (delta) dq_K_ = K;  // (a rank without rows keeps an empty delta and still joins delta_suffstat's sums)
   qz_[cur_].hash_ok = delta && NP_ > 0 && qz_[cur_].hash.p != nullptr && lck::test_switch("LC_SPLIT_NO_QHASH") == nullptr;
   return nch;
@@ -2128,7 +2038,6 @@ void Context::estep_diag(int K, const double* av, const double* w2, const double
   const int64_t nrg = NP_ / lck::RG, grid = lck::estep_diag_grid(nrg);
   fzpart_.reserve((size_t)std::max<int64_t>(grid, 1));
   llpart_.reserve((size_t)std::max<int64_t>(grid, 1) * K);
-  red_.reserve((size_t)1 + K);
   lck::DiagEstepLaunch a;
   a.DP = DP;
   a.D = D;
@@ -2153,37 +2062,15 @@ void Context::estep_diag(int K, const double* av, const double* w2, const double
     a.sink = sink_.p;
     a.ngroups = J_;
   }
-  EvPair ev{};
-  if (timing_) {
-    ev.a = timing_event();
-    ev.b = timing_event();
-    ev.kind = 0;
-    LC_HIP(hipEventRecord(ev.a, stream_));
-  }
-  LC_HIP(lck::launch_estep_diag(a, stream_));
-  if (timing_) {
-    LC_HIP(hipEventRecord(ev.b, stream_));
-    pending_.push_back(ev);
-  }
+  timed(Timed::Estep, [&] { LC_HIP(lck::launch_estep_diag(a, stream_)); });
   if (raw) {
     LC_HIP(hipStreamSynchronize(stream_));
     return;
   }
-  if (grid > 0) {
-    redtmp_.reserve((size_t)lck::REDUCE_TMP_ELEMS * 64);
-    LC_HIP(lck::launch_reduce_partials(fzpart_.p, (int)grid, 1, red_.p, stream_, redtmp_.p));
-    if (LLk) LC_HIP(lck::launch_reduce_partials(llpart_.p, (int)grid, K, red_.p + 1, stream_, redtmp_.p));
-    else LC_HIP(hipMemsetAsync(red_.p + 1, 0, (size_t)K * sizeof(double), stream_));
-  } else {
-    LC_HIP(hipMemsetAsync(red_.p, 0, (size_t)(1 + K) * sizeof(double), stream_));
-  }
-  allreduce(red_.p, 1 + K);
-  hred_.resize((size_t)1 + K);
-  LC_HIP(hipMemcpyAsync(hred_.data(), red_.p, (size_t)(1 + K) * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  enqueue_sums(grid, K, LLk != nullptr);
   run_overlap();
   LC_HIP(hipStreamSynchronize(stream_));
-  if (Fz) *Fz = hred_[0];
-  if (LLk) std::copy(hred_.begin() + 1, hred_.end(), LLk);
+  read_sums(K, Fz, LLk);
 }
 
 void Context::suffstat_diag(const unsigned char* smask, double* Nk, double* xs, double* xxs, double* Njk) {
@@ -2194,7 +2081,7 @@ void Context::suffstat_diag(const unsigned char* smask, double* Nk, double* xs, 
   const size_t nout = (size_t)K * SS + (size_t)J_ * K;
   ssout_.reserve(nout);
   double* njk_d = ssout_.p + (size_t)K * SS;
-  const bool own_counts = J_ > 1 || group_sharded() || smask != nullptr;
+  const bool counts = own_counts(smask != nullptr);
   if (NP_ > 0) {
     // about four blocks per resident slot (2 blocks per CU), whole 32-row batches; the partial records
     // (chunks x row classes x K x (1 + 2 DP) doubles) stay small next to the data
@@ -2225,20 +2112,9 @@ void Context::suffstat_diag(const unsigned char* smask, double* Nk, double* xs, 
     a.nchunks = nchunks;
     a.chunk_rows = rows;
     a.second = xxs ? 1 : 0;
-    EvPair ev{};
-    if (timing_) {
-      ev.a = timing_event();
-      ev.b = timing_event();
-      ev.kind = 1;
-      LC_HIP(hipEventRecord(ev.a, stream_));
-    }
-    LC_HIP(lck::launch_suffstat_diag(a, stream_));
-    if (timing_) {
-      LC_HIP(hipEventRecord(ev.b, stream_));
-      pending_.push_back(ev);
-    }
+    timed(Timed::Suffstat, [&] { LC_HIP(lck::launch_suffstat_diag(a, stream_)); });
     LC_HIP(lck::launch_reduce_partials(sspart_.p, nparts, (int64_t)K * SS, ssout_.p, stream_));
-    if (own_counts) {
+    if (counts) {
       redtmp_.reserve((size_t)lck::REDUCE_TMP_ELEMS * 64);
       LC_HIP(lck::launch_group_colsum(qz_[cur_].buf.p, NP_, K, goff_d_.p, J_, njk_d, stream_, redtmp_.p, NP_));
     }
@@ -2255,19 +2131,13 @@ void Context::suffstat_diag(const unsigned char* smask, double* Nk, double* xs, 
   LC_HIP(hipStreamSynchronize(stream_));
   for (int k = 0; k < K; ++k) {
     const double* rec = hss_.data() + (size_t)k * SS;
-    const bool off = false;  // (see suffstat)
-    if (Nk) Nk[k] = off ? 0.0 : rec[0];
+    if (Nk) Nk[k] = rec[0];
     for (int d = 0; d < D; ++d) {
-      if (xs) xs[(size_t)k * D + d] = off ? 0.0 : rec[1 + d];
-      if (xxs) xxs[(size_t)k * D + d] = off ? 0.0 : rec[1 + DP + d];
+      if (xs) xs[(size_t)k * D + d] = rec[1 + d];
+      if (xxs) xxs[(size_t)k * D + d] = rec[1 + DP + d];
     }
   }
-  if (Njk) {
-    if (!own_counts)
-      for (int k = 0; k < K; ++k) Njk[k] = hss_[(size_t)k * SS];
-    else
-      std::copy(hss_.begin() + (size_t)K * SS, hss_.end(), Njk);
-  }
+  unpack_counts(hss_.data(), SS, K, counts ? hss_.data() + (size_t)K * SS : nullptr, J_, Njk);
 }
 
 // ---------------------------------------------------------------------------
@@ -2276,22 +2146,20 @@ void Context::suffstat_diag(const unsigned char* smask, double* Nk, double* xs, 
 KernelTimes Context::timing_get() {
   use_device();
   if (!pending_.empty()) LC_HIP(hipStreamSynchronize(stream_));
+  struct Heading {
+    double KernelTimes::*ms;
+    int64_t KernelTimes::*calls;
+  };
+  static constexpr Heading headings[] = {{&KernelTimes::estep_ms, &KernelTimes::estep_calls},          // in the order
+                                         {&KernelTimes::suffstat_ms, &KernelTimes::suffstat_calls},    // of enum Timed
+                                         {&KernelTimes::fused_ms, &KernelTimes::fused_calls},
+                                         {&KernelTimes::allreduce_ms, &KernelTimes::allreduce_calls}};
   for (auto& p : pending_) {
     float ms = 0.f;
     LC_HIP(hipEventElapsedTime(&ms, p.a, p.b));
-    if (p.kind == 3) {
-      times_.allreduce_ms += ms;
-      times_.allreduce_calls += 1;
-    } else if (p.kind == 2) {
-      times_.fused_ms += ms;
-      times_.fused_calls += 1;
-    } else if (p.kind == 0) {
-      times_.estep_ms += ms;
-      times_.estep_calls += 1;
-    } else {
-      times_.suffstat_ms += ms;
-      times_.suffstat_calls += 1;
-    }
+    const Heading& h = headings[(int)p.kind];
+    times_.*h.ms += ms;
+    times_.*h.calls += 1;
     evpool_.push_back(p.a);  // (back to the pool: creating an event costs microseconds, and a timed iteration of the
     evpool_.push_back(p.b);  //  small configuration lasts 180 of them)
   }

@@ -310,6 +310,22 @@ class Context {
   void allreduce(double* dbuf, int64_t count);
   // pack the E-step parameter stream (tiles of A_k in consumption order, -b_k; then the J x K table c) into hpack_
   void pack_estep_params(int K, const double* A, const double* m, const double* c);
+  // ... packs and uploads them, and returns the launch of the Gauss-Wishart E-step over the `rows` (padded) rows of X, of
+  // which the first `nrows` are valid when the context has one group; out: K columns, leading dimension `rows`.  The
+  // partial buffers are sized for lck::estep_grid() of the launch (llpart_ only with want_ll).
+  lck::EstepLaunch gw_estep_launch(int K, const double* A, const double* m, const double* c, const double* X, int64_t rows,
+                                   int64_t nrows, double* out, bool raw, bool want_ll);
+  // The frame the passes share.  timed: run `launch` between two events of the pool when timing is on
+  // (a launch that throws leaves no pair behind).
+  enum class Timed { Estep, Suffstat, Fused, Allreduce };  // the heading of KernelTimes a launch is counted under
+  template <class F>
+  void timed(Timed kind, F&& launch);
+  // F_z and LL_k of a normalising pass: fold the `grid` rows of fzpart_ / llpart_ (0: this rank holds no rows), sum over
+  // ranks, and leave [F_z | LL_k] in hred_ once the stream has been synchronised; read_sums() hands them out after that
+  void enqueue_sums(int64_t grid, int K, bool want_ll);
+  void read_sums(int K, double* Fz, double* LLk) const;
+  // N_jk comes from a column-sum pass of its own: several groups, whole groups per rank, or a mask that removes clusters
+  bool own_counts(bool masked) const { return J_ > 1 || group_sharded() || masked; }
   void use_device() const;         // hipSetDevice(device_): every method that allocates, launches or copies starts here
   void require_gw_width() const;  // throws for DP > 128 (full-covariance kernels)
   int build_sparse_worklist(const unsigned char* smask, int K, int64_t SS, lck::SuffstatLaunch& a);
@@ -407,7 +423,7 @@ class Context {
   bool timing_ = false;
   struct EvPair {
     hipEvent_t a, b;
-    int kind;
+    Timed kind;
   };
   std::vector<EvPair> pending_;
   std::vector<hipEvent_t> evpool_;  // recycled timing events
