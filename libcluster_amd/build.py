@@ -21,6 +21,9 @@ LIB = PKG / "lib" / "libcluster_hip.so"
 # LC_TEST_JOURNAL_FAIL_RANK in lc_ctx.cpp); tests load it through LC_LIB_PATH, the shipped library has no such switches
 LIB_TESTHOOKS = PKG / "lib" / "libcluster_hip_testhooks.so"
 HOOKED_SOURCES = ["lc_ctx.cpp"]
+# compiled and linked into the hooks library ONLY: the lc_test_* entry points that hand single launchers host arrays
+# (tests/aux_hooks.py); the shipped library exports none of them
+HOOK_ONLY_SOURCES = ["lc_testhooks.hip"]
 ARCH = "gfx950"
 
 # Device-side scheduling: the AMDGPU register-pressure trackers (and no "unclustered high-RP" re-scheduling stage)
@@ -94,6 +97,13 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         hooked_objs[SOURCES.index(src)] = o
         if force or _newer(o, [s, *hdrs]):
             jobs.append([hipcc, f"--offload-arch={ARCH}", *common, "-DLC_TEST_HOOKS", "-c", str(s), "-o", str(o)])
+            LAST_BUILD["compiled"].append(src + " (test hooks)")
+    for src in HOOK_ONLY_SOURCES:
+        s = CSRC / src
+        o = OBJ / (Path(src).stem + ".o")
+        hooked_objs.append(o)
+        if force or _newer(o, [s, *hdrs]):
+            jobs.append([hipcc, f"--offload-arch={ARCH}", *DEVICE_FLAGS, *common, "-DLC_TEST_HOOKS", "-c", str(s), "-o", str(o)])
             LAST_BUILD["compiled"].append(src + " (test hooks)")
     if jobs:  # the translation units are independent: compile them side by side
         from concurrent.futures import ThreadPoolExecutor

@@ -2204,21 +2204,3 @@ const char* test_switch(const char* name) {
 #endif
 }
 }  // namespace lck
-
-#ifdef LC_TEST_HOOKS
-// libcluster_hip_testhooks.so only (tests/test_gpu_comm.py): the device-side rank-order sum of LIBCLUSTER_COMM=rccl-gather
-// on host data -- `world` blocks of `count` doubles in, `count` out.  0 on success, the HIP error code otherwise.
-extern "C" __attribute__((visibility("default"))) int lc_test_rank_order_sum(const double* in, int world, long long count, double* out) {
-  if (!in || !out || world < 1 || count < 1) return -1;
-  double *din = nullptr, *dout = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&din), (size_t)world * (size_t)count * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), (size_t)count * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(din, in, (size_t)world * (size_t)count * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = lck::launch_rank_order_sum(din, world, count, dout, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)count * sizeof(double), hipMemcpyDeviceToHost);
-  if (din) (void)hipFree(din);
-  if (dout) (void)hipFree(dout);
-  return (int)e;
-}
-#endif

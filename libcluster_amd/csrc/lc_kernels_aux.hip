@@ -871,7 +871,9 @@ __global__ void __launch_bounds__(256) bound_select_kernel(BoundSelectLaunch a) 
       if (t < a.ncol) {
         const double s = fmax(a.sigma[t] * sqrt(fmax(d2[t], 0.0)) - a.bnorm[t], 0.0);
         ub[t] = -0.5 * s * s;
-        skip = skip && (a.cnew[t] + ub[t] < low);  // (NaN anywhere: false -> the row is recomputed)
+        // (NaN anywhere: false -> the row is recomputed.  A NaN reference is asked for by name: fmax drops it -- fmax(NaN, 0) = 0
+        //  made such a row look like one AT its reference cluster's centre, and it could be skipped)
+        skip = skip && d2[t] == d2[t] && (a.cnew[t] + ub[t] < low);
       }
   }
   a.need[row] = skip ? 0.0 : 1.0;

@@ -1,0 +1,442 @@
+// Test-hook entry points: libcluster_hip_testhooks.so ONLY (libcluster_amd/build.py, HOOK_ONLY_SOURCES) -- the shipped
+// library exports no lc_test_* symbol (tests/test_host.py).  One wrapper per launcher of lc_kernels_aux.hip: host arrays in,
+// one launch (or the launcher pair a Context method uses together), host arrays out; 0 on success, the HIP error code
+// otherwise.  Everything a kernel would use as an address is checked on the host BEFORE anything is launched: a wrong
+// test comes back as -1 and a failed assertion, never as a memory fault.  Buffers marked "io" are uploaded as the
+// caller filled them (sentinels) and downloaded whole, so that a write outside the intended entries shows.
+// Python side: tests/aux_hooks.py; cases: tests/test_gpu_aux_kernels.py.
+#include <vector>
+
+#include "lc_device.hpp"
+
+namespace {
+
+using lck::RG;
+typedef long long i64;  // (ctypes c_longlong; int64_t on the device side)
+
+// device copies of the host arrays of one call; finish() waits, downloads the io buffers and frees everything
+class Scope {
+ public:
+  ~Scope() {
+    for (auto& b : bufs_)
+      if (b.d) (void)hipFree(b.d);
+  }
+  template <typename T>
+  T* in(const T* h, size_t n) { return static_cast<T*>(add(const_cast<T*>(h), n * sizeof(T), false, true)); }
+  template <typename T>
+  T* io(T* h, size_t n) { return static_cast<T*>(add(h, n * sizeof(T), true, true)); }
+  template <typename T>
+  T* out(T* h, size_t n) { return static_cast<T*>(add(h, n * sizeof(T), true, false)); }
+  template <typename T>
+  T* scratch(size_t n) { return static_cast<T*>(add(nullptr, n * sizeof(T), false, false)); }
+  bool ok() const { return err_ == hipSuccess; }
+  int finish(hipError_t launched) {
+    if (err_ == hipSuccess) err_ = launched;
+    if (err_ == hipSuccess) err_ = hipDeviceSynchronize();
+    for (auto& b : bufs_)
+      if (err_ == hipSuccess && b.back && b.bytes) err_ = hipMemcpy(b.h, b.d, b.bytes, hipMemcpyDeviceToHost);
+    return (int)err_;
+  }
+
+ private:
+  struct Buf {
+    void *d, *h;
+    size_t bytes;
+    bool back;
+  };
+  void* add(void* h, size_t bytes, bool back, bool upload) {
+    Buf b{nullptr, h, bytes, back};
+    if (err_ == hipSuccess) err_ = hipMalloc(&b.d, bytes ? bytes : 16);  // (an empty array still gets an address)
+    if (err_ == hipSuccess && upload && bytes) err_ = hipMemcpy(b.d, h, bytes, hipMemcpyHostToDevice);
+    bufs_.push_back(b);
+    return b.d;
+  }
+  std::vector<Buf> bufs_;
+  hipError_t err_ = hipSuccess;
+};
+
+// rginfo words of nrg row groups: every group index inside [0, ngroups), every count inside 0 ... 16
+bool rginfo_ok(const int* rginfo, i64 nrg, i64 ngroups) {
+  for (i64 g = 0; g < nrg; ++g) {
+    const int info = rginfo[g];
+    if (info < 0 || (info >> 5) >= ngroups || (info & 31) > RG) return false;
+  }
+  return true;
+}
+
+// a selection as the gathers address it: M source rows inside [0, nsrc), J >= 1 groups whose starts ascend from 0 to M, every
+// destination row goff_sub[j] + (p - starts[j]) inside [0, ndst)
+bool selection_ok(const i64* idx, i64 M, i64 nsrc, const i64* starts, const i64* goff_sub, int J, i64 ndst) {
+  if (!idx || !starts || !goff_sub || M < 0 || J < 1 || nsrc < 0 || ndst < 0) return false;
+  for (i64 p = 0; p < M; ++p)
+    if (idx[p] < 0 || idx[p] >= nsrc) return false;
+  if (starts[0] != 0 || starts[J] != M) return false;
+  for (int j = 0; j < J; ++j) {
+    const i64 cnt = starts[j + 1] - starts[j];
+    if (cnt < 0 || goff_sub[j] < 0 || goff_sub[j] > ndst || cnt > ndst - goff_sub[j]) return false;
+  }
+  return true;
+}
+
+__global__ void __launch_bounds__(256) exp_nonpos_probe_kernel(const double* __restrict__ x, i64 n, double* __restrict__ out) {
+  __shared__ double etab[64];
+  lck::fill_exp_table(etab, threadIdx.x, 256);
+  __syncthreads();
+  const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = lck::exp_nonpos(x[i], etab);
+}
+__global__ void __launch_bounds__(256) rcp_pos_probe_kernel(const double* __restrict__ x, i64 n, double* __restrict__ out) {
+  const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = lck::rcp_pos(x[i]);
+}
+
+}  // namespace
+
+#define LC_HOOK extern "C" __attribute__((visibility("default"))) int
+
+// the device-side rank-order sum of LIBCLUSTER_COMM=rccl-gather on host data (tests/test_gpu_comm.py): `world` blocks of
+// `count` doubles in, `count` out
+LC_HOOK lc_test_rank_order_sum(const double* in, int world, i64 count, double* out) {
+  if (!in || !out || world < 1 || count < 1) return -1;
+  Scope s;
+  const double* din = s.in(in, (size_t)world * (size_t)count);
+  double* dout = s.out(out, (size_t)count);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_rank_order_sum(din, world, count, dout, nullptr));
+}
+
+// ---- device math -------------------------------------------------------------------------------------------------
+LC_HOOK lc_test_exp_nonpos(const double* x, i64 n, double* out) {
+  if (!x || !out || n < 1) return -1;
+  Scope s;
+  const double* dx = s.in(x, (size_t)n);
+  double* dout = s.out(out, (size_t)n);
+  if (!s.ok()) return s.finish(hipSuccess);
+  hipLaunchKernelGGL(exp_nonpos_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, dx, n, dout);
+  return s.finish(hipGetLastError());
+}
+LC_HOOK lc_test_rcp_pos(const double* x, i64 n, double* out) {
+  if (!x || !out || n < 1) return -1;
+  Scope s;
+  const double* dx = s.in(x, (size_t)n);
+  double* dout = s.out(out, (size_t)n);
+  if (!s.ok()) return s.finish(hipSuccess);
+  hipLaunchKernelGGL(rcp_pos_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, dx, n, dout);
+  return s.finish(hipGetLastError());
+}
+
+// ---- reductions --------------------------------------------------------------------------------------------------
+// partial [nparts x n] -> out [n]; use_tmp: hand the launcher its REDUCE_TMP_ELEMS * 64 doubles of scratch
+LC_HOOK lc_test_reduce_partials(const double* partial, int nparts, i64 n, double* out, int use_tmp) {
+  if (!partial || !out || nparts < 0 || n < 1) return -1;
+  Scope s;
+  const double* dp = s.in(partial, (size_t)nparts * (size_t)n);
+  double* dout = s.io(out, (size_t)n);
+  double* tmp = use_tmp ? s.scratch<double>((size_t)lck::REDUCE_TMP_ELEMS * 64) : nullptr;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_reduce_partials(dp, nparts, n, dout, nullptr, tmp));
+}
+// partial [nrec x n]; cluster k sums the records krec[kptr[k] .. kptr[k + 1]) -> out [K x n]
+LC_HOOK lc_test_reduce_records(const double* partial, int nrec, i64 n, int K, const int* kptr, const int* krec, double* out) {
+  if (!partial || !kptr || !krec || !out || nrec < 0 || n < 1 || K < 1 || kptr[0] < 0) return -1;
+  for (int k = 0; k < K; ++k)
+    if (kptr[k + 1] < kptr[k]) return -1;
+  for (int c = kptr[0]; c < kptr[K]; ++c)
+    if (krec[c] < 0 || krec[c] >= nrec) return -1;
+  Scope s;
+  const double* dp = s.in(partial, (size_t)nrec * (size_t)n);
+  const int* dkptr = s.in(kptr, (size_t)K + 1);
+  const int* dkrec = s.in(krec, (size_t)kptr[K]);
+  double* dout = s.io(out, (size_t)K * (size_t)n);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_reduce_records(dp, n, K, dkptr, dkrec, dout, nullptr));
+}
+// qZ [K x ldq], goff [J + 1] -> out [J x K]; use_tmp / rows as launch_group_colsum takes them (`rows` is no address: it
+// only steers the launcher's choice of path, every path reads goff's own row ranges)
+LC_HOOK lc_test_group_colsum(const double* qZ, i64 ldq, int K, const i64* goff, int J, double* out, int use_tmp, i64 rows) {
+  if (!qZ || !goff || !out || K < 1 || J < 1 || ldq < 1 || goff[0] < 0 || goff[J] > ldq) return -1;
+  for (int j = 0; j < J; ++j)
+    if (goff[j + 1] < goff[j]) return -1;
+  Scope s;
+  const double* dq = s.in(qZ, (size_t)K * (size_t)ldq);
+  const int64_t* dg = reinterpret_cast<const int64_t*>(s.in(goff, (size_t)J + 1));
+  double* dout = s.io(out, (size_t)J * (size_t)K);
+  double* tmp = use_tmp ? s.scratch<double>((size_t)lck::REDUCE_TMP_ELEMS * 64) : nullptr;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_group_colsum(dq, ldq, K, dg, J, dout, nullptr, tmp, rows));
+}
+// qZ (io) [Kbuf x ldq]: columns 0 .. K of the nrg * 16 rows are filled; rginfo [nrg] or null (then nrows)
+LC_HOOK lc_test_fill_qz(double* qZ, i64 ldq, int K, int Kbuf, const int* rginfo, i64 nrows, i64 nrg, double value) {
+  if (!qZ || K < 1 || K > Kbuf || nrg < 1 || nrg * RG > ldq) return -1;
+  if (rginfo ? !rginfo_ok(rginfo, nrg, 1 << 26) : (nrows < 0 || nrows > nrg * RG)) return -1;
+  Scope s;
+  double* dq = s.io(qZ, (size_t)Kbuf * (size_t)ldq);
+  const int* drg = rginfo ? s.in(rginfo, (size_t)nrg) : nullptr;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_fill_qz(dq, ldq, K, drg, nrows, nrg, value, nullptr));
+}
+
+// ---- split search: row selection -----------------------------------------------------------------------------------
+// select_count, the host's exclusive scan, select_compact and group_starts as Context::select_rows_col chains them.
+// qcol [NP]; goff [J + 1] ascending; counts (out) [select_blocks(NP)]; idx (io) [cap]; starts (io) [J + 1]; *M (out).
+// -1 when the arguments are unusable or the selection would not fit into idx -- then nothing behind select_count was
+// launched and idx / starts are as the caller filled them (*M is the count found, or untouched); a HIP error code
+// likewise leaves them alone.
+LC_HOOK lc_test_select_rows(const double* qcol, i64 NP, double thresh, const i64* goff, int J, int* counts, i64* idx, i64 cap,
+                            i64* starts, i64* M) {
+  if (!qcol || !goff || !counts || !idx || !starts || !M || NP < 1 || J < 1 || cap < 1) return -1;
+  for (int j = 0; j < J; ++j)
+    if (goff[j + 1] < goff[j]) return -1;
+  const int nb = lck::select_blocks(NP);
+  Scope s;
+  const double* dq = s.in(qcol, (size_t)NP);
+  const int64_t* dg = reinterpret_cast<const int64_t*>(s.in(goff, (size_t)J + 1));
+  int* dcnt = s.scratch<int>((size_t)nb);
+  int64_t* doff = s.scratch<int64_t>((size_t)nb);
+  int64_t* didx = reinterpret_cast<int64_t*>(s.io(idx, (size_t)cap));
+  int64_t* dst = reinterpret_cast<int64_t*>(s.io(starts, (size_t)J + 1));
+  if (!s.ok()) return s.finish(hipSuccess);
+  hipError_t e = lck::launch_select_count(dq, NP, thresh, dcnt, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(counts, dcnt, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return (int)e;
+  std::vector<int64_t> off((size_t)nb);
+  int64_t tot = 0;
+  for (int b = 0; b < nb; ++b) {
+    if (counts[b] < 0 || counts[b] > 1024) return -1;  // (what select_compact would use as an address)
+    off[(size_t)b] = tot;
+    tot += counts[b];
+  }
+  *M = tot;
+  if (tot > cap) return -1;
+  e = hipMemcpy(doff, off.data(), (size_t)nb * sizeof(int64_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = lck::launch_select_compact(dq, NP, thresh, doff, didx, nullptr);
+  if (e == hipSuccess) e = lck::launch_group_starts(didx, tot, dg, J, dst, nullptr);
+  return s.finish(e);
+}
+
+// ---- split search: gathers and the scatter ----------------------------------------------------------------------------
+// X [nsrc x DP] -> Xdst (io) [ndst x DP]
+LC_HOOK lc_test_gather_rows(const double* X, i64 nsrc, int DP, const i64* idx, i64 M, const i64* starts, const i64* goff_sub, int J,
+                            double* Xdst, i64 ndst) {
+  if (!X || !Xdst || DP < 2 || DP % 2 || !selection_ok(idx, M, nsrc, starts, goff_sub, J, ndst)) return -1;
+  Scope s;
+  const double* dX = s.in(X, (size_t)nsrc * DP);
+  const int64_t* di = reinterpret_cast<const int64_t*>(s.in(idx, (size_t)M));
+  const int64_t* ds = reinterpret_cast<const int64_t*>(s.in(starts, (size_t)J + 1));
+  const int64_t* dg = reinterpret_cast<const int64_t*>(s.in(goff_sub, (size_t)J + 1));
+  double* dD = s.io(Xdst, (size_t)ndst * DP);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_gather_rows(dX, DP, di, M, ds, dg, J, dD, nullptr));
+}
+// X [nsrc x DP] -> Xdst (io) [ndst x DP], row p from row idx[p]
+LC_HOOK lc_test_gather_rows_plain(const double* X, i64 nsrc, int DP, const i64* idx, i64 M, double* Xdst, i64 ndst) {
+  if (!X || !Xdst || !idx || DP < 2 || DP % 2 || M < 0 || M > ndst) return -1;
+  for (i64 p = 0; p < M; ++p)
+    if (idx[p] < 0 || idx[p] >= nsrc) return -1;
+  Scope s;
+  const double* dX = s.in(X, (size_t)nsrc * DP);
+  const int64_t* di = reinterpret_cast<const int64_t*>(s.in(idx, (size_t)M));
+  double* dD = s.io(Xdst, (size_t)ndst * DP);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_gather_rows_plain(dX, DP, di, M, dD, nullptr));
+}
+// column-major src [K x lds] (rows < nsrc <= lds) -> column-major dst (io) [K x ldd]
+LC_HOOK lc_test_gather_cols(const double* src, i64 lds, i64 nsrc, int K, const i64* idx, i64 M, const i64* starts,
+                            const i64* goff_sub, int J, double* dst, i64 ldd) {
+  if (!src || !dst || K < 1 || nsrc > lds || !selection_ok(idx, M, nsrc, starts, goff_sub, J, ldd)) return -1;
+  Scope s;
+  const double* dS = s.in(src, (size_t)K * (size_t)lds);
+  const int64_t* di = reinterpret_cast<const int64_t*>(s.in(idx, (size_t)M));
+  const int64_t* ds = reinterpret_cast<const int64_t*>(s.in(starts, (size_t)J + 1));
+  const int64_t* dg = reinterpret_cast<const int64_t*>(s.in(goff_sub, (size_t)J + 1));
+  double* dD = s.io(dst, (size_t)K * (size_t)ldd);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_gather_cols(dS, lds, K, di, M, ds, dg, J, dD, ldd, nullptr));
+}
+// row-major src [nsrc x lds] (lds >= K) -> column-major dst (io) [K x ldd]
+LC_HOOK lc_test_gather_rowmajor(const double* src, i64 lds, i64 nsrc, int K, const i64* idx, i64 M, const i64* starts,
+                                const i64* goff_sub, int J, double* dst, i64 ldd) {
+  if (!src || !dst || K < 1 || K > lds || !selection_ok(idx, M, nsrc, starts, goff_sub, J, ldd)) return -1;
+  Scope s;
+  const double* dS = s.in(src, (size_t)nsrc * (size_t)lds);
+  const int64_t* di = reinterpret_cast<const int64_t*>(s.in(idx, (size_t)M));
+  const int64_t* ds = reinterpret_cast<const int64_t*>(s.in(starts, (size_t)J + 1));
+  const int64_t* dg = reinterpret_cast<const int64_t*>(s.in(goff_sub, (size_t)J + 1));
+  double* dD = s.io(dst, (size_t)K * (size_t)ldd);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_gather_rowmajor(dS, lds, K, di, M, ds, dg, J, dD, ldd, nullptr));
+}
+// row-major src [nsrc x lds], columns cols[0 .. nc) (each inside [0, lds)) -> column-major dst (io) [nc x ldd]
+LC_HOOK lc_test_gather_rowmajor_cols(const double* src, i64 lds, i64 nsrc, const int* cols, int nc, const i64* idx, i64 M,
+                                     const i64* starts, const i64* goff_sub, int J, double* dst, i64 ldd) {
+  if (!src || !dst || !cols || nc < 1 || lds < 1 || !selection_ok(idx, M, nsrc, starts, goff_sub, J, ldd)) return -1;
+  for (int c = 0; c < nc; ++c)
+    if (cols[c] < 0 || cols[c] >= lds) return -1;
+  Scope s;
+  const double* dS = s.in(src, (size_t)nsrc * (size_t)lds);
+  const int* dc = s.in(cols, (size_t)nc);
+  const int64_t* di = reinterpret_cast<const int64_t*>(s.in(idx, (size_t)M));
+  const int64_t* ds = reinterpret_cast<const int64_t*>(s.in(starts, (size_t)J + 1));
+  const int64_t* dg = reinterpret_cast<const int64_t*>(s.in(goff_sub, (size_t)J + 1));
+  double* dD = s.io(dst, (size_t)nc * (size_t)ldd);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_gather_rowmajor_cols(dS, lds, dc, nc, di, M, ds, dg, J, dD, ldd, nullptr));
+}
+// src [ncol x lds] (lds >= M) -> dest (io) [ncol x ndst]: dest[t][idx[p]] = src[t][p].  ncol beyond the launcher's limit is
+// handed to it as it is (its refusal is what a test asks for); nothing is launched then.
+LC_HOOK lc_test_scatter_cols(const double* src, i64 lds, int ncol, double* dest, i64 ndst, const i64* idx, i64 M) {
+  if (!src || !dest || !idx || ncol < 1 || ncol > 64 || M < 0 || M > lds || ndst < 1) return -1;
+  for (i64 p = 0; p < M; ++p)
+    if (idx[p] < 0 || idx[p] >= ndst) return -1;
+  Scope s;
+  const double* dS = s.in(src, (size_t)ncol * (size_t)lds);
+  double* dD = s.io(dest, (size_t)ncol * (size_t)ndst);
+  const int64_t* di = reinterpret_cast<const int64_t*>(s.in(idx, (size_t)M));
+  if (!s.ok()) return s.finish(hipSuccess);
+  std::vector<double*> dp((size_t)ncol);
+  for (int t = 0; t < ncol; ++t) dp[(size_t)t] = dD + (size_t)t * (size_t)ndst;
+  return s.finish(lck::launch_scatter_cols(dS, lds, ncol, dp.data(), di, M, nullptr));
+}
+
+// ---- split search: initial split, augmentation, transpose -----------------------------------------------------------
+// X [NP x DP]; mv [2 DP]; q (io) [2 x ldq]; rginfo [NP / 16] or null (then nrows); thr [ngroups] (mode 2)
+LC_HOOK lc_test_split_init(const double* X, int DP, int D, i64 NP, const int* rginfo, i64 nrows, int ngroups, const double* mv,
+                           double* q, i64 ldq, int mode, const double* thr) {
+  if (!X || !mv || !q || DP < 16 || DP % 16 || D < 1 || D > DP || NP < 1 || NP > ldq || mode < 0 || mode > 2 || ngroups < 1) return -1;
+  if (rginfo ? (NP % RG || !rginfo_ok(rginfo, NP / RG, ngroups)) : (nrows < 0 || nrows > NP)) return -1;
+  if (mode == 2 && !thr) return -1;
+  Scope s;
+  const double* dX = s.in(X, (size_t)NP * DP);
+  const int* drg = rginfo ? s.in(rginfo, (size_t)(NP / RG)) : nullptr;
+  const double* dmv = s.in(mv, (size_t)2 * DP);
+  const double* dthr = thr ? s.in(thr, (size_t)ngroups) : nullptr;
+  double* dq = s.io(q, (size_t)2 * (size_t)ldq);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_split_init(dX, DP, D, NP, drg, nrows, dmv, dq, ldq, mode, dthr, nullptr));
+}
+// q (io) [(K + 1) x ldq] (rows < NP <= ldq); qsub1 [nsub]; qhash (io) [NP] or null
+LC_HOOK lc_test_aug_from_sub(double* q, i64 ldq, i64 NP, int k, int K, const i64* idx, i64 M, const i64* starts,
+                             const i64* goff_sub, int J, const double* qsub1, i64 nsub, i64* qhash) {
+  if (!q || !qsub1 || K < 1 || k < 0 || k >= K || NP > ldq || !selection_ok(idx, M, NP, starts, goff_sub, J, nsub)) return -1;
+  Scope s;
+  double* dq = s.io(q, (size_t)(K + 1) * (size_t)ldq);
+  const int64_t* di = reinterpret_cast<const int64_t*>(s.in(idx, (size_t)M));
+  const int64_t* ds = reinterpret_cast<const int64_t*>(s.in(starts, (size_t)J + 1));
+  const int64_t* dg = reinterpret_cast<const int64_t*>(s.in(goff_sub, (size_t)J + 1));
+  const double* dsub = s.in(qsub1, (size_t)nsub);
+  int64_t* dh = qhash ? reinterpret_cast<int64_t*>(s.io(qhash, (size_t)NP)) : nullptr;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_aug_from_sub(dq, ldq, k, K, di, M, ds, dg, J, dsub, nullptr, dh));
+}
+// qZ [K x ldq] -> qT (io) [nqt >= NP * K]
+LC_HOOK lc_test_transpose_qz(const double* qZ, i64 ldq, int K, i64 NP, double* qT, i64 nqt) {
+  if (!qZ || !qT || K < 1 || NP < 1 || NP > ldq || nqt < NP * K) return -1;
+  Scope s;
+  const double* dq = s.in(qZ, (size_t)K * (size_t)ldq);
+  double* dT = s.io(qT, (size_t)nqt);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_transpose_qz(dq, ldq, K, NP, dT, nullptr));
+}
+
+// ---- model selection: the normalisation sweep, fingerprints, the bounded pass ---------------------------------------------
+// dcache [Kc x ldc]; fresh [nfresh x ldf] or null; colmap [K] or null; ctab [J x K]; rginfo [NP / 16] or null (then nrows);
+// qZ (io) [Kq x ldq], Kq >= K; fz_part (io) [nblk]; optional, all io: ll_part [nblk x K], dq [NP x ldd], amax [NP],
+// qhash [NP], rmax [NP], ramax [NP], colmask [2].  nblk must equal softmax_cached_grid(NP).
+// K beyond the launcher's limit goes to the launcher as it is: it refuses and launches nothing.
+LC_HOOK lc_test_softmax_cached(const double* dcache, int Kc, i64 ldc, const double* fresh, int nfresh, i64 ldf, const int* colmap,
+                               const double* ctab, int J, int K, const int* rginfo, i64 nrows, i64 NP, double* qZ, int Kq, i64 ldq,
+                               double* fz_part, i64 nblk, double* ll_part, double* dq, i64 ldd, double* amax, i64* qhash,
+                               int qhash_in, double* rmax, int* ramax, unsigned long long* colmask) {
+  if (!dcache || !ctab || !qZ || !fz_part || K < 1 || K > 4096 || Kc < 1 || J < 1 || NP < 1 || Kq < K) return -1;
+  if (NP > ldc || NP > ldq || nblk != lck::softmax_cached_grid(NP)) return -1;
+  if (fresh ? (nfresh < 1 || NP > ldf) : nfresh != 0) return -1;
+  for (int j = 0; j < K; ++j) {
+    const int cm = colmap ? colmap[j] : j;
+    if (cm >= 0 ? cm >= Kc : -(i64)cm - 1 >= nfresh) return -1;
+  }
+  if (rginfo ? (NP % RG || !rginfo_ok(rginfo, NP / RG, J)) : (nrows < 0 || nrows > NP)) return -1;
+  if (dq ? (!amax || ldd < K) : (amax || qhash || colmask)) return -1;
+  if (!rmax != !ramax) return -1;
+  Scope s;
+  lck::CachedNormLaunch a{};
+  a.dcache = s.in(dcache, (size_t)Kc * (size_t)ldc);
+  a.ldc = ldc;
+  a.fresh = fresh ? s.in(fresh, (size_t)nfresh * (size_t)ldf) : nullptr;
+  a.ldf = ldf;
+  a.colmap = colmap ? s.in(colmap, (size_t)K) : nullptr;
+  a.ctab = s.in(ctab, (size_t)J * (size_t)K);
+  a.K = K;
+  a.rginfo = rginfo ? s.in(rginfo, (size_t)(NP / RG)) : nullptr;
+  a.nrows = nrows;
+  a.NP = NP;
+  a.qZ = s.io(qZ, (size_t)Kq * (size_t)ldq);
+  a.ldq = ldq;
+  a.fz_part = s.io(fz_part, (size_t)nblk);
+  a.ll_part = ll_part ? s.io(ll_part, (size_t)nblk * (size_t)K) : nullptr;
+  a.dq = dq ? s.io(dq, (size_t)NP * (size_t)ldd) : nullptr;
+  a.ldd = ldd;
+  a.amax = amax ? s.io(amax, (size_t)NP) : nullptr;
+  a.qhash = qhash ? reinterpret_cast<int64_t*>(s.io(qhash, (size_t)NP)) : nullptr;
+  a.qhash_in = qhash_in;
+  a.rmax = rmax ? s.io(rmax, (size_t)NP) : nullptr;
+  a.ramax = ramax ? s.io(ramax, (size_t)NP) : nullptr;
+  a.colmask = colmask ? s.io(colmask, (size_t)2) : nullptr;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_softmax_cached(a, nullptr));
+}
+// qZ [K x ldq], qhash [NP] -> *bad
+LC_HOOK lc_test_qhash_verify(const double* qZ, i64 ldq, int K, i64 NP, const i64* qhash, unsigned long long* bad) {
+  if (!qZ || !qhash || !bad || K < 1 || NP < 1 || NP > ldq) return -1;
+  Scope s;
+  const double* dq = s.in(qZ, (size_t)K * (size_t)ldq);
+  const int64_t* dh = reinterpret_cast<const int64_t*>(s.in(qhash, (size_t)NP));
+  *bad = 0;
+  unsigned long long* db = s.io(bad, 1);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_qhash_verify(dq, ldq, K, NP, dh, db, nullptr));
+}
+// dst (io) [Kdst x ldq], src [K x ldq], dhash (io) [NP], shash [NP]
+LC_HOOK lc_test_qz_resync(double* dst, const double* src, i64 ldq, int K, int Kdst, i64 NP, i64* dhash, const i64* shash) {
+  if (!dst || !src || !dhash || !shash || K < 1 || Kdst < K || NP < 1 || NP > ldq) return -1;
+  Scope s;
+  double* dd = s.io(dst, (size_t)Kdst * (size_t)ldq);
+  const double* ds = s.in(src, (size_t)K * (size_t)ldq);
+  int64_t* dh = reinterpret_cast<int64_t*>(s.io(dhash, (size_t)NP));
+  const int64_t* sh = reinterpret_cast<const int64_t*>(s.in(shash, (size_t)NP));
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_qz_resync(dd, ds, ldq, K, Kdst, NP, dh, sh, nullptr));
+}
+// ref [ncol x NP], dest (io) [ncol x NP], sigma / bnorm / cnew [ncol], rmax [NP], ramax [NP] (any value: the kernel treats
+// an index outside [0, K) as "recompute"), usable [K], dcj [K], need (io) [NP].  ncol or K beyond the launcher's limits
+// go to the launcher (with the first BOUND_MAX_COLS / BOUND_MAX_K entries of the tables): it refuses and launches nothing.
+LC_HOOK lc_test_bound_select(int ncol, int K, i64 NP, const double* ref, double* dest, const double* sigma, const double* bnorm,
+                             const double* cnew, const double* rmax, const int* ramax, double T, const unsigned char* usable,
+                             const double* dcj, double* need) {
+  if (!ref || !dest || !sigma || !bnorm || !cnew || !rmax || !ramax || !usable || !dcj || !need) return -1;
+  if (ncol < 1 || ncol > 64 || K < 1 || K > 4096 || NP < 1) return -1;
+  Scope s;
+  lck::BoundSelectLaunch a{};
+  a.ncol = ncol;
+  a.K = K;
+  a.NP = NP;
+  const double* dref = s.in(ref, (size_t)ncol * (size_t)NP);
+  double* ddest = s.io(dest, (size_t)ncol * (size_t)NP);
+  for (int t = 0; t < ncol && t < lck::BOUND_MAX_COLS; ++t) {
+    a.ref[t] = dref + (size_t)t * (size_t)NP;
+    a.dest[t] = ddest + (size_t)t * (size_t)NP;
+    a.sigma[t] = sigma[t];
+    a.bnorm[t] = bnorm[t];
+    a.cnew[t] = cnew[t];
+  }
+  for (int j = 0; j < K && j < lck::BOUND_MAX_K; ++j) {
+    a.usable[j] = usable[j];
+    a.dcj[j] = dcj[j];
+  }
+  a.rmax = s.in(rmax, (size_t)NP);
+  a.ramax = s.in(ramax, (size_t)NP);
+  a.T = T;
+  a.need = s.io(need, (size_t)NP);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_bound_select(a, nullptr));
+}

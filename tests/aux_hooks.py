@@ -1,0 +1,311 @@
+"""ctypes prototypes and numpy-in / numpy-out wrappers for the lc_test_* entry points of libcluster_hip_testhooks.so
+(libcluster_amd/csrc/lc_testhooks.hip): one launcher of lc_kernels_aux.hip per call, on host arrays.  A plain helper module
+of tests/test_gpu_aux_kernels.py (and of the symbol test in tests/test_host.py); no fixtures, no pytest hooks.
+
+Every wrapper returns the hook's status first (0, -1 = refused by the host-side validation, or a HIP error code); arrays
+the caller passes as destinations are uploaded as they are and overwritten with what the device left in them."""
+from __future__ import annotations
+
+import ctypes as C
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+HOOKS_LIB = ROOT / "libcluster_amd" / "lib" / "libcluster_hip_testhooks.so"
+SHIPPED_LIB = ROOT / "libcluster_amd" / "lib" / "libcluster_hip.so"
+
+# (the constants below restate csrc/lc_kernels.h, lc_device.hpp and lc_kernels_aux.hip; tests/test_host.py compares them
+# with the sources, so a changed constant cannot silently move the boundaries the cases straddle)
+QHASH_NONE = -(1 << 63)
+QHASH_SEED = 0x243F6A8885A308D3
+REDUCE_TMP_ELEMS = 512
+SEL_ROWS = 1024
+GCS_SLICES = 64
+BOUND_MAX_COLS, BOUND_MAX_K = 8, 72
+HIP_ERROR_INVALID_VALUE = 1
+_M64 = (1 << 64) - 1
+
+_P, _I, _L, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_double
+PROTOTYPES = {
+    "lc_test_rank_order_sum": [_P, _I, _L, _P],
+    "lc_test_exp_nonpos": [_P, _L, _P],
+    "lc_test_rcp_pos": [_P, _L, _P],
+    "lc_test_reduce_partials": [_P, _I, _L, _P, _I],
+    "lc_test_reduce_records": [_P, _I, _L, _I, _P, _P, _P],
+    "lc_test_group_colsum": [_P, _L, _I, _P, _I, _P, _I, _L],
+    "lc_test_fill_qz": [_P, _L, _I, _I, _P, _L, _L, _D],
+    "lc_test_select_rows": [_P, _L, _D, _P, _I, _P, _P, _L, _P, _P],
+    "lc_test_gather_rows": [_P, _L, _I, _P, _L, _P, _P, _I, _P, _L],
+    "lc_test_gather_rows_plain": [_P, _L, _I, _P, _L, _P, _L],
+    "lc_test_gather_cols": [_P, _L, _L, _I, _P, _L, _P, _P, _I, _P, _L],
+    "lc_test_gather_rowmajor": [_P, _L, _L, _I, _P, _L, _P, _P, _I, _P, _L],
+    "lc_test_gather_rowmajor_cols": [_P, _L, _L, _P, _I, _P, _L, _P, _P, _I, _P, _L],
+    "lc_test_scatter_cols": [_P, _L, _I, _P, _L, _P, _L],
+    "lc_test_split_init": [_P, _I, _I, _L, _P, _L, _I, _P, _P, _L, _I, _P],
+    "lc_test_aug_from_sub": [_P, _L, _L, _I, _I, _P, _L, _P, _P, _I, _P, _L, _P],
+    "lc_test_transpose_qz": [_P, _L, _I, _L, _P, _L],
+    "lc_test_softmax_cached": [_P, _I, _L, _P, _I, _L, _P, _P, _I, _I, _P, _L, _L, _P, _I, _L, _P, _L, _P, _P, _L, _P, _P, _I,
+                               _P, _P, _P],
+    "lc_test_qhash_verify": [_P, _L, _I, _L, _P, _P],
+    "lc_test_qz_resync": [_P, _P, _L, _I, _I, _L, _P, _P],
+    "lc_test_bound_select": [_I, _I, _L, _P, _P, _P, _P, _P, _P, _P, _D, _P, _P, _P],
+}
+
+_lib = None
+
+
+def hooks():
+    global _lib
+    if _lib is None:
+        try:  # one HIP runtime per process: bind to the copy torch bundles, as libcluster_amd.capi.lib() does
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        lib = C.CDLL(str(HOOKS_LIB))
+        for name, args in PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = args
+            fn.restype = C.c_int
+        _lib = lib
+    return _lib
+
+
+def exported_symbols(path) -> set:
+    """Names in the dynamic symbol table of a shared library (nm -D --defined-only)."""
+    import subprocess
+
+    out = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
+    return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+
+
+def _a(x, dtype):
+    """A C-contiguous array of exactly this dtype (None stays None)."""
+    return None if x is None else np.ascontiguousarray(x, dtype=dtype)
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data
+
+
+def _io(a, dtype):
+    """Destination arrays are written in place: they must already be what the hook expects."""
+    if a is None:
+        return None
+    assert isinstance(a, np.ndarray) and a.dtype == dtype and a.flags.c_contiguous and a.flags.writeable, (a.dtype, dtype)
+    return a
+
+
+f64, i64, i32, u8, u64 = np.float64, np.int64, np.int32, np.uint8, np.uint64
+
+
+# ---- fingerprints (lc_device.hpp: qhash_step / qhash_finish), 64-bit wrap-around -------------------------------------------
+def qhash(row) -> int:
+    """Fingerprint of one row of responsibilities, as a signed 64-bit integer."""
+    acc = QHASH_SEED
+    bits = np.ascontiguousarray(row, dtype=f64).view(u64)
+    for j, b in enumerate(bits.tolist()):
+        if b == 0:
+            continue
+        t = ((acc ^ ((b + 0xD6E8FEB86659FD93 * (j + 1)) & _M64)) * 0x9E3779B97F4A7C15) & _M64
+        acc = t ^ (t >> 32)
+    h = acc - (1 << 64) if acc >= (1 << 63) else acc
+    return 1 if h == QHASH_NONE else h
+
+
+def qhash_rows(q_colmajor, rows=None) -> np.ndarray:
+    """qhash of the rows of a column-major [K x ld] table (all of its ld rows, or the listed ones)."""
+    q = np.asarray(q_colmajor)
+    rows = range(q.shape[1]) if rows is None else rows
+    return np.array([qhash(q[:, r]) for r in rows], dtype=i64)
+
+
+# ---- layouts -------------------------------------------------------------------------------------------------------------
+def padded_offsets(counts) -> np.ndarray:
+    """Group offsets with every group padded to a multiple of 16 rows (Context::build_layout)."""
+    c = (np.asarray(counts, dtype=i64) + 15) // 16 * 16
+    return np.concatenate([[0], np.cumsum(c)]).astype(i64)
+
+
+def rginfo_of(counts) -> np.ndarray:
+    """(group << 5) | nvalid per 16-row group of the padded layout."""
+    out = []
+    for j, n in enumerate(np.asarray(counts).tolist()):
+        full, rest = divmod(n, 16)
+        out += [(j << 5) | 16] * full + ([(j << 5) | rest] if rest else [])
+    return np.array(out, dtype=i32)
+
+
+def valid_rows(counts) -> np.ndarray:
+    """Boolean mask over the padded rows: True on a group's real rows."""
+    goff = padded_offsets(counts)
+    m = np.zeros(int(goff[-1]), dtype=bool)
+    for j, n in enumerate(np.asarray(counts).tolist()):
+        m[goff[j]:goff[j] + n] = True
+    return m
+
+
+def group_of_rows(counts) -> np.ndarray:
+    goff = padded_offsets(counts)
+    g = np.zeros(int(goff[-1]), dtype=i64)
+    for j in range(len(counts)):
+        g[goff[j]:goff[j + 1]] = j
+    return g
+
+
+# ---- wrappers ------------------------------------------------------------------------------------------------------------
+def exp_nonpos(x):
+    x = _a(x, f64)
+    out = np.empty_like(x)
+    return hooks().lc_test_exp_nonpos(_p(x), x.size, _p(out)), out
+
+
+def rcp_pos(x):
+    x = _a(x, f64)
+    out = np.empty_like(x)
+    return hooks().lc_test_rcp_pos(_p(x), x.size, _p(out)), out
+
+
+def reduce_partials(partial, use_tmp=False, sentinel=np.nan):
+    p = _a(partial, f64)
+    nparts, n = p.shape
+    out = np.full(n, sentinel)
+    return hooks().lc_test_reduce_partials(_p(p), nparts, n, _p(out), int(use_tmp)), out
+
+
+def reduce_records(partial, kptr, krec, sentinel=np.nan):
+    p, kptr, krec = _a(partial, f64), _a(kptr, i32), _a(krec, i32)
+    nrec, n = p.shape
+    K = kptr.size - 1
+    out = np.full((K, n), sentinel)
+    return hooks().lc_test_reduce_records(_p(p), nrec, n, K, _p(kptr), _p(krec), _p(out)), out
+
+
+def group_colsum(qZ, goff, use_tmp=False, rows=0, sentinel=np.nan):
+    q, goff = _a(qZ, f64), _a(goff, i64)
+    K, ldq = q.shape
+    J = goff.size - 1
+    out = np.full((J, K), sentinel)
+    return hooks().lc_test_group_colsum(_p(q), ldq, K, _p(goff), J, _p(out), int(use_tmp), rows), out
+
+
+def fill_qz(qZ, K, nrg, value, rginfo=None, nrows=0):
+    q = _io(qZ, f64)
+    rg = _a(rginfo, i32)
+    return hooks().lc_test_fill_qz(_p(q), q.shape[1], K, q.shape[0], _p(rg), nrows, nrg, value)
+
+
+def select_rows(qcol, thresh, goff, sentinel=-7):
+    """-> status, M, idx [NP] (entries >= M keep the sentinel), starts [J + 1], per-block counts"""
+    q, goff = _a(qcol, f64), _a(goff, i64)
+    NP, J = q.size, goff.size - 1
+    counts = np.full((NP + SEL_ROWS - 1) // SEL_ROWS, sentinel, dtype=i32)
+    idx = np.full(NP, sentinel, dtype=i64)
+    starts = np.full(J + 1, sentinel, dtype=i64)
+    M = C.c_longlong(sentinel)
+    rc = hooks().lc_test_select_rows(_p(q), NP, thresh, _p(goff), J, _p(counts), _p(idx), NP, _p(starts), C.addressof(M))
+    return rc, M.value, idx, starts, counts
+
+
+def gather_rows(X, idx, starts, goff_sub, Xdst):
+    X, idx, starts, goff_sub, Xdst = _a(X, f64), _a(idx, i64), _a(starts, i64), _a(goff_sub, i64), _io(Xdst, f64)
+    return hooks().lc_test_gather_rows(_p(X), X.shape[0], X.shape[1], _p(idx), idx.size, _p(starts), _p(goff_sub), starts.size - 1,
+                                       _p(Xdst), Xdst.shape[0])
+
+
+def gather_rows_plain(X, idx, Xdst):
+    X, idx, Xdst = _a(X, f64), _a(idx, i64), _io(Xdst, f64)
+    return hooks().lc_test_gather_rows_plain(_p(X), X.shape[0], X.shape[1], _p(idx), idx.size, _p(Xdst), Xdst.shape[0])
+
+
+def gather_cols(src, nsrc, idx, starts, goff_sub, dst):
+    """src column-major [K x lds], rows < nsrc; dst column-major [K x ldd]"""
+    src, idx, starts, goff_sub, dst = _a(src, f64), _a(idx, i64), _a(starts, i64), _a(goff_sub, i64), _io(dst, f64)
+    return hooks().lc_test_gather_cols(_p(src), src.shape[1], nsrc, src.shape[0], _p(idx), idx.size, _p(starts), _p(goff_sub),
+                                       starts.size - 1, _p(dst), dst.shape[1])
+
+
+def gather_rowmajor(src, K, idx, starts, goff_sub, dst):
+    """src row-major [nsrc x lds], its first K columns; dst column-major [K x ldd]"""
+    src, idx, starts, goff_sub, dst = _a(src, f64), _a(idx, i64), _a(starts, i64), _a(goff_sub, i64), _io(dst, f64)
+    return hooks().lc_test_gather_rowmajor(_p(src), src.shape[1], src.shape[0], K, _p(idx), idx.size, _p(starts), _p(goff_sub),
+                                           starts.size - 1, _p(dst), dst.shape[1])
+
+
+def gather_rowmajor_cols(src, cols, idx, starts, goff_sub, dst):
+    src, cols, idx, starts, goff_sub, dst = (_a(src, f64), _a(cols, i32), _a(idx, i64), _a(starts, i64), _a(goff_sub, i64),
+                                             _io(dst, f64))
+    return hooks().lc_test_gather_rowmajor_cols(_p(src), src.shape[1], src.shape[0], _p(cols), cols.size, _p(idx), idx.size,
+                                                _p(starts), _p(goff_sub), starts.size - 1, _p(dst), dst.shape[1])
+
+
+def scatter_cols(src, idx, dest):
+    """src [ncol x lds]; dest [ncol x ndst] in place: dest[t, idx[p]] = src[t, p]"""
+    src, idx, dest = _a(src, f64), _a(idx, i64), _io(dest, f64)
+    return hooks().lc_test_scatter_cols(_p(src), src.shape[1], src.shape[0], _p(dest), dest.shape[1], _p(idx), idx.size)
+
+
+def split_init(X, D, mv, q, mode, rginfo=None, nrows=0, ngroups=1, thr=None, NP=None):
+    X, mv, q, rg, thr = _a(X, f64), _a(mv, f64), _io(q, f64), _a(rginfo, i32), _a(thr, f64)
+    NP = X.shape[0] if NP is None else NP
+    assert mv.size == 2 * X.shape[1] and q.shape[0] == 2 and (thr is None or thr.size == ngroups)
+    return hooks().lc_test_split_init(_p(X), X.shape[1], D, NP, _p(rg), nrows, ngroups, _p(mv), _p(q), q.shape[1], mode, _p(thr))
+
+
+def aug_from_sub(q, NP, k, idx, starts, goff_sub, qsub1, qhash_arr=None):
+    """q [(K + 1) x ldq] in place"""
+    q, idx, starts, goff_sub, qsub1, qh = (_io(q, f64), _a(idx, i64), _a(starts, i64), _a(goff_sub, i64), _a(qsub1, f64),
+                                           _io(qhash_arr, i64))
+    assert qh is None or qh.size == NP
+    return hooks().lc_test_aug_from_sub(_p(q), q.shape[1], NP, k, q.shape[0] - 1, _p(idx), idx.size, _p(starts), _p(goff_sub),
+                                        starts.size - 1, _p(qsub1), qsub1.size, _p(qh))
+
+
+def transpose_qz(qZ, NP, qT):
+    q, qT = _a(qZ, f64), _io(qT, f64)
+    return hooks().lc_test_transpose_qz(_p(q), q.shape[1], q.shape[0], NP, _p(qT), qT.size)
+
+
+def softmax_cached(dcache, ctab, K, NP, qZ, fz_part, fresh=None, colmap=None, rginfo=None, nrows=0, ll_part=None, dq=None,
+                   amax=None, qhash_arr=None, qhash_in=0, rmax=None, ramax=None, colmask=None):
+    """dcache [Kc x ldc], fresh [nfresh x ldf], ctab [J x K]; qZ [Kq x ldq], fz_part [nblk], ll_part [nblk x K], dq [NP x ldd],
+    amax / qhash / rmax / ramax [NP], colmask [2]: all destinations in place."""
+    dc, ct, fr, cm, rg = _a(dcache, f64), _a(ctab, f64), _a(fresh, f64), _a(colmap, i32), _a(rginfo, i32)
+    assert ct.ndim == 2 and ct.shape[1] == K and (cm is None or cm.size == K)
+    q, fz, ll, dq, amax = _io(qZ, f64), _io(fz_part, f64), _io(ll_part, f64), _io(dq, f64), _io(amax, f64)
+    qh, rmax, ramax, cmk = _io(qhash_arr, i64), _io(rmax, f64), _io(ramax, i32), _io(colmask, u64)
+    assert ll is None or ll.shape == (fz.size, K)
+    for v in (amax, qh, rmax, ramax):
+        assert v is None or v.size == NP
+    assert dq is None or dq.shape[0] == NP
+    assert cmk is None or cmk.size == 2
+    return hooks().lc_test_softmax_cached(_p(dc), dc.shape[0], dc.shape[1], _p(fr), 0 if fr is None else fr.shape[0],
+                                          0 if fr is None else fr.shape[1], _p(cm), _p(ct), ct.shape[0], K, _p(rg), nrows, NP,
+                                          _p(q), q.shape[0], q.shape[1], _p(fz), fz.size, _p(ll), _p(dq),
+                                          0 if dq is None else dq.shape[1], _p(amax), _p(qh), qhash_in, _p(rmax), _p(ramax), _p(cmk))
+
+
+def qhash_verify(qZ, K, NP, qhash_arr):
+    """-> status, number of rows whose stored fingerprint does not describe them"""
+    q, qh = _a(qZ, f64), _a(qhash_arr, i64)
+    bad = C.c_ulonglong(0)
+    rc = hooks().lc_test_qhash_verify(_p(q), q.shape[1], K, NP, _p(qh), C.addressof(bad))
+    return rc, bad.value
+
+
+def qz_resync(dst, src, K, NP, dhash, shash):
+    dst, src, dhash, shash = _io(dst, f64), _a(src, f64), _io(dhash, i64), _a(shash, i64)
+    assert src.shape[1] == dst.shape[1] and src.shape[0] == K
+    return hooks().lc_test_qz_resync(_p(dst), _p(src), dst.shape[1], K, dst.shape[0], NP, _p(dhash), _p(shash))
+
+
+def bound_select(K, ref, dest, sigma, bnorm, cnew, rmax, ramax, T, usable, dcj, need):
+    """ref / dest [ncol x NP] (dest, need in place); usable, dcj [K]"""
+    ref, dest, need = _a(ref, f64), _io(dest, f64), _io(need, f64)
+    sigma, bnorm, cnew, rmax, ramax = _a(sigma, f64), _a(bnorm, f64), _a(cnew, f64), _a(rmax, f64), _a(ramax, i32)
+    usable, dcj = _a(usable, u8), _a(dcj, f64)
+    ncol, NP = ref.shape
+    assert dest.shape == ref.shape and sigma.size == bnorm.size == cnew.size == ncol and usable.size == dcj.size == K
+    assert rmax.size == ramax.size == need.size == NP
+    return hooks().lc_test_bound_select(ncol, K, NP, _p(ref), _p(dest), _p(sigma), _p(bnorm), _p(cnew), _p(rmax), _p(ramax), T,
+                                        _p(usable), _p(dcj), _p(need))

@@ -33,6 +33,45 @@ def test_library_leaves_no_cxx_template_member_undefined():
         assert not bad, (name, bad)
 
 
+def test_test_hooks_live_in_the_hooks_library_only(lib):
+    """The lc_test_* entry points (csrc/lc_testhooks.hip: single launchers on host arrays, tests/test_gpu_aux_kernels.py)
+    are linked into libcluster_hip_testhooks.so only: the shipped library exports none of them, the hooks library every
+    one the Python helper declares -- and otherwise the same symbols as the shipped one.  (Both load without a GPU.)"""
+    import aux_hooks
+
+    shipped = aux_hooks.exported_symbols(aux_hooks.SHIPPED_LIB)
+    hooked = aux_hooks.exported_symbols(aux_hooks.HOOKS_LIB)
+    assert not [s for s in shipped if s.startswith("lc_test_")]
+    declared = set(aux_hooks.PROTOTYPES)
+    assert len(declared) >= 21 and declared <= hooked, sorted(declared - hooked)
+    assert {s for s in hooked if s.startswith("lc_test_")} == declared  # no hook without a prototype either
+    assert {s for s in shipped if s.startswith("lc_")} == {s for s in hooked if s.startswith("lc_")} - declared
+    h = aux_hooks.hooks()  # loads, and every prototype binds
+    assert all(hasattr(h, n) for n in declared)
+
+
+def test_aux_hooks_constants_are_those_of_the_sources():
+    """tests/aux_hooks.py restates the constants that decide which path a launcher takes; the cases of
+    tests/test_gpu_aux_kernels.py sit on both sides of them."""
+    import re
+
+    import aux_hooks
+
+    csrc = ROOT / "libcluster_amd" / "csrc"
+    text = "".join((csrc / f).read_text() for f in ("lc_kernels.h", "lc_device.hpp", "lc_kernels_aux.hip"))
+
+    def const(name):
+        m = re.findall(r"\b" + name + r"\s*=\s*(?:\(int64_t\))?(0x[0-9A-Fa-f]+|\d+)", text)
+        assert len(m) == 1, (name, m)
+        return int(m[0], 0)
+
+    for name in ("REDUCE_TMP_ELEMS", "SEL_ROWS", "GCS_SLICES", "BOUND_MAX_COLS", "BOUND_MAX_K", "QHASH_SEED"):
+        assert const(name) == getattr(aux_hooks, name), name
+    assert const("QHASH_NONE") - (1 << 64) == aux_hooks.QHASH_NONE
+    assert "if (tmp && nparts > 8192 && n <= REDUCE_TMP_ELEMS)" in text and "nparts > 512 && n <= 4096" in text
+    assert "rows >= (int64_t)J * 65536" in text and "if (J > 1024)" in text  # the boundaries the test file names
+
+
 def test_constants(lib):
     assert lib.lc_const_converge() == o.CONVERGE
     assert lib.lc_const_fengydel() == o.FENGYDEL
