@@ -359,6 +359,29 @@ int lc_tmodel_cluster(lc_tmodel* m, int level, int idx, double* N, double* mean,
 int lc_tmodel_rounds(lc_tmodel* m, int* nrounds);
 int lc_tmodel_round(lc_tmodel* m, int r, int* T, int* K, int* niter, double* F, int nF);
 
+/* ---- inference for new documents with a learned SCM / MCM model (nothing in the reference corresponds: its users would
+ * iterate vbeY / vbeZ, scluster.cpp:50-124 / mcluster.cpp:49-135, by hand with the posteriors held fixed).  Every block
+ * of ctx is one document; nothing learned is updated.  With a_t = E[log pi_gt] (+ Eloglike_t(w_i), MCM),
+ * E_tk = E[log pi_tk] and L_nk = Eloglike_k(x_n):
+ *   qY^0 = softmax_t(a_t); sweep r = 1, 2, ...: c_k = sum_t qY^{r-1}_t E_tk, q_nk = softmax_k(c_k + L_nk),
+ *   N_k = sum_n q_nk; like_t = sum_k N_k E_tk, qY^r = softmax_t(a_t + like_t); delta_r = max_t |qY^r_t - qY^{r-1}_t|.
+ * A document stops after sweep R, the first with delta_R <= tol, or R = max_sweeps (tol < 0: always max_sweeps; a
+ * document without rows has delta_1 = 0).  One last vbeZ with qY^R gives qZ (keep_qz != 0: the context's qZ), and per row
+ * logZ and label (argmax_k of c_k + L_nk, lowest k on ties), read with lc_ctx_get_predictions (logp: LC_EINVAL, there
+ * is no density).  Per document: qY^R, label_t (argmax, lowest t on ties), Fyz = sum_t qY^R_t like_t - logZ_y of sweep
+ * R, Fz = -sum_n logZ_n of the last vbeZ, and R.  The sweeps of a document run on the device without host round trips.
+ * LC_EINVAL: D mismatch ("Mismatched dims. of cluster params and obs.!"), W given for an SCM model or missing for an
+ * MCM model, a group index outside [0, J), max_sweeps < 1, a freed model, and a model whose per-document vectors
+ * (4 T + 6 K doubles and a few) do not fit the kernel's 40 KB of LDS: K of about 800 and above ("the model is too
+ * large for the inference kernel"). */
+/* groups[doc]: learned group of every document of ctx (NULL: group 0); W: docs x Dt row-major (MCM; must be NULL for SCM) */
+int lc_tmodel_predict(lc_tmodel* m, lc_ctx* ctx, const int* groups, const double* W, int max_sweeps, double tol, int keep_qz);
+/* documents [doc0, doc0+n) of the last lc_tmodel_predict on ctx; any output may be NULL; qY is n x T row-major */
+int lc_ctx_get_doc_predictions(lc_ctx* ctx, int doc0, int n, double* qY, int32_t* label_t, double* Fyz, double* Fz, int32_t* sweeps);
+/* free the training documents and qZ; the parameters stay (as lc_model_release_data): lc_tmodel_predict still works
+ * while the qY / qZ accessors return LC_EINVAL */
+int lc_tmodel_release_data(lc_tmodel* m);
+
 /* ======================================================================== *
  * Host-only pieces of the path (no GPU needed; used by the C++ facade classes
  * and by tests of the host arithmetic).

@@ -122,7 +122,7 @@ def learnEGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads
                     return_model)
 
 
-def _topic_result(F, m, mcm, return_info):
+def _topic_result(F, m, mcm, return_info, return_model=False):
     d = m.dims()
     qY, qZ = m.qY(), m.qZ()
     wj = [np.exp(m.weights(0, j)[0]).reshape(-1, 1) for j in range(d["J"])]
@@ -132,30 +132,33 @@ def _topic_result(F, m, mcm, return_info):
     info = {"T": d["T"], "K": d["K"], "rounds": m.rounds(), "clusters_k": ck, "clusters_t": ct,
             "Elogweight_j": [m.weights(0, j)[0] for j in range(d["J"])],
             "Elogweight_t": [m.weights(1, t)[0] for t in range(d["T"])]}
-    m.close()
+    if not return_model:
+        m.close()
     mean = lambda cs: [c["mean"].reshape(1, -1) for c in cs]  # noqa: E731
     cov = lambda cs: [c["cov"] for c in cs]  # noqa: E731
     if mcm:  # libclusterpy.cpp:305-307
         out = (F, qY, qZ, wj, wt, mean(ct), mean(ck), cov(ct), cov(ck))
     else:    # libclusterpy.cpp:270-271
         out = (F, qY, qZ, wj, wt, mean(ck), cov(ck))
-    return out + (info,) if return_info else out
+    out = out + (info,) if return_info else out
+    return out + (m,) if return_model else out
 
 
 def learnSCM(X, dirprior=1.0, gausprior=1.0, trunc=100, maxclusters=-1, verbose=False, threads=None, *,
-             nthreads=None, qY0=None, device=0, return_info=False):
+             nthreads=None, qY0=None, device=0, return_info=False, return_model=False):
     """libclusterpy.h:397-425 / include/libcluster.h:583-596.  X: list (groups) of lists (documents) of (N_ji, D)
     arrays.  Returns (f, qY, qZ, w_j, w_t, mu, cov).  qY0: initial (I_j, trunc) top-level assignments instead of the
-    reference's std::rand() start."""
+    reference's std::rand() start.  return_model: the open capi.TopicModel (predict, release_data) as the last
+    element."""
     F, m = capi.learn_topic(X, None, qY0, _f32(dirprior), _f32(gausprior), int(trunc), maxclusters, verbose,
                             _threads(threads, nthreads), device)
-    return _topic_result(F, m, False, return_info)
+    return _topic_result(F, m, False, return_info, return_model)
 
 
 def learnMCM(W, X, gausprior_t=1.0, gausprior_k=1.0, trunc=100, maxclusters=-1, verbose=False, threads=None, *,
-             nthreads=None, qY0=None, device=0, return_info=False):
+             nthreads=None, qY0=None, device=0, return_info=False, return_model=False):
     """libclusterpy.h:427-458 / include/libcluster.h:661-676.  W: list of (I_j, D_t) document observations.
-    Returns (f, qY, qZ, w_j, w_t, mu_t, mu_k, cov_t, cov_k)."""
+    Returns (f, qY, qZ, w_j, w_t, mu_t, mu_k, cov_t, cov_k).  return_model: as learnSCM."""
     F, m = capi.learn_topic(X, W, qY0, _f32(gausprior_t), _f32(gausprior_k), int(trunc), maxclusters, verbose,
                             _threads(threads, nthreads), device)
-    return _topic_result(F, m, True, return_info)
+    return _topic_result(F, m, True, return_info, return_model)

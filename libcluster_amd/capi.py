@@ -6,7 +6,7 @@ from __future__ import annotations
 import ctypes as C
 import re
 from pathlib import Path
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -35,6 +35,19 @@ class Prediction(NamedTuple):
     logZ: np.ndarray
     logp: np.ndarray
     qZ: np.ndarray | None
+
+
+class TopicPrediction(NamedTuple):
+    """Outputs of TopicModel.predict (lc_tmodel_predict).  Per document: qY (docs, T), label_t (int32), Fyz, Fz, sweeps
+    (int32); per document lists of per-row arrays: label (int32), logZ, qZ ((N_i, K) each, or None)."""
+    qY: np.ndarray
+    label_t: np.ndarray
+    Fyz: np.ndarray
+    Fz: np.ndarray
+    sweeps: np.ndarray
+    label: list
+    logZ: list
+    qZ: Optional[list]
 
 
 def comm_unique_id() -> bytes:
@@ -217,6 +230,10 @@ def lib() -> C.CDLL:
                                     c_double_p, c_double_p, c_double_p, c_double_p]
     L.lc_tmodel_rounds.argtypes = [C.c_void_p, c_int_p]
     L.lc_tmodel_round.argtypes = [C.c_void_p, C.c_int, c_int_p, c_int_p, c_int_p, c_double_p, C.c_int]
+    L.lc_tmodel_predict.argtypes = [C.c_void_p, C.c_void_p, c_int_p, c_double_p, C.c_int, C.c_double, C.c_int]
+    L.lc_ctx_get_doc_predictions.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, C.POINTER(C.c_int32), c_double_p,
+                                             c_double_p, C.POINTER(C.c_int32)]
+    L.lc_tmodel_release_data.argtypes = [C.c_void_p]
     L.lc_ng_mstep.argtypes = [C.c_double, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p,
                               c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
     L.lc_eg_mstep.argtypes = [C.c_double, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p,
@@ -541,6 +558,15 @@ class Context:
                                                dptr(logZ), dptr(lp)))
         return label, logZ, lp
 
+    def get_doc_predictions(self, doc0, n, T):
+        """Documents [doc0, doc0+n) of the last TopicModel.predict_context on this context -> (qY (n, T), label_t int32,
+        Fyz, Fz, sweeps int32)."""
+        qY, lt, sw = np.zeros((n, T)), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        Fyz, Fz = np.zeros(n), np.zeros(n)
+        check(lib().lc_ctx_get_doc_predictions(self._h, doc0, n, dptr(qY), lt.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               dptr(Fyz), dptr(Fz), sw.ctypes.data_as(C.POINTER(C.c_int32))))
+        return qY, lt, Fyz, Fz, sw
+
     def synchronize(self):
         check(lib().lc_ctx_synchronize(self._h))
 
@@ -839,6 +865,44 @@ class TopicModel:
             check(lib().lc_tmodel_round(self._h, r, None, None, None, dptr(F), ni.value))
             out.append((T.value, K.value, F.tolist()))
         return out
+
+    # -- inference for new documents ---------------------------------------------------------------
+    def predict_context(self, ctx, W=None, groups=None, max_sweeps=50, tol=None, keep_qz=False):
+        """Infer the documents resident in ctx (lc_tmodel_predict; one block per document): document i with the weights
+        of learned group groups[i] (None: 0) and, for an MCM model, its observation W[i].  tol: None = CONVERGE, < 0 =
+        exactly max_sweeps sweeps.  Nothing is downloaded: read the results with ctx.get_doc_predictions /
+        ctx.get_predictions / ctx.get_qz."""
+        docs = ctx.dims()[0]
+        g = w = None
+        if groups is not None:
+            garr = np.ascontiguousarray(groups, dtype=np.int32)
+            if garr.shape != (docs,):
+                raise ValueError("groups needs one learned group index per document of the context")
+            g = garr.ctypes.data_as(C.POINTER(C.c_int))
+        if W is not None:
+            warr = np.ascontiguousarray(W, dtype=np.float64)
+            if warr.ndim != 2 or warr.shape != (docs, self.dims()["Dt"]):
+                raise ValueError("W and X need to have the same number of 'docs'!")
+            w = dptr(warr)
+        tol = float(lib().lc_const_converge()) if tol is None else float(tol)
+        check(lib().lc_tmodel_predict(self._h, ctx._h, g, w, int(max_sweeps), tol, int(keep_qz)))
+
+    def predict(self, X, W=None, groups=None, max_sweeps=50, tol=None, qz=False, device=0):
+        """TopicPrediction for the documents X, a list of (N_i, D) arrays (W: (docs, Dt) for an MCM model)."""
+        d = self.dims()
+        Xs = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, d["D"])) for x in X]
+        with Context(device) as ctx:
+            ctx.set_data(Xs)
+            self.predict_context(ctx, W, groups, max_sweeps, tol, keep_qz=qz)
+            rows = [x.shape[0] for x in Xs]
+            qY, lt, Fyz, Fz, sw = ctx.get_doc_predictions(0, len(Xs), d["T"])
+            per = [ctx.get_predictions(i, 0, n, logp=False) for i, n in enumerate(rows)]
+            qs = [q.copy() for q in ctx.get_qz(rows)] if qz else None
+        return TopicPrediction(qY, lt, Fyz, Fz, sw, [p[0] for p in per], [p[1] for p in per], qs)
+
+    def release_data(self):
+        """Free the training documents, qY and qZ; the parameters (and predict) stay."""
+        check(lib().lc_tmodel_release_data(self._h))
 
 
 def learn_topic(X, W=None, qY0=None, prior_t=1.0, prior_k=1.0, maxT=100, maxK=-1, verbose=False, nthreads=1,

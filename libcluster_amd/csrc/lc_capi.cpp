@@ -28,7 +28,8 @@
 #include <unordered_set>
 
 namespace {
-// every lc_model that exists: lc_model_predict / lc_model_release_data answer LC_EINVAL for a handle that was freed
+// every lc_model / lc_tmodel that exists: lc_model_predict / lc_model_release_data (and their lc_tmodel counterparts)
+// answer LC_EINVAL for a handle that was freed
 std::mutex g_models_mu;
 std::unordered_set<const void*> g_models;
 void model_registry(const void* m, bool add) {
@@ -80,7 +81,11 @@ struct lc_model {
 };
 
 struct lc_tmodel {
-  std::unique_ptr<lc_ctx> ctx;  // one group per document; holds qZ
+  lc_tmodel() { model_registry(this, true); }
+  ~lc_tmodel() { model_registry(this, false); }
+  lc_tmodel(const lc_tmodel&) = delete;
+  lc_tmodel& operator=(const lc_tmodel&) = delete;
+  std::unique_ptr<lc_ctx> ctx;  // one group per document; holds qZ (null after lc_tmodel_release_data)
   lce::TopicData data;
   lce::TopicModel model;
   std::vector<double> W;        // I_tot x Dt (MCM)
@@ -1332,6 +1337,7 @@ int lc_tmodel_get_qy(lc_tmodel* m, int j, double* qY) {
     need(m, "model");
     need(qY, "qY");
     if (j < 0 || j >= m->data.J) throw std::invalid_argument("group index out of range");
+    if (!m->ctx) throw std::invalid_argument("the model's training data was released");
     const int T = m->model.T;
     std::copy(m->model.qY.begin() + (size_t)m->doc0[(size_t)j] * T, m->model.qY.begin() + (size_t)m->doc0[(size_t)j + 1] * T,
               qY);
@@ -1342,6 +1348,7 @@ int lc_tmodel_get_qz(lc_tmodel* m, int doc, double* q, int64_t rs, int64_t cs) {
   return guarded([&] {
     need(m, "model");
     need(q, "q");
+    if (!m->ctx) throw std::invalid_argument("the model's training data was released");
     m->ctx->impl.qz_get(doc, q, rs, cs);
   });
 }
@@ -1350,6 +1357,7 @@ int lc_tmodel_get_qz_all(lc_tmodel* m, double* q) {
   return guarded([&] {
     need(m, "model");
     need(q, "q");
+    if (!m->ctx) throw std::invalid_argument("the model's training data was released");
     m->ctx->impl.qz_get_all(q);
   });
 }
@@ -1358,6 +1366,7 @@ int lc_tmodel_get_qz_all_colmajor(lc_tmodel* m, double* const* q) {
   return guarded([&] {
     need(m, "model");
     need(q, "q");
+    if (!m->ctx) throw std::invalid_argument("the model's training data was released");
     m->ctx->impl.qz_get_all_colmajor(q);
   });
 }
@@ -1414,6 +1423,49 @@ int lc_tmodel_round(lc_tmodel* m, int r, int* T, int* K, int* niter, double* F, 
     if (niter) *niter = (int)rd.F.size();
     if (F)
       for (int i = 0; i < nF && i < (int)rd.F.size(); ++i) F[i] = rd.F[(size_t)i];
+  });
+}
+
+// ---- inference for new documents ------------------------------------------------------------------
+// vbeY / vbeZ (scluster.cpp:50-124, mcluster.cpp:49-135) iterated per document with the model's final posteriors
+int lc_tmodel_predict(lc_tmodel* m, lc_ctx* ctx, const int* groups, const double* W, int max_sweeps, double tol,
+                      int keep_qz) {
+  return guarded([&] {
+    need(m, "model");
+    need(ctx, "ctx");
+    if (!model_alive(m)) throw std::invalid_argument("the model was freed");
+    if (ctx->impl.D() != m->D) throw std::invalid_argument("Mismatched dims. of cluster params and obs.!");  // vbem, :193
+    const bool mcm = !m->model.clusters_t.empty();
+    if (mcm && !W) throw std::invalid_argument("W and X need to have the same number of 'docs'!");  // mcluster.cpp:553-555
+    if (!mcm && W) throw std::invalid_argument("W must be NULL for an SCM model");
+    if (max_sweeps < 1) throw std::invalid_argument("max_sweeps must be at least 1");
+    for (int b = 0; b < ctx->impl.J(); ++b) {
+      const int j = groups ? groups[b] : 0;
+      if (j < 0 || j >= m->data.J) throw std::invalid_argument("group index out of range");
+    }
+    lce::topic_predict(ctx->impl, m->model, groups, W, max_sweeps, tol, keep_qz != 0);
+  });
+}
+
+int lc_ctx_get_doc_predictions(lc_ctx* ctx, int doc0, int n, double* qY, int32_t* label_t, double* Fyz, double* Fz,
+                               int32_t* sweeps) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.get_doc_predictions(doc0, n, qY, label_t, Fyz, Fz, sweeps);
+  });
+}
+
+int lc_tmodel_release_data(lc_tmodel* m) {
+  return guarded([&] {
+    need(m, "model");
+    if (!model_alive(m)) throw std::invalid_argument("the model was freed");
+    m->ctx.reset();
+    m->data.W = nullptr;
+    std::vector<double>().swap(m->W);
+    std::vector<double>().swap(m->model.qY);
+    std::vector<double>().swap(m->model.lastA);
+    std::vector<double>().swap(m->model.lastm);
+    std::vector<double>().swap(m->model.lastc);
   });
 }
 

@@ -263,7 +263,16 @@ class Context {
   // rows [row0, row0+n) of group j of the last prediction (any output may be null)
   void get_predictions(int j, int64_t row0, int64_t n, int32_t* label, double* logZ, double* logp) const;
   // no prediction is readable until the next one completes (a prediction that fails leaves none behind)
-  void predict_clear() { pred_vb_ = pred_logp_ = false; }
+  void predict_clear() {
+    pred_vb_ = pred_logp_ = false;
+    pred_docs_T_ = 0;
+  }
+  // Two-level models (lc_topic_predict.cpp): after a raw E-step left L_nk = Eloglike_k(x_n) in K columns of
+  // qZ, every group of the context is one document: its qY, label_t, Fyz, Fz and sweep count into the context's
+  // per-document outputs, label / logZ per row as above (lck::TopicInferLaunch; a: J x T, E: T x K host arrays).
+  void topic_infer(int K, int T, const double* a, const double* E, int max_sweeps, double tol, bool keep_q);
+  // documents [doc0, doc0+n) of the last topic_infer (any output may be null; qY: n x T row-major)
+  void get_doc_predictions(int doc0, int n, double* qY, int32_t* label_t, double* Fyz, double* Fz, int32_t* sweeps) const;
 
   // Host work to run while the NEXT normalising E-step is on the device: the E-step calls it once, after its last
   // launch and before it waits for the stream (vbem hands over the free-energy terms that depend on the posteriors
@@ -417,6 +426,11 @@ class Context {
   DevBuf<int> plabel_, pflag_;
   DevBuf<double> plogz_, plogp_, ptab_;
   bool pred_vb_ = false, pred_logp_ = false;
+  // per-document outputs of the last topic_infer ([J x T], [J x 2], [J x 2]); pred_docs_T_ = its T (0: none)
+  DevBuf<double> tqy_, tf_;
+  DevBuf<int> tint_;
+  DevBuf<int64_t> tnrows_;
+  int pred_docs_T_ = 0;
   PinnedBuf hpack_, hred_, hss_, hmask_;
   std::function<void()> overlap_;
 

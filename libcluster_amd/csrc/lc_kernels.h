@@ -464,4 +464,35 @@ struct SynthLaunch {
 };
 hipError_t launch_synth(const SynthLaunch& a, hipStream_t stream);
 
+// topic_infer_kernel (lc_kernels_topic.hip): the class of every document and the segments of its rows
+// under a learned SCM / MCM model, one workgroup per document.  col holds L_nk = Eloglike_k(x_n) (a raw E-step with the
+// clusters' constants); per document the kernel iterates vbeZ / vbeY (scluster.cpp:50-124) with the model fixed until
+// its own qY moves by <= tol (tol < 0: exactly max_sweeps sweeps), then runs one last vbeZ for the per-row outputs.
+struct TopicInferLaunch {
+  double* col = nullptr;  // [K columns x ldq]; with keep_q the documents' rows become q
+  int64_t ldq = 0;
+  int K = 0, T = 0, docs = 0;
+  const int64_t* goff = nullptr;   // [docs] first (padded) row of every document
+  const int64_t* nrows = nullptr;  // [docs] rows of every document
+  const double* a = nullptr;       // [docs x T] E[log pi_gt] (+ Eloglike_t(w_i), MCM)
+  const double* E = nullptr;       // [T x K] E[log pi_tk]
+  int max_sweeps = 1;
+  double tol = 0.0;
+  int keep_q = 0;
+  int threads = 64;       // workgroup size (64, 128 or 256), from the largest document
+  int64_t tile_cap = 0;   // doubles of LDS for a document's L tile (N_i K <= tile_cap: the sweeps never leave the CU)
+  int e_lds = 0;          // E lives in LDS (T K <= TOPIC_E_LDS)
+  int* label = nullptr;   // [NP] per row
+  double* logZ = nullptr; // [NP]
+  double* qY = nullptr;   // [docs x T]
+  double* F = nullptr;    // [docs x 2] Fyz, Fz
+  int* dint = nullptr;    // [docs x 2] label_t, sweeps
+};
+constexpr int TOPIC_E_LDS = 128;            // doubles: the largest E table kept in LDS
+constexpr int TOPIC_LDS_BYTES = 40 * 1024;  // per workgroup at most: four workgroups per CU whatever the documents' size
+// dynamic LDS of a launch over documents of nrows[docs] (host array) rows: the small vectors, the E table when it fits
+// and the largest L tile among the documents that fit the budget (*tile_cap); 0: K and T are too large for the budget
+size_t topic_infer_lds(int K, int T, int threads, const int64_t* nrows, int docs, int64_t* tile_cap, int* e_lds);
+hipError_t launch_topic_infer(const TopicInferLaunch& a, size_t lds_bytes, hipStream_t stream);
+
 }  // namespace lck

@@ -57,4 +57,11 @@ double topic_vbem(lcc::Context& ctx, const TopicData& data, TopicModel& model, c
 double topic_cluster(lcc::Context& ctx, const TopicData& data, TopicModel& model, const TopicOptions& opt,
                      std::vector<TopicRound>* rounds);
 
+// Inference for new documents with the model held fixed (lc_topic_predict.cpp): every group of ctx is one
+// document, scored with the weights of learned group groups[doc] (null: 0) and, for the MCM, its observation
+// W[doc * Dt ..] (null: SCM).  Leaves the per-document and per-row outputs in the context, and the responsibilities in
+// its qZ with keep_qz.  Uses weights_j, weights_t, clusters and clusters_t only.
+void topic_predict(lcc::Context& ctx, const TopicModel& model, const int* groups, const double* W, int max_sweeps,
+                   double tol, bool keep_qz);
+
 }  // namespace lce
