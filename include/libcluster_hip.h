@@ -306,6 +306,26 @@ int lc_model_fenergy(lc_model* m, double* Fw /*[J]*/, double* Fc /*[K]*/);
 int lc_model_predict(lc_model* m, lc_ctx* ctx, const int* groups /* [J of ctx] or NULL */, int keep_qz);
 /* rows [row0, row0+n) of block j of the last prediction on ctx (like lc_ctx_get_qz_rows); any output may be NULL */
 int lc_ctx_get_predictions(lc_ctx* ctx, int j, int64_t row0, int64_t n, int32_t* label, double* logZ, double* logp);
+/* ---- ranking on the device (nothing in the reference corresponds): the m best rows of each of C device-resident
+ * columns, 1 <= m <= 64, without bringing the columns to the host.  Entry a is better than entry b when its score is larger
+ * (largest != 0; smaller otherwise), or the scores compare equal (+0.0 and -0.0 do) and a comes first in the context (lower
+ * block, then lower row): a total order, so the answer is unique.  A NaN score is never selected.
+ *   LC_RANK_QZ:   C = ncols, the first ncols columns of the context's qZ, whatever they hold (1 <= ncols <= K of lc_ctx_dims);
+ *                 by_label != 0: column c only sees the rows the last prediction on ctx labelled c
+ *   LC_RANK_LOGZ, LC_RANK_LOGP: C = 1, the per-row logZ / logp of the last prediction on ctx (ncols is not looked at)
+ * count[C]; group[C*m] (block of ctx), row[C*m] (row within its block), score[C*m]: best first; entries past count[c] are
+ * -1, -1, NaN.  Outliers: lc_model_predict, then lc_ctx_top_rows(ctx, LC_RANK_LOGP, 1, m, 0, 0, ...).
+ * LC_EINVAL: m outside 1 ... 64, ncols outside 1 ... K, by_label / LC_RANK_LOGZ / LC_RANK_LOGP without a prediction on ctx
+ * (LC_RANK_LOGP: one with a log density), by_label together with LC_RANK_LOGZ / LC_RANK_LOGP, a context without data. */
+enum { LC_RANK_QZ = 0, LC_RANK_LOGZ = 1, LC_RANK_LOGP = 2 };
+int lc_ctx_top_rows(lc_ctx* ctx, int what, int ncols, int m, int largest, int by_label, int32_t* count, int32_t* group, int64_t* row, double* score);
+/* Exemplars: lc_model_predict(m, ctx, groups, 0), then per cluster k the mtop rows labelled k (by that prediction) with the
+ * largest Eloglike_k(x) -- for Gauss-Wishart clusters the smallest expected Mahalanobis distance; the responsibility is no
+ * use here: in a separated mixture most rows of a cluster have q = 1.0 exactly.  C = K; score = Eloglike_k(x_n), the raw
+ * data term ranked on the device plus the cluster's constant, added on the host to K*mtop values.  Same side effects on
+ * ctx as lc_model_predict(..., 0): its prediction is replaced and its qZ holds intermediate values afterwards (the raw
+ * data terms, K columns).  LC_EINVAL as lc_model_predict and lc_ctx_top_rows. */
+int lc_model_exemplars(lc_model* m, lc_ctx* ctx, const int* groups, int mtop, int32_t* count, int32_t* group, int64_t* row, double* score);
 /* free the training observations and qZ (and shards) of a model; its parameters stay, so lc_model_predict still works
  * while the qZ accessors return LC_EINVAL.  A borrowed context (lc_vbem, lc_cluster) is left to its owner. */
 int lc_model_release_data(lc_model* m);

@@ -20,6 +20,7 @@ LC_OK, LC_EINVAL, LC_ERUNTIME, LC_EHIP, LC_EDOMAIN = range(5)
 W_DIRICHLET, W_STICKBREAK, W_GDIRICHLET = 0, 1, 2
 ALGO_VDP, ALGO_BGMM, ALGO_GMC, ALGO_SGMC, ALGO_DGMM, ALGO_BEMM, ALGO_DGMC, ALGO_EGMC = range(8)
 C_GAUSSWISH, C_NORMGAMMA, C_EXPGAMMA = 0, 1, 2
+RANK_QZ, RANK_LOGZ, RANK_LOGP = 0, 1, 2  # LC_RANK_*: what lc_ctx_top_rows ranks
 
 c_double_p = C.POINTER(C.c_double)
 c_int64_p = C.POINTER(C.c_int64)
@@ -35,6 +36,16 @@ class Prediction(NamedTuple):
     logZ: np.ndarray
     logp: np.ndarray
     qZ: np.ndarray | None
+
+
+class TopRows(NamedTuple):
+    """The m best rows of each of C columns (lc_ctx_top_rows, lc_model_exemplars), best first: count (C,) int32, group
+    (C, m) int32 (block of the context / of X), row (C, m) int64 (row of that block), score (C, m); the entries past
+    count[c] are -1, -1, NaN."""
+    count: np.ndarray
+    group: np.ndarray
+    row: np.ndarray
+    score: np.ndarray
 
 
 class TopicPrediction(NamedTuple):
@@ -243,6 +254,9 @@ def lib() -> C.CDLL:
     L.lc_ctx_get_predictions.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_int32_p, c_double_p, c_double_p]
     L.lc_model_release_data.argtypes = [C.c_void_p]
     L.lc_weights_predictive.argtypes = [C.c_int, C.c_double, c_double_p, C.c_int, c_double_p, c_double_p]
+    L.lc_ctx_top_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p, c_int64_p,
+                                  c_double_p]
+    L.lc_model_exemplars.argtypes = [C.c_void_p, C.c_void_p, c_int_p, C.c_int, c_int32_p, c_int32_p, c_int64_p, c_double_p]
     _lib = L
     return L
 
@@ -271,6 +285,17 @@ def dptr(a):
 def _strides(a: np.ndarray):
     assert a.ndim == 2 and a.dtype == np.float64
     return a.strides[0] // 8, a.strides[1] // 8
+
+
+def _top_rows_call(call, C_, m):
+    """the output arrays of lc_ctx_top_rows / lc_model_exemplars for C_ columns of m entries -> TopRows"""
+    shape = (max(C_, 0), max(min(m, 64), 0))  # (out-of-range arguments are the library's to refuse: nothing is written)
+    count = np.zeros(shape[0], dtype=np.int32)
+    group, row = np.full(shape, -1, dtype=np.int32), np.full(shape, -1, dtype=np.int64)
+    score = np.full(shape, np.nan)
+    c_int32_p = C.POINTER(C.c_int32)
+    check(call(count.ctypes.data_as(c_int32_p), group.ctypes.data_as(c_int32_p), row.ctypes.data_as(c_int64_p), dptr(score)))
+    return TopRows(count, group, row, score)
 
 
 class Context:
@@ -558,6 +583,21 @@ class Context:
                                                dptr(logZ), dptr(lp)))
         return label, logZ, lp
 
+    def top_rows(self, m, by="qz", largest=True, ncols=None, by_label=False):
+        """TopRows of the m best rows (1 ... 64) of each column, ranked on the device (lc_ctx_top_rows): by="qz" the first
+        ncols columns of qZ (None: all), by="logz" / "logp" the per-row outputs of the last prediction on this context
+        (one column).  Ties go to the earlier row; NaN scores and pad rows are never selected.  by_label: column c only
+        sees the rows the last prediction labelled c."""
+        what = {"qz": RANK_QZ, "logz": RANK_LOGZ, "logp": RANK_LOGP}.get(by)
+        if what is None:
+            raise ValueError("by must be 'qz', 'logz' or 'logp'")
+        if what != RANK_QZ:
+            ncols = 1
+        elif ncols is None:
+            ncols = self.dims()[3]
+        return _top_rows_call(lambda *out: lib().lc_ctx_top_rows(self._h, what, int(ncols), int(m), int(bool(largest)),
+                                                                 int(bool(by_label)), *out), int(ncols), int(m))
+
     def get_doc_predictions(self, doc0, n, T):
         """Documents [doc0, doc0+n) of the last TopicModel.predict_context on this context -> (qY (n, T), label_t int32,
         Fyz, Fz, sweeps int32)."""
@@ -710,6 +750,38 @@ class Model:
             out = [Prediction(*ctx.get_predictions(j, 0, n), None if q is None else q.copy())
                    for j, (n, q) in enumerate(zip(rows, qs))]
         return out if blocks else out[0]
+
+    # -- ranking -------------------------------------------------------------------------------------
+    def _blocks(self, X):
+        blocks = isinstance(X, (list, tuple))
+        Xs = list(X) if blocks else [X]
+        return [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, self.dims()[2])) for x in Xs]
+
+    def exemplars_context(self, ctx, m=10, groups=None):
+        """TopRows with one column per cluster: the m rows of ctx labelled k with the largest Eloglike_k(x) (for
+        Gauss-Wishart clusters: the smallest expected Mahalanobis distance), score = Eloglike_k(x)
+        (lc_model_exemplars).  Runs predict_context(ctx, groups) first: the context's prediction is replaced."""
+        g = None
+        if groups is not None:
+            garr = np.ascontiguousarray(groups, dtype=np.int32)
+            if garr.shape != (ctx.dims()[0],):
+                raise ValueError("groups needs one learned group index per block of the context")
+            g = garr.ctypes.data_as(C.POINTER(C.c_int))
+        return _top_rows_call(lambda *out: lib().lc_model_exemplars(self._h, ctx._h, g, int(m), *out), self.dims()[1], int(m))
+
+    def exemplars(self, X, m=10, groups=None, device=0):
+        """exemplars_context for the host rows X ((N, D) array or a list of blocks, as predict takes): group is the
+        block index, row the row of that block."""
+        with Context(device) as ctx:
+            ctx.set_data(self._blocks(X))
+            return self.exemplars_context(ctx, m, groups)
+
+    def outliers(self, X, m=10, groups=None, device=0):
+        """TopRows (one column) of the m rows of X the model finds least likely: the smallest logp of predict."""
+        with Context(device) as ctx:
+            ctx.set_data(self._blocks(X))
+            self.predict_context(ctx, groups)
+            return ctx.top_rows(m, by="logp", largest=False)
 
     def release_data(self):
         """Free the training observations and qZ; the parameters (and predict) stay."""

@@ -1112,6 +1112,40 @@ int lc_ctx_get_predictions(lc_ctx* ctx, int j, int64_t row0, int64_t n, int32_t*
   });
 }
 
+// ---- ranking -----------------------------------------------------
+int lc_ctx_top_rows(lc_ctx* ctx, int what, int ncols, int m, int largest, int by_label, int32_t* count, int32_t* group,
+                    int64_t* row, double* score) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    need(count, "count");
+    need(group, "group");
+    need(row, "row");
+    need(score, "score");
+    ctx->impl.top_rows(what, ncols, m, largest != 0, by_label != 0, count, group, row, score);
+  });
+}
+
+int lc_model_exemplars(lc_model* m, lc_ctx* ctx, const int* groups, int mtop, int32_t* count, int32_t* group, int64_t* row,
+                       double* score) {
+  return guarded([&] {
+    need(m, "model");
+    need(ctx, "ctx");
+    need(count, "count");
+    need(group, "group");
+    need(row, "row");
+    need(score, "score");
+    if (!model_alive(m)) throw std::invalid_argument("the model was freed");
+    if (ctx->impl.J() < 1) throw std::invalid_argument("the context holds no observations (lc_ctx_set_data / lc_ctx_synth)");
+    if (ctx->impl.D() != m->D) throw std::invalid_argument("Mismatched dims. of cluster params and obs.!");  // vbem, :193
+    const int J = (int)m->model.weights.size();
+    for (int b = 0; b < ctx->impl.J(); ++b) {
+      const int j = groups ? groups[b] : 0;
+      if (j < 0 || j >= J) throw std::invalid_argument("group index out of range");
+    }
+    lcp::exemplars(ctx->impl, m->model, m->sparse, groups, mtop, count, group, row, score);
+  });
+}
+
 int lc_model_release_data(lc_model* m) {
   return guarded([&] {
     need(m, "model");

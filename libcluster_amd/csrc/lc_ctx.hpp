@@ -267,6 +267,12 @@ class Context {
     pred_vb_ = pred_logp_ = false;
     pred_docs_T_ = 0;
   }
+  // ---- ranking ----------------------------------------------------------------------------------------------
+  // The m best rows of each column (lck::TopRowsLaunch for the order): what = 0 the first ncols columns of qZ, 1 / 2 the
+  // logZ / logp of the last prediction (one column; ncols is not looked at).  by_label: column c only sees the rows the
+  // last prediction labelled c.  count[C]; group, row, score [C x m], best first, -1 / -1 / NaN past count[c].
+  void top_rows(int what, int ncols, int m, bool largest, bool by_label, int32_t* count, int32_t* group, int64_t* row,
+                double* score);
   // Two-level models (lc_topic_predict.cpp): after a raw E-step left L_nk = Eloglike_k(x_n) in K columns of
   // qZ, every group of the context is one document: its qY, label_t, Fyz, Fz and sweep count into the context's
   // per-document outputs, label / logZ per row as above (lck::TopicInferLaunch; a: J x T, E: T x K host arrays).
@@ -426,6 +432,9 @@ class Context {
   DevBuf<int> plabel_, pflag_;
   DevBuf<double> plogz_, plogp_, ptab_;
   bool pred_vb_ = false, pred_logp_ = false;
+  // top_rows: the first stage's partial lists and the result [C x m scores | C x m positions]
+  DevBuf<double> topkey_, topout_;
+  DevBuf<int64_t> toppos_;
   // per-document outputs of the last topic_infer ([J x T], [J x 2], [J x 2]); pred_docs_T_ = its T (0: none)
   DevBuf<double> tqy_, tf_;
   DevBuf<int> tint_;

@@ -441,6 +441,31 @@ int64_t softmax_cached_grid(int64_t NP);
 int softmax_cached_max_k();  // widest K the sweep is built for
 hipError_t launch_softmax_cached(const CachedNormLaunch& a, hipStream_t stream);
 
+// ---- ranking (lc_kernels_rank.hip): the m best rows of each of C columns -----------------------------------
+// Entry a is better than b when its score is larger (`largest`; smaller otherwise), or the scores compare equal and its
+// position is lower: a total order, so the result does not depend on the chunking.  NaN scores and pad rows are never
+// selected; with `label`, column c only sees the rows with label[row] == c.
+constexpr int TOP_CHUNK_ROWS = 8192;  // rows per wave of the first stage: N = 10M gives a single column 1 221 waves, more than the chip has SIMDs
+constexpr int TOP_MAX_M = 64;         // one list entry per lane
+struct TopRowsLaunch {
+  const double* col = nullptr;  // [C x ld]
+  int64_t ld = 0;
+  int C = 0;
+  int64_t NP = 0;               // padded rows (multiple of 16)
+  const int* rginfo = nullptr;  // [NP / 16] or nullptr (single group; the valid rows are the first nrows)
+  int64_t nrows = 0;
+  const int* label = nullptr;   // [NP] or nullptr: no filter
+  int m = 0;                    // 1 ... TOP_MAX_M
+  int largest = 1;
+  int nchunks = 0;              // top_rows_chunks(NP)
+  double* pkey = nullptr;       // [nchunks x C x m] partial lists of the first stage (keys: the score, negated for smallest)
+  long long* ppos = nullptr;    // [nchunks x C x m]
+  double* out_score = nullptr;  // [C x m] best first; NaN / -1 in the slots past the column's candidates
+  long long* out_pos = nullptr; // [C x m] padded row
+};
+int top_rows_chunks(int64_t NP);
+hipError_t launch_top_rows(const TopRowsLaunch& a, hipStream_t stream);
+
 // synthetic mixture generator (bench): Philox4x32-10, counter = global row.
 struct SynthLaunch {
   int DP, D, K;

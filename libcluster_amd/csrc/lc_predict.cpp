@@ -126,6 +126,71 @@ void Context::get_predictions(int j, int64_t row0, int64_t n, int32_t* label, do
   LC_HIP(hipStreamSynchronize(stream_));
 }
 
+void Context::top_rows(int what, int ncols, int m, bool largest, bool by_label, int32_t* count, int32_t* group,
+                       int64_t* row, double* score) {
+  use_device();
+  if (J_ < 1) throw std::invalid_argument("the context holds no observations (lc_ctx_set_data / lc_ctx_synth)");
+  if (m < 1 || m > lck::TOP_MAX_M) throw std::invalid_argument("m must be in 1 ... 64");
+  if (what < 0 || what > 2) throw std::invalid_argument("unknown ranking source (LC_RANK_QZ, LC_RANK_LOGZ, LC_RANK_LOGP)");
+  const double* col = nullptr;
+  int C = 1;
+  if (what == 0) {
+    const int K = qz_[cur_].K;
+    if (ncols < 1 || ncols > K) throw std::invalid_argument("ncols must be in 1 ... K, the columns of the context's qZ (" + std::to_string(K) + ")");
+    if (by_label && !pred_vb_) throw std::invalid_argument("the context holds no prediction (lc_model_predict): no labels to rank by");
+    C = ncols;
+    col = qz_[cur_].buf.p;
+  } else {
+    if (by_label) throw std::invalid_argument("by_label ranks the columns of qZ, not logZ / logp");
+    if (!pred_vb_) throw std::invalid_argument("the context holds no prediction (lc_model_predict)");
+    if (what == 2 && !pred_logp_) throw std::invalid_argument("the context's prediction has no log density");
+    col = what == 1 ? plogz_.p : plogp_.p;
+  }
+  const size_t n = (size_t)C * m;
+  std::fill(count, count + C, 0);
+  std::fill(group, group + n, -1);
+  std::fill(row, row + n, (int64_t)-1);
+  std::fill(score, score + n, std::numeric_limits<double>::quiet_NaN());
+  if (NP_ == 0) return;
+  if (!col || (by_label && !plabel_.p)) throw std::logic_error("top_rows: the column is not on the device");
+  lck::TopRowsLaunch a;
+  a.col = col;
+  a.ld = NP_;
+  a.C = C;
+  a.NP = NP_;
+  a.rginfo = J_ > 1 ? rginfo_.p : nullptr;
+  a.nrows = Nj_[0];
+  a.label = by_label ? plabel_.p : nullptr;
+  a.m = m;
+  a.largest = largest ? 1 : 0;
+  a.nchunks = lck::top_rows_chunks(NP_);
+  topkey_.reserve((size_t)a.nchunks * n);
+  toppos_.reserve((size_t)a.nchunks * n);
+  topout_.reserve(2 * n);
+  static_assert(sizeof(long long) == sizeof(double) && sizeof(int64_t) == sizeof(long long), "positions travel in double slots");
+  a.pkey = topkey_.p;
+  a.ppos = reinterpret_cast<long long*>(toppos_.p);
+  a.out_score = topout_.p;
+  a.out_pos = reinterpret_cast<long long*>(topout_.p + n);
+  LC_HIP(lck::launch_top_rows(a, stream_));
+  hred_.resize(2 * n);
+  LC_HIP(hipMemcpyAsync(hred_.data(), topout_.p, 2 * n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+  for (int c = 0; c < C; ++c)
+    for (int i = 0; i < m; ++i) {
+      const size_t at = (size_t)c * m + i;
+      int64_t pos;
+      std::memcpy(&pos, hred_.data() + n + at, sizeof(pos));
+      if (pos < 0) break;  // (best first: the empty slots are the last)
+      const int j = (int)(std::upper_bound(goff_.begin(), goff_.end(), pos) - goff_.begin()) - 1;
+      if (j < 0 || j >= J_ || pos - goff_[(size_t)j] >= Nj_[(size_t)j]) throw std::logic_error("top_rows: a selected position is no observation");
+      group[at] = j;
+      row[at] = pos - goff_[(size_t)j];
+      score[at] = hred_[at];
+      count[c] = i + 1;
+    }
+}
+
 }  // namespace lcc
 
 namespace lcp {
@@ -282,6 +347,21 @@ void predict(lcc::Context& ctx, const lce::Model& model, bool sparse, const int*
     }
   ctx.estep_diag(K, ra.data(), rw2.data(), rw1.data(), zero.data(), nullptr, nullptr, /*raw=*/true);
   ctx.predict_rows(K, 0, c.data(), nullptr, nullptr, nullptr, keep_qz);
+}
+
+void exemplars(lcc::Context& ctx, const lce::Model& model, bool sparse, const int* groups, int mtop, int32_t* count,
+               int32_t* group, int64_t* row, double* score) {
+  if (mtop < 1 || mtop > lck::TOP_MAX_M) throw std::invalid_argument("m must be in 1 ... 64");  // (before the prediction runs)
+  if (ctx.J() < 1) throw std::invalid_argument("the context holds no observations (lc_ctx_set_data / lc_ctx_synth)");
+  // Without keep_qz, predict_rows_kernel only READS the raw columns (it writes label, logZ, logp): when predict() returns,
+  // columns 0 .. K - 1 of qZ still hold the raw E-step's data terms, Eloglike_k(x_n) minus the cluster's constant.
+  predict(ctx, model, sparse, groups, /*keep_qz=*/false);
+  const int K = (int)model.clusters.size();
+  ctx.top_rows(0, K, mtop, /*largest=*/true, /*by_label=*/true, count, group, row, score);
+  for (int k = 0; k < K; ++k) {
+    const double cst = model.clusters[(size_t)k].eloglike_const();
+    for (int i = 0; i < count[k]; ++i) score[(size_t)k * mtop + i] += cst;
+  }
 }
 
 }  // namespace lcp

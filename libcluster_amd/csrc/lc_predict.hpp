@@ -82,4 +82,9 @@ void weights_predictive(const lch::WeightState& w, double* Epi, double* Erest);
 // per-row outputs and, with keep_qz, the responsibilities in its qZ.  Throws std::invalid_argument for a negative
 // observation of an exponential model.
 void predict(lcc::Context& ctx, const lce::Model& model, bool sparse, const int* groups, bool keep_qz);
+// Exemplars: predict(..., keep_qz = false), then per cluster k the mtop rows labelled k with the largest
+// Eloglike_k(x_n) -- ranked on the raw columns the prediction leaves in qZ, the cluster's constant added on the host.
+// Outputs as Context::top_rows with C = K.
+void exemplars(lcc::Context& ctx, const lce::Model& model, bool sparse, const int* groups, int mtop, int32_t* count,
+               int32_t* group, int64_t* row, double* score);
 }  // namespace lcp

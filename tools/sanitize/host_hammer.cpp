@@ -327,6 +327,21 @@ void hammer_capi() {
   // the first kernel launch fails on the stand-in: a status and a message, nothing torn down twice
   CHECK(lc_ctx_fill_qz(ctx, 3, 1.0) != LC_OK);
   CHECK(std::strlen(lc_last_error()) > 0);
+  // ranking (lc_ctx_top_rows): the argument checks answer before anything is written or launched; a valid query sizes
+  // the partial lists and the result buffers, fills the outputs with the empty answer, and fails in its first launch
+  {
+    std::vector<int32_t> cnt(3, 7), grp((size_t)3 * 64, 7);
+    std::vector<int64_t> row((size_t)3 * 64, 7);
+    std::vector<double> sc((size_t)3 * 64, 7.0);
+    CHECK(lc_ctx_top_rows(ctx, LC_RANK_QZ, 3, 0, 1, 0, cnt.data(), grp.data(), row.data(), sc.data()) == LC_EINVAL);
+    CHECK(lc_ctx_top_rows(ctx, LC_RANK_QZ, 4, 5, 1, 0, cnt.data(), grp.data(), row.data(), sc.data()) == LC_EINVAL);
+    CHECK(lc_ctx_top_rows(ctx, LC_RANK_LOGP, 1, 5, 0, 0, cnt.data(), grp.data(), row.data(), sc.data()) == LC_EINVAL);
+    CHECK(lc_ctx_top_rows(ctx, LC_RANK_QZ, 3, 5, 1, 1, cnt.data(), grp.data(), row.data(), sc.data()) == LC_EINVAL);
+    CHECK(cnt[0] == 7 && grp[0] == 7 && row[0] == 7 && sc[0] == 7.0);
+    CHECK(lc_ctx_top_rows(ctx, LC_RANK_QZ, 3, 64, 0, 0, cnt.data(), grp.data(), row.data(), sc.data()) == LC_EHIP);
+    CHECK(std::strstr(lc_last_error(), "HIP") != nullptr);
+    CHECK(cnt[2] == 0 && grp[(size_t)3 * 64 - 1] == -1 && row[(size_t)3 * 64 - 1] == -1 && std::isnan(sc[(size_t)3 * 64 - 1]));
+  }
   lc_ctx_destroy(ctx);
 
   // sharded learners: every shard thread fails in its first launch -- the abort / release / rethrow path of
@@ -348,7 +363,7 @@ void hammer_capi() {
   unsetenv("LIBCLUSTER_GPUS_SAME_DEVICE");
   unsetenv("LIBCLUSTER_FORCE_SHARDED");
   lc_trim_cache();
-  std::printf("capi: concurrent M-steps, upload packer round trip, launch failure -> status, sharded failure path (1, 3, 8 shards) ok\n");
+  std::printf("capi: concurrent M-steps, upload packer round trip, launch failure -> status, ranking arguments and buffers, sharded failure path (1, 3, 8 shards) ok\n");
 }
 
 }  // namespace
