@@ -306,6 +306,28 @@ int lc_model_fenergy(lc_model* m, double* Fw /*[J]*/, double* Fc /*[K]*/);
 int lc_model_predict(lc_model* m, lc_ctx* ctx, const int* groups /* [J of ctx] or NULL */, int keep_qz);
 /* rows [row0, row0+n) of block j of the last prediction on ctx (like lc_ctx_get_qz_rows); any output may be NULL */
 int lc_ctx_get_predictions(lc_ctx* ctx, int j, int64_t row0, int64_t n, int32_t* label, double* logZ, double* logp);
+/* ---- conditional prediction (nothing in the reference corresponds): some columns of a new row are known,
+ * the others are wanted.  Gauss-Wishart models only.  ctx holds the KNOWN columns only: its width is ngiven and its column
+ * i is model column given[i]; target lists the wanted model columns (NULL: every column that is not given, ascending;
+ * ntarget is not looked at then).  Block b of ctx is mixed with the weights of learned group groups[b] (NULL: group 0).
+ * With a = given, b = target, cluster k's posterior (nu, beta, m, iW) and nu' = nu + 1 - D (D the model's full width):
+ *   P_k,a(x_a)  Student-t, nu' degrees of freedom, location m_a, scale (1 + beta) / (beta nu') iW_aa: the marginal of the
+ *               posterior predictive lc_model_predict mixes
+ *   M_k(x_a)  = m_b + iW_ba iW_aa^-1 (x_a - m_a): the cluster's linear expert (the conditional mean of that Student-t)
+ *   logp      = log(sum_k E[pi_jk] P_k,a(x_a) + E[pi_rest] P_0,a(x_a)), the prior component as in lc_model_predict
+ *   mean      = sum_k r_k M_k(x_a), r_k = E[pi_jk] P_k,a(x_a) / exp(logp): E[x_b | x_a, training data]
+ * All K clusters take part, also for sparse models (as in logp of lc_model_predict).  Works for the same models as
+ * lc_model_predict.  Replaces any prediction ctx held (lc_ctx_get_predictions reports none afterwards); a call that
+ * fails leaves none.  The context's qZ holds intermediate values afterwards.
+ * LC_EINVAL: clusters that are not Gauss-Wishart, ngiven < 1, no target column, an index outside [0, D), an index
+ * twice in a list, a column in both lists, a context whose width is not ngiven, a group index outside [0, J), a freed
+ * model. */
+int lc_model_predict_conditional(lc_model* m, lc_ctx* ctx, const int* groups /* [J of ctx] or NULL */, const int* given,
+                                 int ngiven, const int* target /* or NULL */, int ntarget);
+/* rows [row0, row0+n) of block j of the last conditional prediction on ctx: mean is n x ntarget with row_stride doubles
+ * between rows (>= ntarget), logp n values; either may be NULL.  LC_EINVAL: no conditional prediction on ctx, a row
+ * range out of bounds. */
+int lc_ctx_get_conditional(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* mean, int64_t row_stride, double* logp);
 /* ---- ranking on the device (nothing in the reference corresponds): the m best rows of each of C device-resident
  * columns, 1 <= m <= 64, without bringing the columns to the host.  Entry a is better than entry b when its score is larger
  * (largest != 0; smaller otherwise), or the scores compare equal (+0.0 and -0.0 do) and a comes first in the context (lower
@@ -414,6 +436,16 @@ int lc_weights_update(int wkind, double wprior, const double* Nk, int K, double*
  * E-step whitener A (D*D) and Eloglike constant.  Any output may be NULL. */
 int lc_gw_mstep(double clustwidth, int D, double Ns, const double* xs, const double* xxs, double* nu, double* beta,
                 double* m, double* iW, double* logdW, double* fenergy, double* A, double* eloglike_const);
+/* The per-cluster tables of lc_model_predict_conditional from one Gauss-Wishart posterior (nu, beta, m [D], iW [D x D])
+ * and a split into given / target columns (checked as there; target NULL: the columns not given, ntarget not looked at):
+ *   A [ngiven x ngiven] row-major, lower-triangular: ||A (x_a - m_a)||^2 = nu (x_a - m_a)^T iW_aa^-1 (x_a - m_a)
+ *   ma [ngiven], mb [ntarget]; B [ntarget x ngiven] row-major = iW_ba iW_aa^-1 (Cholesky factor of iW_aa and two
+ *   triangular solves)
+ *   log P_a(x_a) = G - e log1p(s ||A (x_a - m_a)||^2), s = beta / ((1 + beta) nu), e = (nu + 1 - D + ngiven) / 2
+ * Any output may be NULL.  LC_EINVAL: the index cases above, nu <= D - 1, beta <= 0, iW_aa not positive definite. */
+int lc_gw_conditional(int D, double nu, double beta, const double* m, const double* iW, const int* given, int ngiven,
+                      const int* target, int ntarget, double* A, double* ma, double* B, double* mb, double* G, double* s,
+                      double* e);
 /* NormGamma: addobs sums -> update() (distributions.cpp:441-464), fenergy (:508-517), Eloglike constant (:486-488).
  * xs, xxs: D values each (sum q x, sum q x.^2). */
 int lc_ng_mstep(double clustwidth, int D, double Ns, const double* xs, const double* xxs, double* nu, double* beta,

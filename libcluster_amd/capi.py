@@ -38,6 +38,13 @@ class Prediction(NamedTuple):
     qZ: np.ndarray | None
 
 
+class Conditional(NamedTuple):
+    """Per-row outputs of Model.predict_conditional (lc_model_predict_conditional): mean (N, ntarget) =
+    E[x_target | x_given, training data], logp (N,) = log p(x_given | training data)."""
+    mean: np.ndarray
+    logp: np.ndarray
+
+
 class TopRows(NamedTuple):
     """The m best rows of each of C columns (lc_ctx_top_rows, lc_model_exemplars), best first: count (C,) int32, group
     (C, m) int32 (block of the context / of X), row (C, m) int64 (row of that block), score (C, m); the entries past
@@ -257,6 +264,11 @@ def lib() -> C.CDLL:
     L.lc_ctx_top_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p, c_int64_p,
                                   c_double_p]
     L.lc_model_exemplars.argtypes = [C.c_void_p, C.c_void_p, c_int_p, C.c_int, c_int32_p, c_int32_p, c_int64_p, c_double_p]
+    L.lc_model_predict_conditional.argtypes = [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, c_int_p, C.c_int]
+    L.lc_ctx_get_conditional.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, C.c_int64, c_double_p]
+    L.lc_gw_conditional.argtypes = [C.c_int, C.c_double, C.c_double, c_double_p, c_double_p, c_int_p, C.c_int, c_int_p,
+                                    C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                    c_double_p]
     _lib = L
     return L
 
@@ -583,6 +595,13 @@ class Context:
                                                dptr(logZ), dptr(lp)))
         return label, logZ, lp
 
+    def get_conditional(self, j, row0, n, ntarget):
+        """Rows [row0, row0+n) of block j of the last Model.predict_conditional_context on this context ->
+        Conditional(mean (n, ntarget), logp (n,)); ntarget is the number of target columns of that call."""
+        mean, logp = np.zeros((n, ntarget)), np.zeros(n)
+        check(lib().lc_ctx_get_conditional(self._h, j, row0, n, dptr(mean), ntarget, dptr(logp)))
+        return Conditional(mean, logp)
+
     def top_rows(self, m, by="qz", largest=True, ncols=None, by_label=False):
         """TopRows of the m best rows (1 ... 64) of each column, ranked on the device (lc_ctx_top_rows): by="qz" the first
         ncols columns of qZ (None: all), by="logz" / "logp" the per-row outputs of the last prediction on this context
@@ -751,6 +770,57 @@ class Model:
                    for j, (n, q) in enumerate(zip(rows, qs))]
         return out if blocks else out[0]
 
+    # -- conditional prediction ------------------------------------------------------------------------
+    def _targets(self, given, target):
+        if target is not None:
+            return [int(t) for t in target]
+        gs = set(int(g) for g in given)
+        return [c for c in range(self.dims()[2]) if c not in gs]
+
+    def predict_conditional_context(self, ctx, given, target=None, groups=None):
+        """E[x_target | x_given] and log p(x_given) of the rows resident in ctx, whose column i is model column
+        given[i] (lc_model_predict_conditional).  target None: every model column that is not given, ascending.
+        Nothing is downloaded: read the rows with ctx.get_conditional.  Returns the number of target columns."""
+        g = None
+        if groups is not None:
+            garr = np.ascontiguousarray(groups, dtype=np.int32)
+            if garr.shape != (ctx.dims()[0],):
+                raise ValueError("groups needs one learned group index per block of the context")
+            g = garr.ctypes.data_as(c_int_p)
+        gv = np.ascontiguousarray(given, dtype=np.int32).reshape(-1)
+        tv = None if target is None else np.ascontiguousarray(target, dtype=np.int32).reshape(-1)
+        check(lib().lc_model_predict_conditional(self._h, ctx._h, g, gv.ctypes.data_as(c_int_p), gv.size,
+                                                 None if tv is None else tv.ctypes.data_as(c_int_p),
+                                                 0 if tv is None else tv.size))
+        return len(self._targets(gv, tv))
+
+    def predict_conditional(self, Xa, given, target=None, groups=None, device=0):
+        """Conditional(mean, logp) for the host rows Xa ((N, len(given)) array: the known columns, in the order of
+        given), or a list of them for a list of blocks (block b mixed with learned group groups[b], default 0)."""
+        blocks = isinstance(Xa, (list, tuple))
+        Xs = list(Xa) if blocks else [Xa]
+        Da = len(given)
+        Xs = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, max(Da, 1))) for x in Xs]
+        with Context(device) as ctx:
+            ctx.set_data(Xs)
+            nt = self.predict_conditional_context(ctx, given, target, groups)
+            out = [ctx.get_conditional(j, 0, x.shape[0], nt) for j, x in enumerate(Xs)]
+        return out if blocks else out[0]
+
+    def impute(self, X, missing, groups=None, device=0):
+        """A copy of the full-width rows X ((N, D) array or a list of blocks) with the columns `missing` replaced by
+        their conditional mean given the other columns (predict_conditional).  What X holds in the missing columns is
+        not looked at (NaN is fine)."""
+        blocks = isinstance(X, (list, tuple))
+        D = self.dims()[2]
+        Xs = [np.array(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (X if blocks else [X])]
+        miss = [int(c) for c in missing]
+        given = [c for c in range(D) if c not in set(miss)]
+        res = self.predict_conditional([x[:, given] for x in Xs], given, miss, groups, device)
+        for x, r in zip(Xs, res):
+            x[:, miss] = r.mean
+        return Xs if blocks else Xs[0]
+
     # -- ranking (DESIGN 4.13) -------------------------------------------------------------------------------------
     def _blocks(self, X):
         blocks = isinstance(X, (list, tuple))
@@ -838,6 +908,24 @@ def gw_mstep(clustwidth, Ns, xs, xxs):
                             C.byref(logdW), C.byref(fe), dptr(A), C.byref(cst)))
     return {"nu": nu.value, "beta": beta.value, "m": m, "iW": iW, "logdW": logdW.value, "fenergy": fe.value,
             "A": A, "eloglike_const": cst.value}
+
+
+def gw_conditional(nu, beta, m, iW, given, target=None):
+    """The per-cluster tables of the conditional prediction (lc_gw_conditional) from one Gauss-Wishart posterior:
+    A (whitener of the given columns), ma, B (= iW_ba iW_aa^-1), mb, G, s, e and the target list."""
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    iW = np.ascontiguousarray(iW, dtype=np.float64)
+    D = m.size
+    gv = np.ascontiguousarray(given, dtype=np.int32).reshape(-1)
+    tv = None if target is None else np.ascontiguousarray(target, dtype=np.int32).reshape(-1)
+    tg = [int(t) for t in tv] if tv is not None else [c for c in range(D) if c not in set(int(g) for g in gv)]
+    Da, Db = gv.size, len(tg)
+    A, ma, B, mb = np.zeros((Da, Da)), np.zeros(Da), np.zeros((Db, Da)), np.zeros(Db)
+    G, s, e = (C.c_double() for _ in range(3))
+    check(lib().lc_gw_conditional(D, nu, beta, dptr(m), dptr(iW), gv.ctypes.data_as(c_int_p), Da,
+                                  None if tv is None else tv.ctypes.data_as(c_int_p), 0 if tv is None else tv.size,
+                                  dptr(A), dptr(ma), dptr(B), dptr(mb), C.byref(G), C.byref(s), C.byref(e)))
+    return {"A": A, "ma": ma, "B": B, "mb": mb, "G": G.value, "s": s.value, "e": e.value, "target": tg}
 
 
 def ng_mstep(clustwidth, Ns, xs, xxs):

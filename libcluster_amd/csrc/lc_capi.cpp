@@ -1112,6 +1112,25 @@ int lc_ctx_get_predictions(lc_ctx* ctx, int j, int64_t row0, int64_t n, int32_t*
   });
 }
 
+// ---- conditional prediction -----------------------------------------
+int lc_model_predict_conditional(lc_model* m, lc_ctx* ctx, const int* groups, const int* given, int ngiven,
+                                 const int* target, int ntarget) {
+  return guarded([&] {
+    need(m, "model");
+    need(ctx, "ctx");
+    ctx->impl.predict_clear();  // (a failure leaves no prediction behind)
+    if (!model_alive(m)) throw std::invalid_argument("the model was freed");
+    lcp::predict_conditional(ctx->impl, m->model, groups, given, ngiven, target, ntarget);
+  });
+}
+
+int lc_ctx_get_conditional(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* mean, int64_t row_stride, double* logp) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.get_conditional(j, row0, n, mean, row_stride, logp);
+  });
+}
+
 // ---- ranking -----------------------------------------------------
 int lc_ctx_top_rows(lc_ctx* ctx, int what, int ncols, int m, int largest, int by_label, int32_t* count, int32_t* group,
                     int64_t* row, double* score) {
@@ -1210,6 +1229,18 @@ int lc_gw_mstep(double clustwidth, int D, double Ns, const double* xs, const dou
       std::copy(a.begin(), a.end(), A);
     }
     if (eloglike_const) *eloglike_const = g.eloglike_const();
+  });
+}
+
+int lc_gw_conditional(int D, double nu, double beta, const double* m, const double* iW, const int* given, int ngiven,
+                      const int* target, int ntarget, double* A, double* ma, double* B, double* mb, double* G, double* s,
+                      double* e) {
+  return guarded([&] {
+    need(m, "m");
+    need(iW, "iW");
+    if (D < 1) throw std::invalid_argument("D must be >= 1!");
+    const std::vector<int> tg = lcp::conditional_split(D, given, ngiven, target, ntarget);
+    lcp::gw_conditional(D, nu, beta, m, iW, std::vector<int>(given, given + ngiven), tg, A, ma, B, mb, G, s, e);
   });
 }
 

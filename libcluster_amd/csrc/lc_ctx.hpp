@@ -266,7 +266,17 @@ class Context {
   void predict_clear() {
     pred_vb_ = pred_logp_ = false;
     pred_docs_T_ = 0;
+    pred_cond_ = 0;
   }
+  // Conditional prediction: after a raw E-step with zero constants over the context's (given) columns left
+  // Kp columns in qZ, per row E[x_target | x_given] (Db columns) and log p(x_given) into the context's conditional outputs
+  // (lck::PredictCondLaunch for the tables: tt J x Kp, ps, pe Kp, ma Kp x D, B Kp x Db x D, mb Kp x Db, host arrays).
+  // qZ is left holding the Kp per-cluster log terms.
+  void predict_cond(int Kp, int Db, const double* tt, const double* ps, const double* pe, const double* ma,
+                    const double* B, const double* mb);
+  // rows [row0, row0+n) of group j of the last conditional prediction (either output may be null)
+  void get_conditional(int j, int64_t row0, int64_t n, double* mean, int64_t row_stride, double* logp) const;
+  int conditional_width() const { return pred_cond_; }  // target columns of the conditional prediction held (0: none)
   // ---- ranking ----------------------------------------------------------------------------------------------
   // The m best rows of each column (lck::TopRowsLaunch for the order): what = 0 the first ncols columns of qZ, 1 / 2 the
   // logZ / logp of the last prediction (one column; ncols is not looked at).  by_label: column c only sees the rows the
@@ -432,6 +442,9 @@ class Context {
   DevBuf<int> plabel_, pflag_;
   DevBuf<double> plogz_, plogp_, ptab_;
   bool pred_vb_ = false, pred_logp_ = false;
+  // ... of the last conditional prediction: mean [NP x pred_cond_] and log p(x_given) [NP]; pred_cond_ = 0: none
+  DevBuf<double> pcmean_, pclogp_;
+  int pred_cond_ = 0;
   // top_rows: the first stage's partial lists and the result [C x m scores | C x m positions]
   DevBuf<double> topkey_, topout_;
   DevBuf<int64_t> toppos_;

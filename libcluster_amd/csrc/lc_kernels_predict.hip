@@ -328,6 +328,121 @@ __global__ __launch_bounds__(PR_THREADS) void predict_diag_kernel(PredictDiagLau
   a.logp[row] = m + log(s);
 }
 
+// Conditional mean.  Lane = lo2 + 4 blk + 16 hi of v_mfma_f64_4x4x4_4b (lc_device.hpp): MFMA block blk of
+// row group g multiplies the rows 16 g + 4 blk + {0..3} of the wave (A: row lo2, column hi of the k-step) with a 4 x 4 piece
+// of the table (B: given column hi, target lo2 -- the same in all four blocks) into D (row hi, target lo2).  In the first
+// part lane l scores row l of the wave, which is row 4 blk + lo2 of row group hi: the r_k of row group g sit in the lanes
+// with hi = g, and one __shfl per row group hands them to the lanes that build the A operands.
+__global__ __launch_bounds__(PC_THREADS) void predict_cond_kernel(PredictCondLaunch a) {
+  __shared__ double etab[64];
+  __shared__ LogEntry ltab[128];
+  fill_exp_table(etab, threadIdx.x, PC_THREADS);
+  fill_log_table(ltab, threadIdx.x, PC_THREADS);
+  __syncthreads();  // (the only barrier: from here on the waves do not meet)
+  constexpr int NG = PC_WAVE_ROWS / RG, NS = PC_CHUNK / 4, NQ = PC_PANEL / 4;
+  static_assert(RG == 16 && NG == 4, "one MFMA block per quad of rows, one shuffle source per row group");
+  const int lane = threadIdx.x & 63, lo2 = lane & 3, blk = (lane >> 2) & 3, hi = lane >> 4;
+  const int64_t NP = a.nrg * RG;
+  const int64_t wrow0 = ((int64_t)blockIdx.x * (PC_THREADS / 64) + (threadIdx.x >> 6)) * PC_WAVE_ROWS;
+  if (wrow0 >= NP) return;
+  // NP is a multiple of 16, not of 64: rows past the end are clamped for reading and never written
+  const int64_t row = wrow0 + lane, rrow = row < NP ? row : NP - 1;
+  int j = 0;
+  const bool valid = row_valid(rrow, a.rginfo, a.nrows, j) && row < NP;
+  if (!valid) j = 0;  // (a pad row is scored like any other, so that the wave stays whole, and nothing of it is written)
+  constexpr double NINF = -std::numeric_limits<double>::infinity();
+  double* __restrict__ col = a.col + rrow;
+  double logp;
+  {  // log p(x_a) as predict_rows_kernel forms logp; t_k replaces the raw column
+    const double* __restrict__ tt = a.ttab + (size_t)j * a.Kp;
+    double m = NINF, s = 0.0;
+    for (int k0 = 0; k0 < a.Kp; k0 += PR_COLS) {
+      double r[PR_COLS];
+#pragma unroll
+      for (int i = 0; i < PR_COLS; ++i) r[i] = k0 + i < a.Kp ? col[(size_t)(k0 + i) * a.ldq] : 0.0;
+#pragma unroll
+      for (int i = 0; i < PR_COLS; ++i) {
+        const int k = k0 + i;
+        if (k < a.Kp) {
+          const double t = tt[k] - a.pexp[k] * log1p_nonneg(a.pscale[k] * (-2.0 * r[i]), ltab);
+          lse_push(t, m, s, etab);
+          if (valid) col[(size_t)k * a.ldq] = t;
+        }
+      }
+    }
+    logp = m + log(s);
+    if (valid) a.logp[row] = logp;
+  }
+  // rows of the A operands (row lo2 of block blk) and of the results (row hi of block blk), per row group
+  int64_t xrow[NG];
+  bool ovalid[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int64_t ra = wrow0 + g * RG + 4 * blk + lo2, ro = wrow0 + g * RG + 4 * blk + hi;
+    xrow[g] = ra < NP ? ra : NP - 1;
+    int jo;
+    ovalid[g] = ro < NP && row_valid(ro < NP ? ro : NP - 1, a.rginfo, a.nrows, jo);
+  }
+  for (int t0 = 0; t0 < a.Db; t0 += PC_PANEL) {  // the accumulators of one panel of targets are resident
+    const int nq = (a.Dbp - t0) / 4 < NQ ? (a.Dbp - t0) / 4 : NQ;
+    double acc[NG][NQ];
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) acc[g][q] = 0.0;
+    for (int c0 = 0; c0 < a.Dae; c0 += PC_CHUNK) {  // the x of one chunk of given columns is resident
+      const int ns = (a.Dae - c0) / 4 < NS ? (a.Dae - c0) / 4 : NS;
+      double x[NG][NS];
+#pragma unroll
+      for (int g = 0; g < NG; ++g)
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          const int c = c0 + 4 * s + hi;
+          x[g][s] = c < a.Da ? a.X[(size_t)xrow[g] * a.DP + c] : c == a.Da ? 1.0 : 0.0;  // (the ones column carries m_b)
+        }
+      for (int k = 0; k < a.Kp; ++k) {
+        // the tables stream from the cache cluster by cluster: Kp (Da + 1) Db doubles do not fit the LDS
+        const double t = valid ? col[(size_t)k * a.ldq] : NINF;
+        const double r = valid ? exp_nonpos(t - logp, etab) : 0.0;
+        double rg[NG];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) rg[g] = __shfl(r, g * RG + 4 * blk + lo2);
+        const double* __restrict__ mk = a.mext + (size_t)k * a.Dae + c0 + hi;
+        const double* __restrict__ Tk = a.T + ((size_t)k * a.Dae + c0 + hi) * a.Dbp + t0 + lo2;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          if (s < ns) {
+            // the four scaled, centred operands of a k-step first, then its MFMAs in one run (a VALU
+            // instruction between MFMAs is paid per switch)
+            const double mv = mk[4 * s];
+            double av[NG], bv[NQ];
+#pragma unroll
+            for (int g = 0; g < NG; ++g) av[g] = rg[g] * (x[g][s] - mv);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) bv[q] = q < nq ? Tk[(size_t)(4 * s) * a.Dbp + 4 * q] : 0.0;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+              if (q < nq) {
+#pragma unroll
+                for (int g = 0; g < NG; ++g) acc[g][q] = mfma4(av[g], bv[q], acc[g][q]);
+              }
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const int64_t ro = wrow0 + g * RG + 4 * blk + hi;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const int tcol = t0 + 4 * q + lo2;
+        if (ovalid[g] && tcol < a.Db) a.mean[(size_t)ro * a.Db + tcol] = acc[g][q];
+      }
+    }
+  }
+}
+
 template <int MODE>
 hipError_t launch_diag_mode(const PredictDiagLaunch& a, dim3 grid, hipStream_t stream) {
   switch (a.DP) {
@@ -355,6 +470,16 @@ hipError_t launch_predict_diag(const PredictDiagLaunch& a, hipStream_t stream) {
   if (rows == 0 || a.DP % PRED_RENORM != 0) return rows == 0 ? hipSuccess : hipErrorInvalidValue;
   const dim3 grid((unsigned)((rows + PR_THREADS - 1) / PR_THREADS));
   return a.mode == 0 ? launch_diag_mode<0>(a, grid, stream) : launch_diag_mode<1>(a, grid, stream);
+}
+
+hipError_t launch_predict_cond(const PredictCondLaunch& a, hipStream_t stream) {
+  const int64_t rows = a.nrg * RG;
+  if (rows == 0) return hipSuccess;
+  if (a.Kp < 1 || a.Da < 1 || a.Db < 1 || a.DP < a.Da || a.Dae < a.Da + 1 || a.Dae % 4 != 0 || a.Dbp < a.Db || a.Dbp % 4 != 0)
+    return hipErrorInvalidValue;
+  const int64_t per = (int64_t)(PC_THREADS / 64) * PC_WAVE_ROWS;
+  hipLaunchKernelGGL(predict_cond_kernel, dim3((unsigned)((rows + per - 1) / per)), dim3(PC_THREADS), 0, stream, a);
+  return hipGetLastError();
 }
 
 }  // namespace lck

@@ -126,6 +126,79 @@ void Context::get_predictions(int j, int64_t row0, int64_t n, int32_t* label, do
   LC_HIP(hipStreamSynchronize(stream_));
 }
 
+void Context::predict_cond(int Kp, int Db, const double* tt, const double* ps, const double* pe, const double* ma,
+                           const double* B, const double* mb) {
+  use_device();
+  if (Kp < 1 || Db < 1) throw std::invalid_argument("K and the number of target columns must be >= 1");
+  pred_cond_ = 0;
+  if (NP_ == 0) {
+    pred_cond_ = Db;
+    return;
+  }
+  if (qz_[cur_].cap < Kp || !qz_[cur_].buf.p) throw std::logic_error("predict_cond: no raw E-step columns");
+  const int Da = D_, Dae = (Da + 1 + 3) / 4 * 4, Dbp = (Db + 3) / 4 * 4;
+  pcmean_.reserve((size_t)NP_ * Db);
+  pclogp_.reserve((size_t)NP_);
+  // tables: [tt J x Kp | ps Kp | pe Kp | mext Kp x Dae | T Kp x Dae x Dbp], the pads zero
+  const size_t nt = (size_t)J_ * Kp, nm = (size_t)Kp * Dae, nT = nm * Dbp;
+  hpack_.assign(nt + 2 * (size_t)Kp + nm + nT, 0.0);
+  double* h = hpack_.data();
+  std::copy(tt, tt + nt, h);
+  std::copy(ps, ps + Kp, h + nt);
+  std::copy(pe, pe + Kp, h + nt + Kp);
+  double* hm = h + nt + 2 * (size_t)Kp;
+  double* hT = hm + nm;
+  for (int k = 0; k < Kp; ++k) {
+    std::copy(ma + (size_t)k * Da, ma + (size_t)(k + 1) * Da, hm + (size_t)k * Dae);
+    double* Tk = hT + (size_t)k * Dae * Dbp;
+    for (int t = 0; t < Db; ++t) {
+      for (int c = 0; c < Da; ++c) Tk[(size_t)c * Dbp + t] = B[((size_t)k * Db + t) * Da + c];
+      Tk[(size_t)Da * Dbp + t] = mb[(size_t)k * Db + t];  // the row of the ones column
+    }
+  }
+  ptab_.reserve(hpack_.size());
+  LC_HIP(hipMemcpyAsync(ptab_.p, hpack_.data(), hpack_.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+  lck::PredictCondLaunch a;
+  a.X = X_.p;
+  a.DP = DP_;
+  a.Da = Da;
+  a.Dae = Dae;
+  a.Db = Db;
+  a.Dbp = Dbp;
+  a.Kp = Kp;
+  a.col = qz_[cur_].buf.p;
+  a.ldq = NP_;
+  a.nrg = NP_ / lck::RG;
+  a.rginfo = J_ > 1 ? rginfo_.p : nullptr;
+  a.nrows = Nj_[0];
+  a.ttab = ptab_.p;
+  a.pscale = ptab_.p + nt;
+  a.pexp = ptab_.p + nt + Kp;
+  a.mext = ptab_.p + nt + 2 * (size_t)Kp;
+  a.T = a.mext + nm;
+  a.mean = pcmean_.p;
+  a.logp = pclogp_.p;
+  LC_HIP(lck::launch_predict_cond(a, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ and ptab_ are free again)
+  qz_[cur_].K = Kp;
+  qz_[cur_].hash_ok = false;
+  pred_cond_ = Db;
+}
+
+void Context::get_conditional(int j, int64_t row0, int64_t n, double* mean, int64_t row_stride, double* logp) const {
+  use_device();
+  if (pred_cond_ < 1) throw std::invalid_argument("the context holds no conditional prediction (lc_model_predict_conditional)");
+  if (j < 0 || j >= J_ || row0 < 0 || n < 0 || row0 + n > Nj_[j]) throw std::invalid_argument("row range out of bounds");
+  if (mean && row_stride < pred_cond_) throw std::invalid_argument("row_stride is smaller than the number of target columns");
+  if (n == 0) return;
+  const size_t at = (size_t)(goff_[j] + row0), w = (size_t)pred_cond_ * sizeof(double);
+  if (mean)
+    LC_HIP(hipMemcpy2DAsync(mean, (size_t)row_stride * sizeof(double), pcmean_.p + at * pred_cond_, w, w, (size_t)n,
+                            hipMemcpyDeviceToHost, stream_));
+  if (logp) LC_HIP(hipMemcpyAsync(logp, pclogp_.p + at, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+}
+
 void Context::top_rows(int what, int ncols, int m, bool largest, bool by_label, int32_t* count, int32_t* group,
                        int64_t* row, double* score) {
   use_device();
@@ -347,6 +420,125 @@ void predict(lcc::Context& ctx, const lce::Model& model, bool sparse, const int*
     }
   ctx.estep_diag(K, ra.data(), rw2.data(), rw1.data(), zero.data(), nullptr, nullptr, /*raw=*/true);
   ctx.predict_rows(K, 0, c.data(), nullptr, nullptr, nullptr, keep_qz);
+}
+
+std::vector<int> conditional_split(int D, const int* given, int ngiven, const int* target, int ntarget) {
+  if (ngiven < 1 || !given) throw std::invalid_argument("given needs at least one column");
+  std::vector<char> seen((size_t)D, 0);
+  for (int i = 0; i < ngiven; ++i) {
+    const int c = given[i];
+    if (c < 0 || c >= D) throw std::invalid_argument("given column " + std::to_string(c) + " is outside [0, D = " + std::to_string(D) + ")");
+    if (seen[(size_t)c]) throw std::invalid_argument("given column " + std::to_string(c) + " appears twice");
+    seen[(size_t)c] = 1;
+  }
+  std::vector<int> tg;
+  if (!target) {
+    for (int c = 0; c < D; ++c)
+      if (!seen[(size_t)c]) tg.push_back(c);
+    if (tg.empty()) throw std::invalid_argument("target needs at least one column: every column of the model is given");
+    return tg;
+  }
+  if (ntarget < 1) throw std::invalid_argument("target needs at least one column");
+  for (int i = 0; i < ntarget; ++i) {
+    const int c = target[i];
+    if (c < 0 || c >= D) throw std::invalid_argument("target column " + std::to_string(c) + " is outside [0, D = " + std::to_string(D) + ")");
+    if (seen[(size_t)c] == 1) throw std::invalid_argument("column " + std::to_string(c) + " is both given and target");
+    if (seen[(size_t)c]) throw std::invalid_argument("target column " + std::to_string(c) + " appears twice");
+    seen[(size_t)c] = 2;
+    tg.push_back(c);
+  }
+  return tg;
+}
+
+void gw_conditional(int D, double nu, double beta, const double* m, const double* iW, const std::vector<int>& given,
+                    const std::vector<int>& target, double* A, double* ma, double* B, double* mb, double* G, double* s,
+                    double* e) {
+  const int Da = (int)given.size(), Db = (int)target.size();
+  const double nup = nu + 1 - D;  // Student-t degrees of freedom: of the FULL model's width (the marginal keeps them)
+  if (!(nup > 0.0) || !(beta > 0.0)) throw std::invalid_argument("nu must exceed D - 1 and beta must be positive");
+  std::vector<double> L((size_t)Da * Da);
+  for (int i = 0; i < Da; ++i)
+    for (int c = 0; c < Da; ++c) L[(size_t)i * Da + c] = iW[(size_t)given[(size_t)i] * D + given[(size_t)c]];
+  if (!lch::cholesky(L, Da)) throw std::invalid_argument("Matrix A is not positive definite");  // (iW_aa = L L^T)
+  double logdet = 0.0;
+  for (int i = 0; i < Da; ++i) logdet += std::log(L[(size_t)i * Da + i]);
+  logdet *= 2.0;
+  if (A) {  // GaussWishState::whitener() of the sub-block
+    const std::vector<double> Li = lch::tril_inverse(L, Da);
+    const double sq = std::sqrt(nu);
+    for (size_t i = 0; i < Li.size(); ++i) A[i] = sq * Li[i];
+  }
+  if (ma)
+    for (int i = 0; i < Da; ++i) ma[i] = m[given[(size_t)i]];
+  if (mb)
+    for (int t = 0; t < Db; ++t) mb[t] = m[target[(size_t)t]];
+  if (B) {  // row t of B solves iW_aa b = iW_a,t: L y = iW_a,t, then L^T b = y
+    std::vector<double> y((size_t)Da);
+    for (int t = 0; t < Db; ++t) {
+      for (int i = 0; i < Da; ++i) {
+        double v = iW[(size_t)target[(size_t)t] * D + given[(size_t)i]];
+        for (int c = 0; c < i; ++c) v -= L[(size_t)i * Da + c] * y[(size_t)c];
+        y[(size_t)i] = v / L[(size_t)i * Da + i];
+      }
+      double* b = B + (size_t)t * Da;
+      for (int i = Da - 1; i >= 0; --i) {
+        double v = y[(size_t)i];
+        for (int c = i + 1; c < Da; ++c) v -= L[(size_t)c * Da + i] * b[c];
+        b[i] = v / L[(size_t)i * Da + i];
+      }
+    }
+  }
+  if (G)
+    *G = lch::lgam((nup + Da) / 2) - lch::lgam(nup / 2) - 0.5 * Da * std::log(nup * lch::PI) +
+         0.5 * (Da * std::log(nup * beta / (1 + beta)) - logdet);
+  if (s) *s = beta / ((1 + beta) * nu);
+  if (e) *e = (nup + Da) / 2;
+}
+
+void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* groups, const int* given, int ngiven,
+                         const int* target, int ntarget) {
+  ctx.predict_clear();  // (whatever an earlier prediction left must not outlive a failure of this one)
+  const int K = (int)model.clusters.size(), J = (int)model.weights.size(), Jc = ctx.J();
+  if (K < 1) throw std::invalid_argument("the model has no clusters");
+  if (model.ckind != lch::C_GAUSSWISH)
+    throw std::invalid_argument("conditional prediction needs Gauss-Wishart clusters: the columns of NormGamma / ExpGamma "
+                                "clusters are independent within a cluster (not supported)");
+  const int D = model.clusters[0].gw.D;
+  const std::vector<int> gv(given, given + (ngiven > 0 && given ? ngiven : 0));
+  const std::vector<int> tg = conditional_split(D, given, ngiven, target, ntarget);
+  const int Da = ngiven, Db = (int)tg.size();
+  if (ctx.D() != Da)
+    throw std::invalid_argument("the context has " + std::to_string(ctx.D()) + " columns, given names " + std::to_string(Da));
+  for (int b = 0; b < Jc; ++b) {
+    const int j = groups ? groups[b] : 0;
+    if (j < 0 || j >= J) throw std::invalid_argument("group index out of range");
+  }
+  std::vector<double> Epi((size_t)J * K), Erest((size_t)J);
+  bool rest = false;
+  for (int j = 0; j < J; ++j) {
+    if ((int)model.weights[(size_t)j].alpha1.size() != K) throw std::invalid_argument("weights and clusters disagree");
+    weights_predictive(model.weights[(size_t)j], Epi.data() + (size_t)j * K, &Erest[(size_t)j]);
+    rest = rest || Erest[(size_t)j] > 0.0;
+  }
+  const int Kp = K + (rest ? 1 : 0);
+  const lch::ClusterAny prior(model.ckind, model.clusters[0].prior(), D);  // clearobs state: a cluster that saw no data
+  std::vector<double> A((size_t)Kp * Da * Da), ma((size_t)Kp * Da), B((size_t)Kp * Db * Da), mb((size_t)Kp * Db),
+      G((size_t)Kp), ps((size_t)Kp), pe((size_t)Kp);
+  for (int k = 0; k < Kp; ++k) {
+    const lch::GaussWishState& g = k < K ? model.clusters[(size_t)k].gw : prior.gw;
+    gw_conditional(D, g.nu, g.beta, g.m.data(), g.iW.data(), gv, tg, A.data() + (size_t)k * Da * Da,
+                   ma.data() + (size_t)k * Da, B.data() + (size_t)k * Db * Da, mb.data() + (size_t)k * Db, &G[(size_t)k],
+                   &ps[(size_t)k], &pe[(size_t)k]);
+  }
+  std::vector<double> tt((size_t)Jc * Kp), zero((size_t)Jc * Kp, 0.0);
+  for (int b = 0; b < Jc; ++b) {
+    const int j = groups ? groups[b] : 0;
+    for (int k = 0; k < K; ++k) tt[(size_t)b * Kp + k] = std::log(Epi[(size_t)j * K + k]) + G[(size_t)k];
+    if (rest) tt[(size_t)b * Kp + K] = std::log(Erest[(size_t)j]) + G[(size_t)K];
+  }
+  // one raw E-step over the given columns with the marginal whiteners: -d^2 / 2 per column
+  ctx.estep(Kp, A.data(), ma.data(), zero.data(), nullptr, nullptr, /*raw=*/true);
+  ctx.predict_cond(Kp, Db, tt.data(), ps.data(), pe.data(), ma.data(), B.data(), mb.data());
 }
 
 void exemplars(lcc::Context& ctx, const lce::Model& model, bool sparse, const int* groups, int mtop, int32_t* count,

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 namespace lck {
 
@@ -59,6 +60,40 @@ struct PredictDiagLaunch {
 };
 hipError_t launch_predict_diag(const PredictDiagLaunch& a, hipStream_t stream);
 
+// predict_cond_kernel: the conditional mean of the target columns given the context's columns under a
+// Gauss-Wishart mixture.  A raw E-step over the given columns left -d_k^2 / 2 in column k; per valid row
+//   t_k = ttab_jk - e_k log1p(s_k d_k^2),  logp = LSE_k t_k,  r_k = exp(t_k - logp)
+//   mean[row, :] = sum_k r_k (m_b,k + B_k (x_a - m_a,k))
+// The sum over k and over the given columns is one GEMM on the fp64 matrix pipe (v_mfma_f64_4x4x4_4b): its left operand
+// r_k [x_a - m_a,k, 1] is formed in registers, its right operand is the table T.  The kernel overwrites the Kp columns with
+// t_k (each lane reads back only what it wrote itself).  One wave owns 64 rows: no atomics, the same bits on every call.
+constexpr int PC_THREADS = 256;   // four waves, each on its own 64 rows
+constexpr int PC_WAVE_ROWS = 64;  // four row groups of 16: one MFMA block per quad of rows
+constexpr int PC_CHUNK = 32;      // given columns (ones column included) whose x stays in registers: 8 MFMA k-steps
+constexpr int PC_PANEL = 32;      // target columns whose accumulators are resident: 8 quads
+struct PredictCondLaunch {
+  const double* X = nullptr;  // [NP x DP] the given columns (pad columns zero)
+  int DP = 0;
+  int Da = 0;   // given columns
+  int Dae = 0;  // Da + 1 (the ones column) rounded up to a multiple of 4
+  int Db = 0;   // target columns
+  int Dbp = 0;  // Db rounded up to a multiple of 4
+  int Kp = 0;
+  double* col = nullptr;  // [Kp columns x ldq] raw E-step in, t_k out
+  int64_t ldq = 0;
+  int64_t nrg = 0;
+  const int* rginfo = nullptr;
+  int64_t nrows = 0;
+  const double* ttab = nullptr;    // [J x Kp] log E[pi_jk] + G_k
+  const double* pscale = nullptr;  // [Kp] s_k
+  const double* pexp = nullptr;    // [Kp] e_k
+  const double* mext = nullptr;    // [Kp x Dae] m_a,k, then zeros (the ones column is centred on 0)
+  const double* T = nullptr;       // [Kp x Dae x Dbp] T[k][c][t] = B_k[t][c] (c < Da), m_b,k[t] (c = Da), 0 beyond
+  double* mean = nullptr;          // [NP x Db]
+  double* logp = nullptr;          // [NP]
+};
+hipError_t launch_predict_cond(const PredictCondLaunch& a, hipStream_t stream);
+
 }  // namespace lck
 
 namespace lch {
@@ -72,6 +107,24 @@ struct Model;
 }
 
 namespace lcp {
+// The two column lists of a conditional prediction, checked: every index in [0, D), no index twice, none in both lists,
+// at least one of each.  target == nullptr: every column that is not given, ascending.  Returns the target list; throws
+// std::invalid_argument naming the case.
+std::vector<int> conditional_split(int D, const int* given, int ngiven, const int* target, int ntarget);
+// Per-cluster tables of the conditional prediction from a Gauss-Wishart posterior (nu, beta, m [D], iW
+// [D x D]) and a checked split (a = given, b = target):
+//   A [Da x Da] lower-triangular, row-major: ||A (x_a - m_a)||^2 = nu (x_a - m_a)^T iW_aa^-1 (x_a - m_a)
+//   B [Db x Da] = iW_ba iW_aa^-1 (two triangular solves with the Cholesky factor of iW_aa), ma [Da], mb [Db]
+//   log P_a(x_a) = G - e log1p(s d^2): the Student-t marginal with nu + 1 - D degrees of freedom
+// Any output may be null.
+void gw_conditional(int D, double nu, double beta, const double* m, const double* iW, const std::vector<int>& given,
+                    const std::vector<int>& target, double* A, double* ma, double* B, double* mb, double* G, double* s,
+                    double* e);
+// E[x_target | x_given, training data] and log p(x_given | training data) of the rows in ctx (its columns are the given
+// columns, in the order of `given`): into the context's conditional outputs (Context::get_conditional).  Gauss-Wishart
+// models only; all K clusters take part (and the prior component of StickBreak weights), as in predict()'s logp.
+void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* groups, const int* given, int ngiven,
+                         const int* target, int ntarget);
 // E[pi_k] (K values) and the mass beyond the truncation E[pi_rest] of a weight distribution in its updated state:
 //   Dirichlet:  alpha_k / sum(alpha), no rest
 //   StickBreak: E[v_k] prod_{i before k} E[1 - v_i] in ordvec order (distributions.cpp:139-165), rest prod_i E[1 - v_i]
