@@ -4,10 +4,13 @@
 // otherwise.  Everything a kernel would use as an address is checked on the host BEFORE anything is launched: a wrong
 // test comes back as -1 and a failed assertion, never as a memory fault.  Buffers marked "io" are uploaded as the
 // caller filled them (sentinels) and downloaded whole, so that a write outside the intended entries shows.
-// Python side: tests/aux_hooks.py; cases: tests/test_gpu_aux_kernels.py.
+// Python side: tests/aux_hooks.py; cases: tests/test_gpu_aux_kernels.py, and tests/test_gpu_predict_kernels.py for the
+// launchers of lc_kernels_predict.hip and lc_kernels_topic.hip at the end of this file.
+#include <algorithm>
 #include <vector>
 
 #include "lc_device.hpp"
+#include "lc_predict.hpp"
 
 namespace {
 
@@ -89,6 +92,19 @@ __global__ void __launch_bounds__(256) rcp_pos_probe_kernel(const double* __rest
   const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
   if (i < n) out[i] = lck::rcp_pos(x[i]);
 }
+__global__ void __launch_bounds__(256) log1p_nonneg_probe_kernel(const double* __restrict__ x, i64 n, double* __restrict__ out) {
+  __shared__ lck::LogEntry ltab[128];
+  lck::fill_log_table(ltab, threadIdx.x, 256);
+  __syncthreads();
+  const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = lck::log1p_nonneg(x[i], ltab);
+}
+
+// the rows of a prediction launch: nrg >= 1 row groups inside ldq; rginfo words naming groups below J, or (null) nrows
+bool pred_rows_ok(i64 nrg, i64 ldq, const int* rginfo, i64 nrows, int J) {
+  if (nrg < 1 || nrg > ((i64)1 << 40) / RG || nrg * RG > ldq || J < 1) return false;
+  return rginfo ? rginfo_ok(rginfo, nrg, J) : (nrows >= 0 && nrows <= nrg * RG);
+}
 
 }  // namespace
 
@@ -122,6 +138,15 @@ LC_HOOK lc_test_rcp_pos(const double* x, i64 n, double* out) {
   double* dout = s.out(out, (size_t)n);
   if (!s.ok()) return s.finish(hipSuccess);
   hipLaunchKernelGGL(rcp_pos_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, dx, n, dout);
+  return s.finish(hipGetLastError());
+}
+LC_HOOK lc_test_log1p_nonneg(const double* x, i64 n, double* out) {
+  if (!x || !out || n < 1) return -1;
+  Scope s;
+  const double* dx = s.in(x, (size_t)n);
+  double* dout = s.out(out, (size_t)n);
+  if (!s.ok()) return s.finish(hipSuccess);
+  hipLaunchKernelGGL(log1p_nonneg_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, dx, n, dout);
   return s.finish(hipGetLastError());
 }
 
@@ -439,4 +464,168 @@ LC_HOOK lc_test_bound_select(int ncol, int K, i64 NP, const double* ref, double*
   a.need = s.io(need, (size_t)NP);
   if (!s.ok()) return s.finish(hipSuccess);
   return s.finish(lck::launch_bound_select(a, nullptr));
+}
+
+// ---- prediction (lc_kernels_predict.hip) ------------------------------------------------------------------------------------
+// col (io; qcol == col) [ncols x ldq], ncols >= max(K, Kp); rginfo [nrg] or null (then nrows, J = 1); ctab [J x K];
+// ptab [J x Kp], pscale / pexp [Kp] (null when Kp = 0); label / logZ / logp (io) [nrg * 16]
+LC_HOOK lc_test_predict_rows(double* col, int ncols, i64 ldq, int K, int Kp, i64 nrg, const int* rginfo, i64 nrows, int J,
+                             const double* ctab, const double* ptab, const double* pscale, const double* pexp, int keep_q,
+                             int* label, double* logZ, double* logp) {
+  if (!col || !ctab || !label || !logZ || !logp || K < 1 || Kp < 0 || ncols < K || ncols < Kp || ncols > 4096) return -1;
+  if (Kp > 0 && (!ptab || !pscale || !pexp)) return -1;
+  if (!pred_rows_ok(nrg, ldq, rginfo, nrows, J) || (!rginfo && J != 1)) return -1;
+  const size_t NP = (size_t)(nrg * RG);
+  Scope s;
+  lck::PredictRowsLaunch a;
+  double* dcol = s.io(col, (size_t)ncols * (size_t)ldq);
+  a.col = dcol;
+  a.qcol = dcol;
+  a.ldq = ldq;
+  a.K = K;
+  a.Kp = Kp;
+  a.nrg = nrg;
+  a.rginfo = rginfo ? s.in(rginfo, (size_t)nrg) : nullptr;
+  a.nrows = nrows;
+  a.ctab = s.in(ctab, (size_t)J * K);
+  a.ptab = Kp ? s.in(ptab, (size_t)J * Kp) : nullptr;
+  a.pscale = Kp ? s.in(pscale, (size_t)Kp) : nullptr;
+  a.pexp = Kp ? s.in(pexp, (size_t)Kp) : nullptr;
+  a.keep_q = keep_q ? 1 : 0;
+  a.label = s.io(label, NP);
+  a.logZ = s.io(logZ, NP);
+  a.logp = s.io(logp, NP);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_predict_rows(a, nullptr));
+}
+// X [nrg * 16 x DP]; a / w [Kp x DP]; ptab [J x Kp]; pexp [Kp]; logp (io) [nrg * 16]; flag (io) one int.  A DP that is no
+// multiple of PRED_RENORM goes to the launcher as it is (its refusal is what a test asks for; nothing is launched then).
+LC_HOOK lc_test_predict_diag(int mode, const double* X, int DP, i64 nrg, const int* rginfo, i64 nrows, int J, int Kp,
+                             const double* a_, const double* w, const double* ptab, const double* pexp, double* logp, int* flag) {
+  if (!X || !a_ || !w || !ptab || !pexp || !logp || !flag || (mode != 0 && mode != 1) || DP < 1 || DP > 4096 || Kp < 1) return -1;
+  if (!pred_rows_ok(nrg, nrg * RG, rginfo, nrows, J) || (!rginfo && J != 1)) return -1;
+  const size_t NP = (size_t)(nrg * RG);
+  Scope s;
+  lck::PredictDiagLaunch a;
+  a.mode = mode;
+  a.X = s.in(X, NP * DP);
+  a.DP = DP;
+  a.nrg = nrg;
+  a.rginfo = rginfo ? s.in(rginfo, (size_t)nrg) : nullptr;
+  a.nrows = nrows;
+  a.Kp = Kp;
+  a.a = s.in(a_, (size_t)Kp * DP);
+  a.w = s.in(w, (size_t)Kp * DP);
+  a.ptab = s.in(ptab, (size_t)J * Kp);
+  a.pexp = s.in(pexp, (size_t)Kp);
+  a.logp = s.io(logp, NP);
+  a.flag = s.io(flag, 1);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_predict_diag(a, nullptr));
+}
+// X [nrg * 16 x DP]; col (io) [Kp x ldq]; ttab [J x Kp]; pscale / pexp [Kp]; mext [Kp x Dae]; T [Kp x Dae x Dbp]; mean (io)
+// [nrg * 16 x Db]; logp (io) [nrg * 16].  A combination of widths that launch_predict_cond refuses (its own conditions,
+// restated here) has no array sizes: it goes to the launcher with the numbers alone and no buffer, and nothing is launched.
+LC_HOOK lc_test_predict_cond(const double* X, int DP, int Da, int Dae, int Db, int Dbp, int Kp, double* col, i64 ldq, i64 nrg,
+                             const int* rginfo, i64 nrows, int J, const double* ttab, const double* pscale, const double* pexp,
+                             const double* mext, const double* T, double* mean, double* logp) {
+  if (!X || !col || !ttab || !pscale || !pexp || !mext || !T || !mean || !logp) return -1;
+  if (!pred_rows_ok(nrg, ldq, rginfo, nrows, J) || (!rginfo && J != 1)) return -1;
+  lck::PredictCondLaunch a;
+  a.DP = DP;
+  a.Da = Da;
+  a.Dae = Dae;
+  a.Db = Db;
+  a.Dbp = Dbp;
+  a.Kp = Kp;
+  a.ldq = ldq;
+  a.nrg = nrg;
+  a.nrows = nrows;
+  if (Kp < 1 || Da < 1 || Db < 1 || DP < Da || Dae < Da + 1 || Dae % 4 != 0 || Dbp < Db || Dbp % 4 != 0)
+    return (int)lck::launch_predict_cond(a, nullptr);
+  if (Kp > 4096 || DP > 4096 || Dae > 4096 || Dbp > 4096) return -1;
+  const size_t NP = (size_t)(nrg * RG);
+  Scope s;
+  a.X = s.in(X, NP * DP);
+  a.col = s.io(col, (size_t)Kp * (size_t)ldq);
+  a.rginfo = rginfo ? s.in(rginfo, (size_t)nrg) : nullptr;
+  a.ttab = s.in(ttab, (size_t)J * Kp);
+  a.pscale = s.in(pscale, (size_t)Kp);
+  a.pexp = s.in(pexp, (size_t)Kp);
+  a.mext = s.in(mext, (size_t)Kp * Dae);
+  a.T = s.in(T, (size_t)Kp * Dae * Dbp);
+  a.mean = s.io(mean, NP * Db);
+  a.logp = s.io(logp, NP);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_predict_cond(a, nullptr));
+}
+
+// ---- document inference (lc_kernels_topic.hip) ----------------------------------------------------------------------------------
+// topic_infer_lds itself: the bytes of dynamic LDS (0: K and T do not fit; *tile_cap and *e_lds are then untouched)
+LC_HOOK lc_test_topic_plan(int K, int T, int threads, const i64* nrows, int docs, i64* tile_cap, int* e_lds) {
+  if (!tile_cap || !e_lds || K < 1 || T < 1 || K > (1 << 20) || T > (1 << 20) || threads < 64 || threads > 1024 || docs < 0 ||
+      (docs > 0 && !nrows))
+    return -1;
+  for (int i = 0; i < docs; ++i)
+    if (nrows[i] < 0 || nrows[i] > ((i64)1 << 40)) return -1;
+  int64_t cap = *tile_cap;
+  const size_t lds = lck::topic_infer_lds(K, T, threads, reinterpret_cast<const int64_t*>(nrows), docs, &cap, e_lds);
+  *tile_cap = cap;
+  return (int)lds;
+}
+// col (io) [K x ldq]; goff / nrows [docs]: document i owns the rows goff[i] ... goff[i] + nrows[i], inside NP <= ldq and
+// disjoint from every other document's; a [docs x T]; E [T x K]; label / logZ (io) [NP]; qY (io) [docs x T]; F / dint (io)
+// [docs x 2].  threads = 0: chosen as Context::topic_infer does.  The plan (LDS bytes, tile_cap, e_lds) is topic_infer_lds';
+// lds_request > 0 replaces the byte count and must exceed it (a test of the launcher's upper limit).  K, T, max_sweeps or
+// threads that launch_topic_infer refuses go to it with the numbers alone and no buffer: nothing is launched.
+LC_HOOK lc_test_topic_infer(double* col, i64 ldq, i64 NP, int K, int T, int docs, const i64* goff, const i64* nrows, const double* a_,
+                            const double* E, int max_sweeps, double tol, int keep_q, int threads, i64 lds_request, int* label,
+                            double* logZ, double* qY, double* F, int* dint) {
+  if (!col || !E || !label || !logZ || docs < 0 || NP < 0 || NP > ldq) return -1;
+  if (docs > 0 && (!goff || !nrows || !a_ || !qY || !F || !dint)) return -1;
+  i64 maxN = 0;
+  std::vector<std::pair<i64, i64>> span;
+  for (int i = 0; i < docs; ++i) {
+    if (nrows[i] < 0 || goff[i] < 0 || goff[i] > NP || nrows[i] > NP - goff[i]) return -1;
+    maxN = std::max(maxN, nrows[i]);
+    if (nrows[i]) span.emplace_back(goff[i], goff[i] + nrows[i]);
+  }
+  std::sort(span.begin(), span.end());
+  for (size_t i = 1; i < span.size(); ++i)
+    if (span[i].first < span[i - 1].second) return -1;
+  lck::TopicInferLaunch l;
+  l.threads = threads ? threads : maxN <= 64 ? 64 : maxN <= 128 ? 128 : 256;
+  l.ldq = ldq;
+  l.K = K;
+  l.T = T;
+  l.docs = docs;
+  l.max_sweeps = max_sweeps;
+  l.tol = tol;
+  l.keep_q = keep_q ? 1 : 0;
+  if (docs > 0 && (K < 1 || T < 1 || max_sweeps < 1 || (l.threads != 64 && l.threads != 128 && l.threads != 256)))
+    return (int)lck::launch_topic_infer(l, 0, nullptr);
+  if (K < 1 || T < 1 || K > 4096 || T > 4096) return -1;
+  int64_t cap = 0;
+  int el = 0;
+  size_t lds = lck::topic_infer_lds(K, T, l.threads, reinterpret_cast<const int64_t*>(nrows), docs, &cap, &el);
+  if (lds == 0) return -1;
+  if (lds_request != 0) {
+    if (lds_request <= (i64)lds) return -1;
+    lds = (size_t)lds_request;
+  }
+  l.tile_cap = cap;
+  l.e_lds = el;
+  Scope s;
+  l.col = s.io(col, (size_t)K * (size_t)ldq);
+  l.goff = reinterpret_cast<const int64_t*>(s.in(goff, (size_t)docs));
+  l.nrows = reinterpret_cast<const int64_t*>(s.in(nrows, (size_t)docs));
+  l.a = s.in(a_, (size_t)docs * T);
+  l.E = s.in(E, (size_t)T * K);
+  l.label = s.io(label, (size_t)NP);
+  l.logZ = s.io(logZ, (size_t)NP);
+  l.qY = s.io(qY, (size_t)docs * T);
+  l.F = s.io(F, (size_t)docs * 2);
+  l.dint = s.io(dint, (size_t)docs * 2);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_topic_infer(l, lds, nullptr));
 }

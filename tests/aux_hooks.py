@@ -1,6 +1,7 @@
 """ctypes prototypes and numpy-in / numpy-out wrappers for the lc_test_* entry points of libcluster_hip_testhooks.so
-(libcluster_amd/csrc/lc_testhooks.hip): one launcher of lc_kernels_aux.hip per call, on host arrays.  A plain helper module
-of tests/test_gpu_aux_kernels.py (and of the symbol test in tests/test_host.py); no fixtures, no pytest hooks.
+(libcluster_amd/csrc/lc_testhooks.hip): one launcher of lc_kernels_aux.hip, lc_kernels_predict.hip or lc_kernels_topic.hip per
+call, on host arrays.  A plain helper module of tests/test_gpu_aux_kernels.py and tests/test_gpu_predict_kernels.py (and of
+the symbol test in tests/test_host.py); no fixtures, no pytest hooks.
 
 Every wrapper returns the hook's status first (0, -1 = refused by the host-side validation, or a HIP error code); arrays
 the caller passes as destinations are uploaded as they are and overwritten with what the device left in them."""
@@ -23,6 +24,13 @@ REDUCE_TMP_ELEMS = 512
 SEL_ROWS = 1024
 GCS_SLICES = 64
 BOUND_MAX_COLS, BOUND_MAX_K = 8, 72
+# (lc_kernels_predict.hip, lc_predict.hpp, lc_kernels_topic.hip, lc_kernels.h: tests/test_gpu_predict_kernels.py)
+PR_COLS = 8
+PC_CHUNK, PC_PANEL, PC_WAVE_ROWS, PC_THREADS = 32, 32, 64, 256
+PRED_RENORM = 4
+TI_KR = 16
+TOPIC_E_LDS = 128
+TOPIC_LDS_BYTES = 40 * 1024
 HIP_ERROR_INVALID_VALUE = 1
 _M64 = (1 << 64) - 1
 
@@ -31,6 +39,7 @@ PROTOTYPES = {
     "lc_test_rank_order_sum": [_P, _I, _L, _P],
     "lc_test_exp_nonpos": [_P, _L, _P],
     "lc_test_rcp_pos": [_P, _L, _P],
+    "lc_test_log1p_nonneg": [_P, _L, _P],
     "lc_test_reduce_partials": [_P, _I, _L, _P, _I],
     "lc_test_reduce_records": [_P, _I, _L, _I, _P, _P, _P],
     "lc_test_group_colsum": [_P, _L, _I, _P, _I, _P, _I, _L],
@@ -50,6 +59,11 @@ PROTOTYPES = {
     "lc_test_qhash_verify": [_P, _L, _I, _L, _P, _P],
     "lc_test_qz_resync": [_P, _P, _L, _I, _I, _L, _P, _P],
     "lc_test_bound_select": [_I, _I, _L, _P, _P, _P, _P, _P, _P, _P, _D, _P, _P, _P],
+    "lc_test_predict_rows": [_P, _I, _L, _I, _I, _L, _P, _L, _I, _P, _P, _P, _P, _I, _P, _P, _P],
+    "lc_test_predict_diag": [_I, _P, _I, _L, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P],
+    "lc_test_predict_cond": [_P, _I, _I, _I, _I, _I, _I, _P, _L, _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P],
+    "lc_test_topic_plan": [_I, _I, _I, _P, _I, _P, _P],
+    "lc_test_topic_infer": [_P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _I, _D, _I, _I, _L, _P, _P, _P, _P, _P],
 }
 
 _lib = None
@@ -164,6 +178,12 @@ def rcp_pos(x):
     x = _a(x, f64)
     out = np.empty_like(x)
     return hooks().lc_test_rcp_pos(_p(x), x.size, _p(out)), out
+
+
+def log1p_nonneg(x):
+    x = _a(x, f64)
+    out = np.empty_like(x)
+    return hooks().lc_test_log1p_nonneg(_p(x), x.size, _p(out)), out
 
 
 def reduce_partials(partial, use_tmp=False, sentinel=np.nan):
@@ -309,3 +329,71 @@ def bound_select(K, ref, dest, sigma, bnorm, cnew, rmax, ramax, T, usable, dcj, 
     assert rmax.size == ramax.size == need.size == NP
     return hooks().lc_test_bound_select(ncol, K, NP, _p(ref), _p(dest), _p(sigma), _p(bnorm), _p(cnew), _p(rmax), _p(ramax), T,
                                         _p(usable), _p(dcj), _p(need))
+
+
+# ---- prediction and document inference -----------------------------------------------------------------------------------
+def _rows(rginfo, nrows, nrg, tab):
+    """-> rginfo array or None, nrows, J of a prediction launch whose per-group table is `tab` [J x *]"""
+    rg = _a(rginfo, i32)
+    assert tab.ndim == 2 and (rg is None or rg.size == nrg) and (rg is not None or tab.shape[0] == 1)
+    return rg, int(nrows), tab.shape[0]
+
+
+def predict_rows(col, K, Kp, nrg, ctab, ptab, pscale, pexp, keep_q, label, logZ, logp, rginfo=None, nrows=0):
+    """col [ncols x ldq] in place; ctab [J x K]; ptab [J x Kp], pscale / pexp [Kp] (None when Kp = 0); label (int32), logZ,
+    logp [nrg * 16] in place"""
+    col, label, logZ, logp = _io(col, f64), _io(label, i32), _io(logZ, f64), _io(logp, f64)
+    ct, pt, ps, pe = _a(ctab, f64), _a(ptab, f64), _a(pscale, f64), _a(pexp, f64)
+    rg, nrows, J = _rows(rginfo, nrows, nrg, ct)
+    assert ct.shape == (J, K) and label.size == logZ.size == logp.size == nrg * 16
+    assert Kp == 0 or (pt.shape == (J, Kp) and ps.size == pe.size == Kp)
+    return hooks().lc_test_predict_rows(_p(col), col.shape[0], col.shape[1], K, Kp, nrg, _p(rg), nrows, J, _p(ct), _p(pt), _p(ps),
+                                        _p(pe), int(keep_q), _p(label), _p(logZ), _p(logp))
+
+
+def predict_diag(mode, X, a, w, ptab, pexp, logp, flag, rginfo=None, nrows=0):
+    """X [nrg * 16 x DP]; a / w [Kp x DP]; ptab [J x Kp]; logp [nrg * 16] and flag (int32 [1]) in place"""
+    X, a, w, pt, pe, logp, flag = _a(X, f64), _a(a, f64), _a(w, f64), _a(ptab, f64), _a(pexp, f64), _io(logp, f64), _io(flag, i32)
+    NP, DP = X.shape
+    Kp = pe.size
+    rg, nrows, J = _rows(rginfo, nrows, NP // 16, pt)
+    assert NP % 16 == 0 and a.shape == w.shape == (Kp, DP) and pt.shape == (J, Kp) and logp.size == NP and flag.size == 1
+    return hooks().lc_test_predict_diag(mode, _p(X), DP, NP // 16, _p(rg), nrows, J, Kp, _p(a), _p(w), _p(pt), _p(pe), _p(logp),
+                                        _p(flag))
+
+
+def predict_cond(X, Da, Dae, Db, Dbp, col, ttab, pscale, pexp, mext, T, mean, logp, rginfo=None, nrows=0, check_shapes=True, Kp=None):
+    """X [nrg * 16 x DP]; col [Kp x ldq], mean [nrg * 16 x Db], logp [nrg * 16] in place; ttab [J x Kp]; mext [Kp x Dae];
+    T [Kp x Dae x Dbp].  check_shapes=False: the widths (and Kp, when given) go to the hook as they are (the launcher's refusals)."""
+    X, col, mean, logp = _a(X, f64), _io(col, f64), _io(mean, f64), _io(logp, f64)
+    tt, ps, pe, mext, T = _a(ttab, f64), _a(pscale, f64), _a(pexp, f64), _a(mext, f64), _a(T, f64)
+    NP, DP = X.shape
+    Kp = ps.size if Kp is None else Kp
+    rg, nrows, J = _rows(rginfo, nrows, NP // 16, tt)
+    if check_shapes:
+        assert NP % 16 == 0 and col.shape[0] == Kp and tt.shape == (J, Kp) and pe.size == Kp and mext.shape == (Kp, Dae)
+        assert T.shape == (Kp, Dae, Dbp) and mean.shape == (NP, Db) and logp.size == NP
+    return hooks().lc_test_predict_cond(_p(X), DP, Da, Dae, Db, Dbp, Kp, _p(col), col.shape[1], NP // 16, _p(rg), nrows, J, _p(tt),
+                                        _p(ps), _p(pe), _p(mext), _p(T), _p(mean), _p(logp))
+
+
+def topic_plan(K, T, threads, nrows):
+    """-> bytes of dynamic LDS (0: does not fit, -1: refused), tile_cap, e_lds"""
+    nr = _a(nrows, i64)
+    cap, el = C.c_longlong(-7), C.c_int(-7)
+    rc = hooks().lc_test_topic_plan(K, T, threads, _p(nr), nr.size, C.addressof(cap), C.addressof(el))
+    return rc, cap.value, el.value
+
+
+def topic_infer(col, NP, K, T, goff, nrows, a, E, max_sweeps, tol, keep_q, threads, label, logZ, qY, F, dint, lds_request=0,
+                check_shapes=True):
+    """col [K x ldq] in place (its shape is not looked at when check_shapes is False: the launcher's refusals); goff / nrows
+    [docs]; a [docs x T]; E [T x K]; label (int32) / logZ [NP], qY [docs x T], F / dint (int32) [docs x 2] in place"""
+    col, label, logZ, qY, F, dint = _io(col, f64), _io(label, i32), _io(logZ, f64), _io(qY, f64), _io(F, f64), _io(dint, i32)
+    goff, nrows, a, E = _a(goff, i64), _a(nrows, i64), _a(a, f64), _a(E, f64)
+    docs = goff.size
+    if check_shapes:
+        assert col.shape[0] == K and nrows.size == docs and a.shape == (docs, T) and E.shape == (T, K)
+        assert label.size == logZ.size == NP and qY.shape == (docs, T) and F.shape == (docs, 2) and dint.shape == (docs, 2)
+    return hooks().lc_test_topic_infer(_p(col), col.shape[1], NP, K, T, docs, _p(goff), _p(nrows), _p(a), _p(E), max_sweeps, tol,
+                                       int(keep_q), threads, lds_request, _p(label), _p(logZ), _p(qY), _p(F), _p(dint))

@@ -43,7 +43,7 @@ def test_test_hooks_live_in_the_hooks_library_only(lib):
     hooked = aux_hooks.exported_symbols(aux_hooks.HOOKS_LIB)
     assert not [s for s in shipped if s.startswith("lc_test_")]
     declared = set(aux_hooks.PROTOTYPES)
-    assert len(declared) >= 21 and declared <= hooked, sorted(declared - hooked)
+    assert len(declared) >= 27 and declared <= hooked, sorted(declared - hooked)
     assert {s for s in hooked if s.startswith("lc_test_")} == declared  # no hook without a prototype either
     assert {s for s in shipped if s.startswith("lc_")} == {s for s in hooked if s.startswith("lc_")} - declared
     h = aux_hooks.hooks()  # loads, and every prototype binds
@@ -70,6 +70,22 @@ def test_aux_hooks_constants_are_those_of_the_sources():
     assert const("QHASH_NONE") - (1 << 64) == aux_hooks.QHASH_NONE
     assert "if (tmp && nparts > 8192 && n <= REDUCE_TMP_ELEMS)" in text and "nparts > 512 && n <= 4096" in text
     assert "rows >= (int64_t)J * 65536" in text and "if (J > 1024)" in text  # the boundaries the test file names
+    # the prediction and document-inference kernels (tests/test_gpu_predict_kernels.py)
+    text = "".join((csrc / f).read_text() for f in ("lc_predict.hpp", "lc_kernels.h", "lc_kernels_topic.hip", "lc_kernels_predict.hip"))
+    for name in ("PR_COLS", "PC_CHUNK", "PC_PANEL", "PC_WAVE_ROWS", "PC_THREADS", "PRED_RENORM", "TI_KR", "TOPIC_E_LDS"):
+        assert const(name) == getattr(aux_hooks, name), name
+    assert "TOPIC_LDS_BYTES = 40 * 1024;" in text and aux_hooks.TOPIC_LDS_BYTES == 40 * 1024
+    assert "for (int k0 = 0; k0 < Kmax; k0 += PR_COLS)" in text and "const int Kmax = a.K > a.Kp ? a.K : a.Kp;" in text
+    assert "if (a.K <= TI_KR)" in text and "if (N * K <= a.tile_cap)" in text  # registers or not; tile in LDS or not
+    assert "(int64_t)T * K <= TOPIC_E_LDS ? 1 : 0" in text
+    for dp in (16, 32, 48, 64):  # the register-resident instances of predict_diag_kernel; every other width is generic
+        assert text.count(f"case {dp}: hipLaunchKernelGGL((predict_diag_kernel<MODE, {dp}>)") == 1
+    assert "default: hipLaunchKernelGGL((predict_diag_kernel<MODE, 0>)" in text
+    assert "a.DP % PRED_RENORM != 0" in text
+    assert "x[g][s] = c < a.Da ? a.X[(size_t)xrow[g] * a.DP + c] : c == a.Da ? 1.0 : 0.0;" in text  # the ones column
+    # the workgroup size the API picks, which lc_test_topic_infer restates for threads = 0
+    pick = "maxN <= 64 ? 64 : maxN <= 128 ? 128 : 256;"
+    assert pick in (csrc / "lc_topic_predict.cpp").read_text() and pick in (csrc / "lc_testhooks.hip").read_text()
 
 
 def test_constants(lib):
