@@ -361,7 +361,8 @@ const char* lc_last_error(void) { return g_err.c_str(); }
 int lc_version(void) { return 300; }
 const char* lc_statistics_kernel_name(int D, int K) {
   const int DP = D <= 128 ? lck::padded_dim(D) : 0;
-  return DP > 0 ? lck::suffstat_kernel_name(DP, K, lck::estep_active_width(D, DP)) : "suffstat_kernel";
+  // (the dense pass of this shape; the name does not depend on the number of rows)
+  return DP > 0 ? lck::suffstat_plan(DP, lck::estep_active_width(D, DP), lck::RG, K, lck::SS_DENSE).name : "suffstat_kernel";
 }
 #ifndef LC_SOURCE_HASH
 #define LC_SOURCE_HASH "unknown"

@@ -1096,10 +1096,9 @@ bool Context::estep_suffstat_fused(int K, const double* A, const double* m, cons
 // (32-row-aligned row range inside ONE group) x (slice of that group's ACTIVE clusters), upload it with the active
 // cluster lists and the per-cluster record lists, and point the launch at it.  Returns the number of partial records
 // (one per listed (row range, cluster) pair).
-int Context::build_sparse_worklist(const unsigned char* smask, int K, int64_t SS, lck::SuffstatLaunch& a) {
-  const int DP = DP_;
+int Context::build_sparse_worklist(const unsigned char* smask, int K, const lck::SuffstatPlan& plan, lck::SuffstatLaunch& a) {
   int nrec = 0;
-  const int cpb = lck::suffstat_clusters_per_block(DP, K);
+  const int cpb = plan.clusters_per_block;
   std::vector<int> klist, kofs((size_t)J_ + 1, 0);
   for (int j2 = 0; j2 < J_; ++j2) {
     for (int k2 = 0; k2 < K; ++k2)
@@ -1159,7 +1158,6 @@ int Context::build_sparse_worklist(const unsigned char* smask, int K, int64_t SS
   a.rginfo = nullptr;
   sskptr_ = kptr_d;
   sskrec_ = krec_d;
-  sspart_reserve((size_t)std::max(nrec, 1) * SS);
   return nrec;
 }
 
@@ -1179,9 +1177,6 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
   const bool direct = !distributed() && !counts && NP_ > 0;
   hss_.resize(nout);
   if (NP_ > 0) {
-    int64_t chunk_rows = 0;
-    const int nchunks = lck::suffstat_plan(DP, NP_, K, &chunk_rows, DC_);
-    sspart_reserve((size_t)nchunks * K * SS);
     lck::SuffstatLaunch a;
     a.DP = DP;
     a.DC = DC_;
@@ -1192,17 +1187,12 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
     a.K = K;
     a.rginfo = nullptr;
     a.smask = nullptr;
-    if (smask && J_ > 1) {
+    a.mode = skip_zero_ ? lck::SS_ZERO_SKIP : lck::SS_DENSE;
+    if (smask && J_ > 1) {  // (single group: a masked cluster simply receives nothing -- handled on the host below)
       smask_.reserve((size_t)J_ * K);
       LC_HIP(hipMemcpyAsync(smask_.p, smask, (size_t)J_ * K, hipMemcpyHostToDevice, stream_));
       a.rginfo = rginfo_.p;
       a.smask = smask_.p;
-    } else if (smask) {
-      // single group: a masked cluster simply receives nothing (handled on the host below)
-    }
-    a.skip_zero = skip_zero_ ? 1 : 0;
-    bool listed = false;  // sparse work list instead of the dense (chunk, slice) grid
-    if (a.smask) {
       double off = 0.0, tot = 0.0;
       for (int j2 = 0; j2 < J_; ++j2)
         for (int k2 = 0; k2 < K; ++k2) {
@@ -1212,22 +1202,18 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
       // Sparse mode (cluster.cpp:67-79).  When the mask removes a fair share of the (row, cluster) pairs the pass
       // runs over a work list -- (row range of one group) x (slice of that group's ACTIVE clusters) -- so the
       // work is proportional to sum_j N_j * K_active(j); otherwise the dense grid with masked q staged as zeros.
-      if (off > 0.3 * tot) {
-        listed = true;
-        build_sparse_worklist(smask, K, SS, a);  // (sizes the partial buffer for its records)
-      } else if (!skip_zero_) {
-        a.skip_zero = -1;  // dense variant; masked q are staged as zeros
-      }
+      if (off > 0.3 * tot) a.mode = lck::SS_WORK_LIST;
+      else if (!skip_zero_) a.mode = lck::SS_MASKED_DENSE;
     }
-    // ragged K (dense grid only): extra row-split records of the last cluster slice, folded in after the reduction
-    int klast0 = K;
-    const bool skipping = a.skip_zero > 0 || (a.skip_zero == 0 && a.smask);
-    const int extra = listed ? 0 : lck::suffstat_extra_records(DP, K, skipping, &klast0, DC_);
-    const int KR = K + extra;
-    if (extra > 0) {
-      sspart_reserve((size_t)nchunks * KR * SS);
-      ssext_.reserve((size_t)KR * SS);
-    }
+    // kernel, row chunks and records per chunk (ragged K: extra row-split records of the last cluster slice, folded in
+    // after the reduction)
+    const lck::SuffstatPlan plan = lck::suffstat_plan(DP, DC_, NP_, K, a.mode);
+    const bool listed = a.mode == lck::SS_WORK_LIST;  // sparse work list instead of the dense (chunk, slice) grid
+    const int nchunks = plan.nchunks, KR = plan.KR, extra = plan.extra;
+    a.skip_listed = listed && skip_zero_;
+    const int nrec = listed ? build_sparse_worklist(smask, K, plan, a) : nchunks * KR;
+    sspart_reserve((size_t)std::max(nrec, 1) * SS);
+    if (extra > 0) ssext_.reserve((size_t)KR * SS);
     a.KR = KR;
     // active width below the padded one: the feature-GEMM kernel never writes the record entries of the idle columns --
     // they have to BE zero (every other Gauss-Wishart writer of this buffer stores zeros there; the separable families and
@@ -1238,13 +1224,13 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
     }
     a.partial = sspart_.p;
     a.nchunks = nchunks;
-    a.chunk_rows = chunk_rows;
-    timed(Timed::Suffstat, [&] { LC_HIP(lck::launch_suffstat(a, stream_)); });
+    a.chunk_rows = plan.chunk_rows;
+    timed(Timed::Suffstat, [&] { LC_HIP(lck::launch_suffstat(a, plan, stream_)); });
     if (listed)
       LC_HIP(lck::launch_reduce_records(sspart_.p, SS, K, sskptr_, sskrec_, ssout_.p, stream_));
     else if (extra > 0) {
       LC_HIP(lck::launch_reduce_partials(sspart_.p, nchunks, (int64_t)KR * SS, ssext_.p, stream_));
-      LC_HIP(lck::launch_fold_extra(ssext_.p, SS, K, klast0, extra, stream_));
+      LC_HIP(lck::launch_fold_extra(ssext_.p, SS, K, plan.klast0, extra, stream_));
       LC_HIP(hipMemcpyAsync(direct ? hss_.data() : ssout_.p, ssext_.p, (size_t)K * SS * sizeof(double),
                             direct ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream_));
     } else

@@ -353,7 +353,7 @@ class Context {
   bool own_counts(bool masked) const { return J_ > 1 || group_sharded() || masked; }
   void use_device() const;         // hipSetDevice(device_): every method that allocates, launches or copies starts here
   void require_gw_width() const;  // throws for DP > 128 (full-covariance kernels)
-  int build_sparse_worklist(const unsigned char* smask, int K, int64_t SS, lck::SuffstatLaunch& a);
+  int build_sparse_worklist(const unsigned char* smask, int K, const lck::SuffstatPlan& plan, lck::SuffstatLaunch& a);
 
   int device_;
   hipStream_t stream_;

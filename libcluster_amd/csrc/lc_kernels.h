@@ -89,12 +89,20 @@ struct EstepLaunch {
   double* ll_part;       // [estep_grid(...) x K], or nullptr: skip the split-ordering data term
   int raw = 0;           // 1: stop after writing log q~ (no log-sum-exp, fz/ll untouched)
   int sparse = 0;        // 1: ctab holds -inf entries; waves skip clusters inactive for all their rows
-  int lq_lds = 0;        // filled in by launch_estep: log q~ waits in LDS (D <= 48, small K) instead of in qZ
+  int lq_lds = 0;        // filled in by launch_estep (EstepPlan::lq_lds)
 };
-int estep_rows_per_block(int DP);
-// blocks of the launch (and partial sums the caller provides): a function of the WHOLE launch -- DP, DC, K, raw, sparse, nrg
-// have to be set (D = 64 / 80 run four row groups per wave where the log q~ table fits in LDS: other rows per block)
-int64_t estep_grid(const EstepLaunch& a);
+// ONE decision per launch, read by estep_grid and by every launcher: a function of the WHOLE launch -- DP, DC, K, raw,
+// sparse, nrg have to be set (D = 64 / 80 run four row groups per wave where the log q~ table fits in LDS: other rows per block)
+struct EstepPlan {
+  bool ok;              // false: no instance serves this launch (launch_estep returns hipErrorInvalidValue)
+  int rows_per_block;
+  int64_t grid;         // blocks of the launch (and partial sums the caller provides); -1 when !ok
+  bool four_groups;     // the four-row-group instance of D = 64 / 80
+  int DC, lq_lds;       // the active-width instance; log q~ waits in LDS (four row groups per wave, small K) instead of in qZ
+  size_t lds_bytes;     // dynamic LDS of the launch
+};
+EstepPlan estep_plan(const EstepLaunch& a);
+int64_t estep_grid(const EstepLaunch& a);  // estep_plan(a).grid
 hipError_t launch_estep(const EstepLaunch& a, hipStream_t stream);
 
 // ---- small observations: E-step + the next iteration's statistics in one persistent pass (lc_kernels_fused.hip) ----
@@ -132,42 +140,54 @@ struct SSItem {
   int kofs, kcnt;
   int64_t rec0;  // partial record of the item's first cluster
 };
+// ---- the Gauss-Wishart statistics pass: ONE decision (suffstat_plan) for the caller's buffers, the launcher and the tests ----
+constexpr int SS_BR = 32;  // rows staged per batch: a row chunk is a whole number of them
+// the kernel a pass runs: suffstat_kernel, suffstat_feat_kernel, suffstat_quad_kernel, suffstat_kernel's panel launches (DP > 128)
+enum SuffstatRoute { SS_PER_CLUSTER = 0, SS_FEAT = 1, SS_QUAD = 2, SS_WIDE = 3 };
+// what a pass does with the responsibilities: all of them (no mask); a [J x K] mask whose pairs are staged as zeros;
+// the variant that skips (4-row step, cluster) pairs with all-zero q (exact; with or without a mask); a sparse work list
+enum SuffstatMode { SS_DENSE = 0, SS_MASKED_DENSE = 1, SS_ZERO_SKIP = 2, SS_WORK_LIST = 3 };
+struct SuffstatPlan {
+  SuffstatRoute route;
+  int nchunks;             // row chunks of the dense (chunk, slice) grid ...
+  int64_t chunk_rows;      // ... of this many rows (a multiple of SS_BR)
+  // Ragged K: when the last cluster slice of the per-cluster kernel fills only one or two of its four waves, the idle waves
+  // take over part of the active waves' rows (2 or 4 row classes) and write `extra` more records per chunk after the K regular
+  // ones ([row class - 1][cluster of the last slice]); klast0 = first cluster of that slice.  launch_fold_extra adds them in.
+  int extra, klast0, KR;   // KR = K + extra records per chunk
+  int clusters_per_block;  // of the per-cluster kernel (4 waves x clusters per wave): what a work-list item holds
+  const char* name;        // the kernel a profiler will list
+};
+// a function of the shape and the mode alone (identical on every rank) -- and, from NP = 64 * 1024 on, of the device's
+// CU count and the resident blocks per CU of the instance (asked once per instance).  K < 1 or NP < 1: nothing to run.
+SuffstatPlan suffstat_plan(int DP, int DC, int64_t NP, int K, SuffstatMode mode);
 struct SuffstatLaunch {
   int DP;
-  int DC = 0;               // active width (estep_active_width; 0 = DP): the feature-GEMM kernel deals out its patches only
+  int DC = 0;               // active width (estep_active_width; 0 = DP): the feature-GEMM and few-cluster kernels deal out its patches only
   const double* X;
   int64_t NP;               // padded rows (multiple of 16)
   const double* qZ;
   int64_t ldq;
   int K;
+  SuffstatMode mode = SS_DENSE;
   const int* rginfo;        // needed only with smask
-  const unsigned char* smask;  // [J x K] 1 = accumulate (sparse), or nullptr
-  double* partial;          // [nchunks x K x stat_stride(DP)]
-  int nchunks;
-  int64_t chunk_rows;       // multiple of 4
-  int nslice = 1;           // filled in by launch_suffstat
-  int skip_zero = 0;        // 1: use the variant that skips (4-row step, cluster) pairs with all-zero q (exact)
-  const SSItem* items = nullptr;  // sparse work list (device) or nullptr: dense (chunk, slice) grid
-  const int* klist = nullptr;     // active cluster lists the items point into
-  int nitems = 0;
-  // ragged K (see suffstat_extra_records): records per chunk = K + extra; 0 = K
-  int KR = 0;
-  int slice0 = 0, rs = 1, klast0 = 0, nklast = 0;  // filled in by launch_suffstat for the row-split launch of the last slice
-  // wide observations (DP > 128), filled in by launch_suffstat: the kernel works on 64-column panels
-  int* occ_out = nullptr;         // suffstat_plan's question to the few-cluster kernel: resident blocks per CU of the instance this launch would take (nothing is launched)
-  int64_t ldx = 0;                // row stride of X
-  int DPW = 0, colA = 0, colB = 0;  // record width, first column of the A-side / B-side panel
+  const unsigned char* smask;  // [J x K] 1 = accumulate, or nullptr (SS_MASKED_DENSE: set; SS_ZERO_SKIP: optional; else nullptr)
+  double* partial;          // [nchunks x KR x stat_stride(DP)]
+  // the plan's, copied by the caller: launch_suffstat refuses a launch that contradicts the plan it is handed
+  int nchunks = 0, KR = 0;
+  int64_t chunk_rows = 0;
+  // SS_WORK_LIST: the items (device) instead of the dense (chunk, slice) grid, the active cluster lists they point into
+  const SSItem* items = nullptr;
+  const int* klist = nullptr;
+  int nitems = 0, skip_listed = 0;  // skip_listed: the listed pairs run the zero-skipping variant too
+  // ---- written by the internal launchers, each for its own kernel (whatever the caller puts here is overwritten) ----
+  int nslice = 1;                                  // blocks per row chunk
+  int slice0 = 0, rs = 1, klast0 = 0, nklast = 0;  // suffstat_kernel: the row-split launch of the last slice; suffstat_feat_kernel: klast0 = first cluster of the range
+  int64_t ldx = 0;                                 // wide observations (DP > 128), 64-column panels: row stride of X,
+  int DPW = 0, colA = 0, colB = 0;                 // record width, first column of the A-side / B-side panel
 };
-// choose a chunking for (NP, K); returns nchunks and sets chunk_rows
-int suffstat_plan(int DP, int64_t NP, int K, int64_t* chunk_rows, int DC = 0);
-hipError_t launch_suffstat(const SuffstatLaunch& a, hipStream_t stream);
-int suffstat_clusters_per_block(int DP, int K);  // 4 waves x clusters per wave
-const char* suffstat_kernel_name(int DP, int K, int DC = 0);  // "suffstat_kernel" or "suffstat_feat_kernel" (dense pass of this shape)
-// When the last cluster slice of the dense pass fills only one or two of its four waves, the idle waves take over part
-// of the active waves' rows (2 or 4 row classes) and write partial records of their own: `extra` more records per
-// chunk, laid out after the K regular ones ([row class - 1][cluster of the last slice]).  Returns extra (0: no split);
-// klast0 = first cluster of the last slice.  launch_fold_extra adds them into their clusters after the reduction.
-int suffstat_extra_records(int DP, int K, bool skip_or_items, int* klast0, int DC = 0);
+// p = suffstat_plan(a.DP, a.DC, a.NP, a.K, a.mode), computed ONCE per pass by the caller (the fill searches are not free)
+hipError_t launch_suffstat(const SuffstatLaunch& a, const SuffstatPlan& p, hipStream_t stream);
 
 // ---- tile plan of the feature-GEMM statistics kernel (suffstat_feat_kernel, lc_kernels_suffstat.hip) ----------------
 // Features of the active width DC, one per lane of a 16-feature tile (lane (lo2, blk) of tile T holds feature

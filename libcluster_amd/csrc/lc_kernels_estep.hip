@@ -755,10 +755,9 @@ __global__ void __launch_bounds__(WAVES * 64, NPX ? 1 : 2) estep_wide_kernel(Est
 }
 constexpr int WIDE_R = 2, WIDE_WAVES = 4;
 
-static hipError_t launch_estep_wide(const EstepLaunch& a, hipStream_t stream) {
-  if (a.DP % 64) return hipErrorInvalidValue;
-  const size_t shmem = (size_t)(2 * WIDE_CHUNK + WIDE_WAVES * a.K + WIDE_WAVES) * sizeof(double);
-  const int64_t grid = estep_grid(a);
+static hipError_t launch_estep_wide(const EstepLaunch& a, const EstepPlan& p, hipStream_t stream) {
+  const size_t shmem = p.lds_bytes;
+  const int64_t grid = p.grid;
   if (grid <= 0) return hipSuccess;
   static LdsGrant grants[3];
   auto go = [&](auto kern, LdsGrant& grant) {
@@ -778,42 +777,11 @@ static hipError_t launch_estep_wide(const EstepLaunch& a, hipStream_t stream) {
   return go(estep_wide_kernel<WIDE_R, WIDE_WAVES, 0>, grants[0]);
 }
 
-template <int DP>
-struct EstepCfg;
-template <>
-struct EstepCfg<16> { static constexpr int R = 4, WAVES = 4; };
-template <>
-struct EstepCfg<32> { static constexpr int R = 4, WAVES = 4; };  // (8-wave blocks: 15-30 % slower at every narrow shape, 2-wave blocks 0-20 %: round 6)
-template <>
-struct EstepCfg<48> { static constexpr int R = 4, WAVES = 4; };
-template <>
-struct EstepCfg<64> { static constexpr int R = 3, WAVES = 4; };
-template <>
-struct EstepCfg<80> { static constexpr int R = 3, WAVES = 4; };
-template <>
-struct EstepCfg<96> { static constexpr int R = 3, WAVES = 4; };  // (5.04 vs 5.43 ms for R = 2 / WAVES = 8 at N = 1M, K = 32)
-template <>
-struct EstepCfg<112> { static constexpr int R = 2, WAVES = 8; };  // (three row groups spill here)
-template <>
-struct EstepCfg<128> { static constexpr int R = 2, WAVES = 8; };
-
-template <int DP>
-static int rows_per_block_t() { return EstepCfg<DP>::R * EstepCfg<DP>::WAVES * RG; }
-
-int estep_rows_per_block(int DP) {
-  switch (DP) {
-    case 16: return rows_per_block_t<16>();
-    case 32: return rows_per_block_t<32>();
-    case 48: return rows_per_block_t<48>();
-    case 64: return rows_per_block_t<64>();
-    case 80: return rows_per_block_t<80>();
-    case 96: return rows_per_block_t<96>();
-    case 112: return rows_per_block_t<112>();
-    case 128: return rows_per_block_t<128>();
-  }
-  if (DP > 128 && DP % 64 == 0) return WIDE_R * WIDE_WAVES * RG;
-  return -1;
-}
+// row groups per wave and waves per block of the default instance of every layout
+// (32: 8-wave blocks measure 15-30 % slower at every narrow shape, 2-wave blocks 0-20 %: round 6; 96: 5.04 vs 5.43 ms for
+//  R = 2 / WAVES = 8 at N = 1M, K = 32; 112 and 128: three row groups spill)
+constexpr int estep_cfg_r(int DP) { return DP <= 48 ? 4 : DP <= 96 ? 3 : 2; }
+constexpr int estep_cfg_waves(int DP) { return DP <= 96 ? 4 : 8; }
 
 // log q~ waits in LDS up to this block size (LC_ES_LQLDS_KB, test-hooks library: A/B).  Round 6: 40 -> 80 KB, two blocks per CU.
 // With ONE exponential per entry on that path the table pays although the occupancy halves: D = 32, K = 16 2.16 -> 2.00 ms
@@ -830,68 +798,77 @@ static size_t estep_lds_base(int DC, int K, int R, int WAVES) {
 // exponential per entry and the selector-chain epilogue wins where that table fits next to the two parameter records (D = 64:
 // K <= 21, D = 80: K <= 12) from six clusters on -- D = 64, N = 4M: K = 8 2.30 -> 2.25 ms, K = 12 3.35 -> 3.25, K = 16 4.31 -> 4.19
 // (0.82 -> 0.85 of the peak), K = 20 5.31 -> 5.19; K = 4 loses 2 % and keeps three (gpurun_out/r06r).  Dense, normalising
-// launches only.  ONE decision for the launch and for the grid the caller sizes its partial sums by (estep_grid).
-static bool estep_four_groups(const EstepLaunch& a) {
-  static const bool off = test_switch("LC_ES_R4") && atoi(test_switch("LC_ES_R4")) == 0;  // (tests: the default scheme everywhere)
-  if (off || (a.DP != 64 && a.DP != 80) || a.raw || a.sparse || a.K < 6) return false;
-  const int DC = a.DC > 0 ? a.DC : a.DP;
-  return estep_lds_base(DC, a.K, 4, 4) + (size_t)a.K * 4 * 64 * sizeof(double) <= estep_lq_cap();
+// launches only.  ONE decision for the instance, its LDS and the grid the caller sizes its partial sums by (estep_grid).
+EstepPlan estep_plan(const EstepLaunch& a) {
+  EstepPlan p{false, 0, -1, false, a.DC > 0 ? a.DC : a.DP, 0, 0};
+  const int DP = a.DP, DC = p.DC;
+  auto finish = [&](bool ok, int rows_per_block, size_t lds_bytes) {
+    const int64_t rgpb = rows_per_block / RG;
+    p.ok = ok, p.rows_per_block = rows_per_block, p.lds_bytes = lds_bytes;
+    if (ok) p.grid = (a.nrg + rgpb - 1) / rgpb;
+    return p;
+  };
+  if (DP > 128)
+    return finish(DP % 64 == 0, WIDE_R * WIDE_WAVES * RG, (size_t)(2 * WIDE_CHUNK + WIDE_WAVES * a.K + WIDE_WAVES) * sizeof(double));
+  if (padded_dim(DP) != DP) return p;
+  // log q~ of a block's rows as a table in LDS: four row groups per wave, normalising launches, up to the cap
+  auto lq_fits = [&](int R, int WAVES) {
+    return R == 4 && !a.raw && estep_lds_base(DC, a.K, R, WAVES) + (size_t)a.K * WAVES * 64 * sizeof(double) <= estep_lq_cap();
+  };
+  static const bool r4_off = test_switch("LC_ES_R4") && atoi(test_switch("LC_ES_R4")) == 0;  // (tests: the default scheme everywhere)
+  p.four_groups = !r4_off && (DP == 64 || DP == 80) && !a.sparse && a.K >= 6 && lq_fits(4, 4);
+  const int R = p.four_groups ? 4 : estep_cfg_r(DP), WAVES = p.four_groups ? 4 : estep_cfg_waves(DP);
+  // the active-width instances: DP; DP - 8 from 32 columns on (four row groups: those two only); DP - 4 and DP - 12 at 32 and 48
+  const bool ok = DC == DP || (DP >= 32 && DC == DP - 8) || ((DP == 32 || DP == 48) && (DC == DP - 4 || DC == DP - 12));
+  p.lq_lds = lq_fits(R, WAVES) ? 1 : 0;
+  return finish(ok, R * WAVES * RG, estep_lds_base(DC, a.K, R, WAVES) + (p.lq_lds ? (size_t)a.K * WAVES * 64 * sizeof(double) : 0));
 }
-int64_t estep_grid(const EstepLaunch& a) {
-  const int64_t rgpb = (a.DP <= 128 && estep_four_groups(a) ? 4 * 4 * RG : estep_rows_per_block(a.DP)) / RG;
-  return (a.nrg + rgpb - 1) / rgpb;
-}
+int64_t estep_grid(const EstepLaunch& a) { return estep_plan(a).grid; }
 
-template <int DP, int DC, bool SPARSE, int R = EstepCfg<DP>::R, int WAVES = EstepCfg<DP>::WAVES>
-static hipError_t launch_estep_s(const EstepLaunch& a, hipStream_t stream) {
-  size_t shmem = estep_lds_base(DC, a.K, R, WAVES);
+template <int DP, int DC, bool SPARSE, int R = estep_cfg_r(DP), int WAVES = estep_cfg_waves(DP)>
+static hipError_t launch_estep_s(const EstepLaunch& a, const EstepPlan& p, hipStream_t stream) {
+  if (p.DC != DC || p.rows_per_block != R * WAVES * RG) return hipErrorInvalidValue;  // (the instance is the plan's)
   EstepLaunch b = a;
-  if (R == 4 && !a.raw && shmem + (size_t)a.K * WAVES * 64 * sizeof(double) <= estep_lq_cap()) {
-    b.lq_lds = 1;  // log q~ stays in LDS until the normalisation
-    shmem += (size_t)a.K * WAVES * 64 * sizeof(double);
-  }
+  b.lq_lds = p.lq_lds;  // log q~ stays in LDS until the normalisation
   auto kern = estep_kernel<DP, DC, R, WAVES, SPARSE>;
   static LdsGrant grant;  // largest dynamic-LDS size already granted, per device
-  if (hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(kern), shmem, grant); e != hipSuccess) return e;
-  const int64_t grid = estep_grid(a);
-  if (grid <= 0) return hipSuccess;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WAVES * 64), shmem, stream, b);
+  if (hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(kern), p.lds_bytes, grant); e != hipSuccess) return e;
+  if (p.grid <= 0) return hipSuccess;
+  hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(WAVES * 64), p.lds_bytes, stream, b);
   return hipGetLastError();
 }
 
 template <int DP>
-static hipError_t launch_estep_t(const EstepLaunch& a, hipStream_t stream) {
+static hipError_t launch_estep_t(const EstepLaunch& a, const EstepPlan& p, hipStream_t stream) {
   if constexpr (DP == 64 || DP == 80) {
-    if (estep_four_groups(a)) {
-      if (a.DC == DP - 8) return launch_estep_s<DP, DP - 8, false, 4, 4>(a, stream);
-      if (a.DC == 0 || a.DC == DP) return launch_estep_s<DP, DP, false, 4, 4>(a, stream);
-    }
+    if (p.four_groups)
+      return p.DC == DP - 8 ? launch_estep_s<DP, DP - 8, false, 4, 4>(a, p, stream) : launch_estep_s<DP, DP, false, 4, 4>(a, p, stream);
   }
   if constexpr (DP >= 32) {
-    if (a.DC == DP - 8) return a.sparse ? launch_estep_s<DP, DP - 8, true>(a, stream) : launch_estep_s<DP, DP - 8, false>(a, stream);
+    if (p.DC == DP - 8) return a.sparse ? launch_estep_s<DP, DP - 8, true>(a, p, stream) : launch_estep_s<DP, DP - 8, false>(a, p, stream);
   }
   if constexpr (DP == 32 || DP == 48) {  // (active widths in steps of four columns at the two narrowest layouts)
-    if (a.DC == DP - 4) return a.sparse ? launch_estep_s<DP, DP - 4, true>(a, stream) : launch_estep_s<DP, DP - 4, false>(a, stream);
-    if (a.DC == DP - 12) return a.sparse ? launch_estep_s<DP, DP - 12, true>(a, stream) : launch_estep_s<DP, DP - 12, false>(a, stream);
+    if (p.DC == DP - 4) return a.sparse ? launch_estep_s<DP, DP - 4, true>(a, p, stream) : launch_estep_s<DP, DP - 4, false>(a, p, stream);
+    if (p.DC == DP - 12) return a.sparse ? launch_estep_s<DP, DP - 12, true>(a, p, stream) : launch_estep_s<DP, DP - 12, false>(a, p, stream);
   }
-  if (a.DC != 0 && a.DC != DP) return hipErrorInvalidValue;
-  return a.sparse ? launch_estep_s<DP, DP, true>(a, stream) : launch_estep_s<DP, DP, false>(a, stream);
+  return a.sparse ? launch_estep_s<DP, DP, true>(a, p, stream) : launch_estep_s<DP, DP, false>(a, p, stream);
 }
 
 hipError_t launch_estep(const EstepLaunch& a, hipStream_t stream) {
-  if (a.DP > 128) return launch_estep_wide(a, stream);  // -inf entries of ctab need no special handling there
+  const EstepPlan p = estep_plan(a);
+  if (!p.ok) return hipErrorInvalidValue;  // (a width or an active width without an instance: nothing falls through to another one)
+  if (a.DP > 128) return launch_estep_wide(a, p, stream);  // -inf entries of ctab need no special handling there
   switch (a.DP) {
-    case 16: return launch_estep_t<16>(a, stream);
-    case 32: return launch_estep_t<32>(a, stream);
-    case 48: return launch_estep_t<48>(a, stream);
-    case 64: return launch_estep_t<64>(a, stream);
-    case 80: return launch_estep_t<80>(a, stream);
-    case 96: return launch_estep_t<96>(a, stream);
-    case 112: return launch_estep_t<112>(a, stream);
-    case 128: return launch_estep_t<128>(a, stream);
+    case 16: return launch_estep_t<16>(a, p, stream);
+    case 32: return launch_estep_t<32>(a, p, stream);
+    case 48: return launch_estep_t<48>(a, p, stream);
+    case 64: return launch_estep_t<64>(a, p, stream);
+    case 80: return launch_estep_t<80>(a, p, stream);
+    case 96: return launch_estep_t<96>(a, p, stream);
+    case 112: return launch_estep_t<112>(a, p, stream);
+    case 128: return launch_estep_t<128>(a, p, stream);
   }
   return hipErrorInvalidValue;
 }
-
 
 }  // namespace lck

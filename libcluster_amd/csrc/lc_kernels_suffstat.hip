@@ -41,8 +41,6 @@ namespace lck {
 template <int NB>
 struct SSAcc { static constexpr int N = NB * 3 + NB * (NB - 1) / 2 * 4; };
 
-constexpr int SS_BR = 32;  // rows staged per batch
-
 // SKIP: a (4-row step, cluster) pair whose four responsibilities are all exactly 0.0 contributes exactly nothing;
 // the sparse mode (cluster.cpp:67-79: groups without mass in a cluster are left out) launches this variant so that
 // "sparse" saves the work it saves in the reference.  The dense variant carries no test in its inner loop.
@@ -562,6 +560,8 @@ __host__ __device__ constexpr int ft_qld(int NQ) { return NQ > 8 ? 68 : 36; }
 // cluster range of one launch: 32 (up to 8 quads), or -- D = 128 -- 64 in ONE pass over X (16 quads, 4 tiles per wave:
 // one multiply per 16 MFMAs; config 5's K = 64 used to take two launches of 8 quads, each re-reading and re-staging X)
 inline int ft_range(int DP, int K) { return DP == 128 && K % 64 == 0 ? 64 : DP == 128 && K % 64 >= 57 ? 64 : 32; }
+// the instance (its NQ) that serves a launch of nq cluster quads: launch_ss_feat_d's dispatch and suffstat_plan's fill search
+constexpr int ft_instance_quads(int nq) { return nq > 8 ? 16 : nq > 4 ? nq : nq > 2 ? 4 : 2; }
 inline bool ss_feat_eligible(int DP, int K, int DC) {
   // (tests, libcluster_hip_testhooks.so only: 0 off, 1 where it wins, 2 everywhere it exists)
   static const int mode = test_switch("LC_SS_FEAT") ? atoi(test_switch("LC_SS_FEAT")) : 1;
@@ -880,26 +880,21 @@ static hipError_t launch_ss_feat_d(const SuffstatLaunch& a, hipStream_t stream) 
   // range of its own -- near-equal ranges (K = 48 as 24 + 24) put BOTH launches at the poor 5-6 quad ratio.  Every range
   // re-reads X, which an MFMA-bound pass affords.
   SuffstatLaunch b = a;
-  if (b.KR < a.K) b.KR = a.K;
   const int range = ft_range(DP, a.K);
   for (int k0 = 0; k0 < a.K; k0 += range) {
     b.klast0 = k0;
     const int nq = ((a.K - k0 < range ? a.K - k0 : range) + 3) / 4;
     hipError_t e = hipErrorInvalidValue;
-    if constexpr (DP == 128) {
-      if (nq > 8) {
-        e = launch_ss_feat_q<DP, DC, 16>(b, stream);
-        if (e != hipSuccess) return e;
-        continue;
-      }
-    }
-    switch (nq) {
-      case 1: case 2: e = launch_ss_feat_q<DP, DC, 2>(b, stream); break;
-      case 3: case 4: e = launch_ss_feat_q<DP, DC, 4>(b, stream); break;
+    switch (ft_instance_quads(nq)) {
+      case 2: e = launch_ss_feat_q<DP, DC, 2>(b, stream); break;
+      case 4: e = launch_ss_feat_q<DP, DC, 4>(b, stream); break;
       case 5: e = launch_ss_feat_q<DP, DC, 5>(b, stream); break;
       case 6: e = launch_ss_feat_q<DP, DC, 6>(b, stream); break;
       case 7: e = launch_ss_feat_q<DP, DC, 7>(b, stream); break;
       case 8: e = launch_ss_feat_q<DP, DC, 8>(b, stream); break;
+      case 16:  // (ranges of 64 clusters: D = 128 only, ft_range)
+        if constexpr (DP == 128) e = launch_ss_feat_q<DP, DC, 16>(b, stream);
+        break;
     }
     if (e != hipSuccess) return e;
   }
@@ -1156,52 +1151,66 @@ __global__ void __launch_bounds__(256, 2) suffstat_quad_kernel(SuffstatLaunch a)
   }
 }
 
-template <int DP, int DC, int NPART>
-static hipError_t launch_ss_quad_p(const SuffstatLaunch& a, hipStream_t stream) {
-  const size_t shmem = (size_t)(2 * SQ_BR * lds_row_stride(DP) + 2 * SQ_BR * SQ_QLD) * sizeof(double);
-  auto kern = suffstat_quad_kernel<DP, DC, NPART>;
-  static LdsGrant grant;
-  if (hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(kern), shmem, grant); e != hipSuccess) return e;
-  if (a.occ_out) {  // (suffstat_plan: how many blocks of this instance a CU holds)
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, shmem) != hipSuccess || per_cu < 1) per_cu = 2;
-    *a.occ_out = per_cu;
-    return hipSuccess;
-  }
-  SuffstatLaunch b = a;
-  b.nslice = sq_nslice(DP, a.K);
-  if (b.KR < a.K) b.KR = a.K;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(b.nchunks * b.nslice)), dim3(256), shmem, stream, b);
-  return hipGetLastError();
-}
-template <int DP, int DC>
-static hipError_t launch_ss_quad_d(const SuffstatLaunch& a, hipStream_t stream) {
-  const int np = sq_npart(DP, a.K);  // (only the instances sq_npart can ask for exist)
+// the instance <DP, DC, NPART> of a shape, handed to f as three integral constants (only the instances sq_npart can ask for exist)
+template <int DP, int DC, class F>
+static hipError_t sq_instance_d(int K, F& f) {
+  const int np = sq_npart(DP, K);
+  using dp = std::integral_constant<int, DP>;
+  using dc = std::integral_constant<int, DC>;
   if constexpr (DP <= 32) {
-    if (np == 1) return launch_ss_quad_p<DP, DC, 1>(a, stream);
+    if (np == 1) return f(dp{}, dc{}, std::integral_constant<int, 1>{});
   }
   if constexpr (DP <= 48) {
-    if (np == 2) return launch_ss_quad_p<DP, DC, 2>(a, stream);
+    if (np == 2) return f(dp{}, dc{}, std::integral_constant<int, 2>{});
   }
-  return np == 4 ? launch_ss_quad_p<DP, DC, 4>(a, stream) : hipErrorInvalidValue;
+  return np == 4 ? f(dp{}, dc{}, std::integral_constant<int, 4>{}) : hipErrorInvalidValue;
 }
-template <int DP>
-static hipError_t launch_ss_quad_w(const SuffstatLaunch& a, hipStream_t stream) {
+template <int DP, class F>
+static hipError_t sq_instance_w(int DC, int K, F& f) {
   if constexpr (DP <= 48) {
-    if (a.DC == DP - 4) return launch_ss_quad_d<DP, DP - 4>(a, stream);
-    if (a.DC == DP - 12) return launch_ss_quad_d<DP, DP - 12>(a, stream);
+    if (DC == DP - 4) return sq_instance_d<DP, DP - 4>(K, f);
+    if (DC == DP - 12) return sq_instance_d<DP, DP - 12>(K, f);
   }
-  if (a.DC == DP - 8) return launch_ss_quad_d<DP, DP - 8>(a, stream);
-  if (a.DC != 0 && a.DC != DP) return hipErrorInvalidValue;
-  return launch_ss_quad_d<DP, DP>(a, stream);
+  if (DC == DP - 8) return sq_instance_d<DP, DP - 8>(K, f);
+  if (DC != 0 && DC != DP) return hipErrorInvalidValue;
+  return sq_instance_d<DP, DP>(K, f);
 }
-static hipError_t launch_ss_quad(const SuffstatLaunch& a, hipStream_t stream) {
-  switch (a.DP) {
-    case 32: return launch_ss_quad_w<32>(a, stream);
-    case 48: return launch_ss_quad_w<48>(a, stream);
-    case 64: return launch_ss_quad_w<64>(a, stream);
+template <class F>
+static hipError_t sq_instance(int DP, int DC, int K, F f) {
+  switch (DP) {
+    case 32: return sq_instance_w<32>(DC, K, f);
+    case 48: return sq_instance_w<48>(DC, K, f);
+    case 64: return sq_instance_w<64>(DC, K, f);
   }
   return hipErrorInvalidValue;
+}
+static size_t sq_lds_bytes(int DP) { return (size_t)(2 * SQ_BR * lds_row_stride(DP) + 2 * SQ_BR * SQ_QLD) * sizeof(double); }
+static hipError_t launch_ss_quad(const SuffstatLaunch& a, hipStream_t stream) {
+  return sq_instance(a.DP, a.DC, a.K, [&](auto dp, auto dc, auto np) {
+    auto kern = suffstat_quad_kernel<decltype(dp)::value, decltype(dc)::value, decltype(np)::value>;
+    const size_t shmem = sq_lds_bytes(a.DP);
+    static LdsGrant grant;
+    if (hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(kern), shmem, grant); e != hipSuccess) return e;
+    SuffstatLaunch b = a;
+    b.nslice = sq_nslice(a.DP, a.K);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(b.nchunks * b.nslice)), dim3(256), shmem, stream, b);
+    return hipGetLastError();
+  });
+}
+// resident blocks per CU of the instance a shape takes (suffstat_plan's fill search): the runtime is asked once per instance
+static int sq_blocks_per_cu(int DP, int DC, int K) {
+  static std::atomic<int> cache[8 * 16 * 4];  // [layout][active-width step][parts]
+  const int np = sq_npart(DP, K);
+  std::atomic<int>& slot = cache[((DP / 16) % 8) * 64 + (((DP - DC) / 4) % 16) * 4 + (np == 1 ? 0 : np == 2 ? 1 : 2)];
+  int per_cu = slot.load(std::memory_order_relaxed);
+  if (per_cu > 0) return per_cu;
+  const hipError_t e = sq_instance(DP, DC, K, [&](auto dp, auto dc, auto npc) {
+    auto kern = suffstat_quad_kernel<decltype(dp)::value, decltype(dc)::value, decltype(npc)::value>;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, sq_lds_bytes(DP));  // (below 64 KB: no grant needed)
+  });
+  if (e != hipSuccess || per_cu < 1) per_cu = 2;
+  slot.store(per_cu, std::memory_order_relaxed);
+  return per_cu;
 }
 
 template <int DP>
@@ -1232,19 +1241,6 @@ static int ss_cpw(int DP, int K) {
 // row classes for a last slice with `active` of its four waves in use
 static int ss_row_classes(int active) { return active == 1 ? 4 : active == 2 ? 2 : 1; }
 
-int suffstat_extra_records(int DP, int K, bool skip_or_items, int* klast0, int DC) {
-  if (klast0) *klast0 = K;
-  if (DP > 128 || skip_or_items || K < 1) return 0;
-  if (ss_quad_eligible(DP, K)) return 0;      // (whole quads of clusters per wave: no ragged last slice)
-  if (ss_feat_eligible(DP, K, DC)) return 0;  // (the feature-GEMM kernel covers any K of its range with the same 16 waves)
-  const int cpw = ss_cpw(DP, K), kwaves = (K + cpw - 1) / cpw, nslice = (kwaves + 3) / 4;
-  const int rs = ss_row_classes(kwaves - (nslice - 1) * 4);
-  if (rs == 1) return 0;
-  const int k0 = (nslice - 1) * 4 * cpw;
-  if (klast0) *klast0 = k0;
-  return (rs - 1) * (K - k0);
-}
-
 // rec[(klast0 + e % nlast) * SS + i] += rec[(K + e) * SS + i], e = 0 .. extra-1 in order (deterministic)
 __global__ void __launch_bounds__(256) fold_extra_kernel(double* rec, int64_t SS, int K, int klast0, int extra) {
   const int nlast = K - klast0;
@@ -1263,30 +1259,41 @@ hipError_t launch_fold_extra(double* rec, int64_t SS, int K, int klast0, int ext
   return hipGetLastError();
 }
 
-// which kernel a dense Gauss-Wishart statistics pass of this shape runs (bench.py names the kernel it prices)
-const char* suffstat_kernel_name(int DP, int K, int DC) {
-  if (ss_quad_eligible(DP, K)) return "suffstat_quad_kernel";
-  return DP <= 128 && ss_feat_eligible(DP, K, DC) ? "suffstat_feat_kernel" : "suffstat_kernel";
-}
-
-int suffstat_clusters_per_block(int DP, int K) { return DP > 128 ? 4 : 4 * ss_cpw(DP, K); }
-
-int suffstat_plan(int DP, int64_t NP, int K, int64_t* chunk_rows, int DC) {
-  const int cpw = DP > 128 ? 1 : ss_cpw(DP, K);  // wide: panel launches, one cluster per wave
+SuffstatPlan suffstat_plan(int DP, int DC, int64_t NP, int K, SuffstatMode mode) {
+  SuffstatPlan p{SS_PER_CLUSTER, 0, 0, 0, K, K, 4, "suffstat_kernel"};
+  if (K < 1 || NP < 1) return p;
+  if (DC <= 0) DC = DP;
+  // The kernel this SHAPE is eligible for -- the route of its dense pass.  The other modes run the per-cluster kernel, and
+  // at a quad- or feature-eligible shape they run it on the chunking computed below as if the eligible kernel ran, and
+  // without the row split of a ragged last slice (a masked dense pass elsewhere keeps the split): kept as it was found,
+  // not a measured choice (open question).
+  const bool wide = DP > 128, quad = !wide && ss_quad_eligible(DP, K), feat = !wide && !quad && ss_feat_eligible(DP, K, DC);
+  p.route = wide ? SS_WIDE : mode != SS_DENSE ? SS_PER_CLUSTER : quad ? SS_QUAD : feat ? SS_FEAT : SS_PER_CLUSTER;
+  p.name = p.route == SS_QUAD ? "suffstat_quad_kernel" : p.route == SS_FEAT ? "suffstat_feat_kernel" : "suffstat_kernel";
+  const int cpw = wide ? 1 : ss_cpw(DP, K);  // wide: panel launches, one cluster per wave
+  p.clusters_per_block = 4 * cpw;
   const int kwaves = (K + cpw - 1) / cpw;  // waves needed to cover the clusters
+  if (!wide && !quad && !feat && (mode == SS_DENSE || mode == SS_MASKED_DENSE)) {  // (whole quads / any K of a range: no ragged last slice)
+    const int nslice = (kwaves + 3) / 4, rs = ss_row_classes(kwaves - (nslice - 1) * 4);
+    if (rs > 1) {
+      p.klast0 = (nslice - 1) * 4 * cpw;
+      p.extra = (rs - 1) * (K - p.klast0);
+    }
+  }
+  p.KR = K + p.extra;
   // aim for ~8 waves per CU on 256 CUs, at least 256 rows per chunk
   int64_t want = (256 * 8 + kwaves - 1) / kwaves;
-  if (ss_quad_eligible(DP, K)) want = (256 * 8 / 4 + sq_nslice(DP, K) - 1) / sq_nslice(DP, K);  // blocks of four waves, nslice per chunk
+  if (quad) want = (256 * 8 / 4 + sq_nslice(DP, K) - 1) / sq_nslice(DP, K);  // blocks of four waves, nslice per chunk
   // four blocks per resident slot: the hardware back-fills slots as blocks retire, which evens out the
   // per-CU / per-XCD speed differences (measured 25.7 -> 24.9 ms at N=10M, D=64, K=32), while the partial
   // records (chunks x K x (1 + DP + DP^2) doubles) stay below 1 GiB
   const int rounds = 4;
   const int64_t rec = (int64_t)K * (1 + DP + (int64_t)DP * DP) * 8;
   // (wide records are large: allow 4 GiB of them so that the grid still covers the chip)
-  const int64_t cap = ((int64_t)(DP > 128 ? 4 : 1) << 30) / rec;
+  const int64_t cap = ((int64_t)(wide ? 4 : 1) << 30) / rec;
   if (want * rounds <= cap) want *= rounds;
   else if (want < cap) want = cap;
-  else if (want > cap && DP > 128) want = cap > 1 ? cap : 1;
+  else if (want > cap && wide) want = cap > 1 ? cap : 1;
   // at least 1024 rows per chunk where that still leaves two chunks per CU (a chunk's K records are written and read
   // back by the reduction: at 256 rows they are half of a two-cluster sub-problem's traffic), 256 rows otherwise
   int64_t maxchunks = std::max<int64_t>((NP + 1023) / 1024, std::min<int64_t>((NP + 255) / 256, 512));
@@ -1300,66 +1307,48 @@ int suffstat_plan(int DP, int64_t NP, int K, int64_t* chunk_rows, int DC) {
   };
   int64_t rows = 0;
   int64_t n = plan(want, &rows);
+  // share of the last round's resident slots that a grid of `chunks` x nslice blocks fills
+  auto fill = [](int64_t chunks, int nslice, int64_t slots) {
+    const int64_t blocks = chunks * nslice, rounds = (blocks + slots - 1) / slots;
+    return (double)blocks / (double)(rounds * slots);
+  };
   // Feature-GEMM launches put nslice blocks on every chunk and one (8 waves) or two (4 waves) blocks on a CU: a grid
   // whose last round of resident blocks is half empty loses that much of the launch.  Config 5 (D = 128, K = 64: 17 blocks
   // per chunk) ran 127 chunks = 2159 blocks = 8.43 rounds of 256 -- 6 % of the pass idle; 120 chunks are 7.97 rounds.
   // Among the chunk counts down to 80 % of the wanted one, take the fullest last round (the larger count on ties).
-  if (DP <= 128 && !ss_quad_eligible(DP, K) && ss_feat_eligible(DP, K, DC) && NP >= 64 * 1024) {
-    const int range = ft_range(DP, K), nq = ((K < range ? K : range) + 3) / 4;
-    const int nqi = nq > 8 ? 16 : nq > 4 ? nq : nq > 2 ? 4 : 2;  // the instance launch_ss_feat_d takes
-    const int nslice = ft_nslice(DP, DC > 0 ? DC : DP, nqi);
+  if (feat && NP >= 64 * 1024) {
+    const int range = ft_range(DP, K);
+    const int nslice = ft_nslice(DP, DC, ft_instance_quads(((K < range ? K : range) + 3) / 4));
     if (nslice > 0) {
-      const int cus = current_device_cus();
-      const int64_t slots = (int64_t)cus * (ft_waves(DP) == 8 ? 1 : 2);
-      auto fill = [&](int64_t chunks) {
-        const int64_t blocks = chunks * nslice, rounds = (blocks + slots - 1) / slots;
-        return (double)blocks / (double)(rounds * slots);
-      };
-      double best = fill(n);
+      const int64_t slots = (int64_t)current_device_cus() * (ft_waves(DP) == 8 ? 1 : 2);
+      double best = fill(n, nslice, slots);
       for (int64_t w = want - 1; w >= 1 && w * 5 >= want * 4 && best < 0.985; --w) {
         int64_t r2 = 0;
         const int64_t n2 = plan(w, &r2);
-        if (fill(n2) > best + 1e-9) best = fill(n2), n = n2, rows = r2;
+        if (fill(n2, nslice, slots) > best + 1e-9) best = fill(n2, nslice, slots), n = n2, rows = r2;
       }
     }
   }
   // ... and the few-cluster kernel (sq_nslice blocks per chunk, 2 - 4 resident per CU): N = 5M, D = 48, K = 12 ran 684 chunks = 2052
   // blocks = 2.67 rounds of 768
-  if (ss_quad_eligible(DP, K) && NP >= 64 * 1024) {
-    static std::atomic<int> occ_cache[8 * 16 * 4];  // [layout][active-width step][parts]: resident blocks per CU, asked once
-    const int dc = DC > 0 ? DC : DP, np = sq_npart(DP, K);
-    const int slot = ((DP / 16) % 8) * 64 + (((DP - dc) / 4) % 16) * 4 + (np == 1 ? 0 : np == 2 ? 1 : 2);
-    int per_cu = occ_cache[slot].load(std::memory_order_relaxed);
-    if (per_cu <= 0) {
-      SuffstatLaunch q{};
-      q.DP = DP;
-      q.DC = dc;
-      q.K = K;
-      q.nchunks = 1;
-      q.occ_out = &per_cu;
-      if (launch_ss_quad(q, nullptr) != hipSuccess || per_cu < 1) per_cu = 2;
-      occ_cache[slot].store(per_cu, std::memory_order_relaxed);
-    }
+  if (quad && NP >= 64 * 1024) {
     const int nslice = sq_nslice(DP, K);
-    const int64_t slots = (int64_t)current_device_cus() * per_cu;
-    auto fill = [&](int64_t chunks) {
-      const int64_t blocks = chunks * nslice, rounds = (blocks + slots - 1) / slots;
-      return (double)blocks / (double)(rounds * slots);
-    };
+    const int64_t slots = (int64_t)current_device_cus() * sq_blocks_per_cu(DP, DC, K);
     // (chunk counts from 80 % to 125 % of the wanted one, the nearest first: three blocks per chunk on 768 slots have no
     //  full round between 512 and 768 chunks)
-    double best = fill(n);
+    double best = fill(n, nslice, slots);
     for (int64_t d = 1; best < 0.985 && d * 4 <= want; ++d)
       for (int sgn = -1; sgn <= 1; sgn += 2) {
         const int64_t w = want + sgn * d;
         if (w < 1 || (sgn < 0 && w * 5 < want * 4) || w > maxchunks || (sgn > 0 && w > cap)) continue;  // (cap: the partial records' memory)
         int64_t r2 = 0;
         const int64_t n2 = plan(w, &r2);
-        if (fill(n2) > best + 1e-9) best = fill(n2), n = n2, rows = r2;
+        if (fill(n2, nslice, slots) > best + 1e-9) best = fill(n2, nslice, slots), n = n2, rows = r2;
       }
   }
-  *chunk_rows = rows;
-  return (int)n;
+  p.nchunks = (int)n;
+  p.chunk_rows = rows;
+  return p;
 }
 
 template <int DP, int CPW, bool SKIP, int HALF, int PAN = 0, bool RSP = false>
@@ -1382,9 +1371,8 @@ static hipError_t launch_ss_h(const SuffstatLaunch& a, hipStream_t stream) {
   const int nslice = (kwaves + wpb - 1) / wpb;
   SuffstatLaunch b = a;
   b.nslice = nslice;
-  if (b.KR < a.K) b.KR = a.K;
   if constexpr (PAN == 0 && !SKIP && !(DP > 80 && HALF == 0)) {
-    // ragged K: the last slice runs as its own launch with the idle waves sharing the rows (suffstat_extra_records)
+    // ragged K: the last slice runs as its own launch with the idle waves sharing the rows (SuffstatPlan::extra)
     const int rs = ss_row_classes(kwaves - (nslice - 1) * wpb);
     if (!a.items && rs > 1 && b.KR > a.K) {
       b.nslice = nslice - 1;
@@ -1435,45 +1423,42 @@ static hipError_t launch_ss_s(const SuffstatLaunch& a, hipStream_t stream) {
 }
 
 template <int DP, int CPW>
-static hipError_t launch_ss_t(const SuffstatLaunch& a, hipStream_t stream) {
-  // skip_zero: 1 = skipping variant, -1 = dense even with a mask, 0 = skipping iff a mask is given
-  const bool skip = a.skip_zero > 0 || (a.skip_zero == 0 && a.smask);
+static hipError_t launch_ss_t(const SuffstatLaunch& a, bool skip, hipStream_t stream) {
   return skip ? launch_ss_s<DP, CPW, true>(a, stream) : launch_ss_s<DP, CPW, false>(a, stream);
 }
 
-hipError_t launch_suffstat(const SuffstatLaunch& a, hipStream_t stream) {
-  if (a.K <= 0 || a.nchunks <= 0) return hipSuccess;
-  if (a.DP > 128) {
-    if (a.DP % 64) return hipErrorInvalidValue;
-    const bool skip = a.skip_zero > 0 || (a.skip_zero == 0 && a.smask);
-    return skip ? launch_ss_wide<true>(a, stream) : launch_ss_wide<false>(a, stream);
+hipError_t launch_suffstat(const SuffstatLaunch& a, const SuffstatPlan& p, hipStream_t stream) {
+  if (a.K <= 0 || p.nchunks <= 0) return hipSuccess;
+  if (a.DP > 128 && a.DP % 64) return hipErrorInvalidValue;
+  // the launch has to be the one its plan describes: mask and work list as the mode says, the plan's records and chunks
+  if ((p.route == SS_WIDE) != (a.DP > 128) || (p.route != SS_WIDE && p.route != SS_PER_CLUSTER && a.mode != SS_DENSE)) return hipErrorInvalidValue;
+  const bool listed = a.mode == SS_WORK_LIST;
+  if (listed != (a.items != nullptr) || a.KR != p.KR) return hipErrorInvalidValue;
+  if (a.mode != SS_ZERO_SKIP && (a.smask != nullptr) != (a.mode == SS_MASKED_DENSE)) return hipErrorInvalidValue;
+  if (!listed && (a.nchunks != p.nchunks || a.chunk_rows != p.chunk_rows)) return hipErrorInvalidValue;
+  const bool skip = a.mode == SS_ZERO_SKIP || (listed && a.skip_listed);  // the variant that skips all-zero (step, cluster) pairs
+  const int cpw = p.clusters_per_block / 4;
+  switch (p.route) {
+    case SS_WIDE: return skip ? launch_ss_wide<true>(a, stream) : launch_ss_wide<false>(a, stream);
+    case SS_QUAD: return launch_ss_quad(a, stream);
+    case SS_FEAT: return launch_ss_feat(a, stream);
+    case SS_PER_CLUSTER: break;
   }
-  if (ss_quad_eligible(a.DP, a.K) && !a.smask && !a.items && a.skip_zero <= 0 && a.KR <= a.K) return launch_ss_quad(a, stream);
-  if (ss_feat_eligible(a.DP, a.K, a.DC) && !a.smask && !a.items && a.skip_zero <= 0 && a.KR <= a.K)
-    return launch_ss_feat(a, stream);
-  const int cpw = ss_cpw(a.DP, a.K);
   switch (a.DP) {
     case 16:
-      return cpw == 4 ? launch_ss_t<16, 4>(a, stream) : cpw == 2 ? launch_ss_t<16, 2>(a, stream)
-                                                                : launch_ss_t<16, 1>(a, stream);
+      return cpw == 4 ? launch_ss_t<16, 4>(a, skip, stream) : cpw == 2 ? launch_ss_t<16, 2>(a, skip, stream)
+                                                                : launch_ss_t<16, 1>(a, skip, stream);
     case 32:
-      return cpw == 4 ? launch_ss_t<32, 4>(a, stream) : cpw == 2 ? launch_ss_t<32, 2>(a, stream)
-                                                                : launch_ss_t<32, 1>(a, stream);
-    case 48:
-      return cpw == 2 ? launch_ss_t<48, 2>(a, stream) : launch_ss_t<48, 1>(a, stream);
-    case 64:
-      return cpw == 2 ? launch_ss_t<64, 2>(a, stream) : launch_ss_t<64, 1>(a, stream);
-    case 80:
-      return launch_ss_t<80, 1>(a, stream);
-    case 96:
-      return launch_ss_t<96, 1>(a, stream);
-    case 112:
-      return launch_ss_t<112, 1>(a, stream);
-    case 128:
-      return launch_ss_t<128, 1>(a, stream);
+      return cpw == 4 ? launch_ss_t<32, 4>(a, skip, stream) : cpw == 2 ? launch_ss_t<32, 2>(a, skip, stream)
+                                                                : launch_ss_t<32, 1>(a, skip, stream);
+    case 48: return cpw == 2 ? launch_ss_t<48, 2>(a, skip, stream) : launch_ss_t<48, 1>(a, skip, stream);
+    case 64: return cpw == 2 ? launch_ss_t<64, 2>(a, skip, stream) : launch_ss_t<64, 1>(a, skip, stream);
+    case 80: return launch_ss_t<80, 1>(a, skip, stream);
+    case 96: return launch_ss_t<96, 1>(a, skip, stream);
+    case 112: return launch_ss_t<112, 1>(a, skip, stream);
+    case 128: return launch_ss_t<128, 1>(a, skip, stream);
   }
   return hipErrorInvalidValue;
 }
-
 
 }  // namespace lck

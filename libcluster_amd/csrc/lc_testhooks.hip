@@ -4,9 +4,11 @@
 // otherwise.  Everything a kernel would use as an address is checked on the host BEFORE anything is launched: a wrong
 // test comes back as -1 and a failed assertion, never as a memory fault.  Buffers marked "io" are uploaded as the
 // caller filled them (sentinels) and downloaded whole, so that a write outside the intended entries shows.
-// Python side: tests/aux_hooks.py; cases: tests/test_gpu_aux_kernels.py, and tests/test_gpu_predict_kernels.py for the
-// launchers of lc_kernels_predict.hip and lc_kernels_topic.hip at the end of this file.
+// Python side: tests/aux_hooks.py; cases: tests/test_gpu_aux_kernels.py, tests/test_gpu_predict_kernels.py for the
+// launchers of lc_kernels_predict.hip and lc_kernels_topic.hip, and tests/test_gpu_launch_plans.py for the two launch plans
+// at the end of this file.
 #include <algorithm>
+#include <cstdio>
 #include <vector>
 
 #include "lc_device.hpp"
@@ -628,4 +630,30 @@ LC_HOOK lc_test_topic_infer(double* col, i64 ldq, i64 NP, int K, int T, int docs
   l.dint = s.io(dint, (size_t)docs * 2);
   if (!s.ok()) return s.finish(hipSuccess);
   return s.finish(lck::launch_topic_infer(l, lds, nullptr));
+}
+
+// ---- launch plans (lc_kernels.h: SuffstatPlan, EstepPlan) ----------------------------------------------------------------------
+// suffstat_plan itself: out [7] = route, nchunks, chunk_rows, extra, klast0, KR, clusters per block; name [32]
+LC_HOOK lc_test_suffstat_plan(int DP, int DC, i64 NP, int K, int mode, i64* out, char* name) {
+  if (!out || !name || K < 1 || NP < 1 || mode < 0 || mode > 3) return -1;
+  const lck::SuffstatPlan p = lck::suffstat_plan(DP, DC, NP, K, (lck::SuffstatMode)mode);
+  out[0] = p.route, out[1] = p.nchunks, out[2] = p.chunk_rows, out[3] = p.extra, out[4] = p.klast0, out[5] = p.KR;
+  out[6] = p.clusters_per_block;
+  snprintf(name, 32, "%s", p.name);
+  return 0;
+}
+// An E-step launch that no instance serves: *grid = estep_grid, the return value is launch_estep's.  The launch carries
+// numbers alone and no buffer, so a launch that estep_plan accepts is not handed on (-1): nothing is ever launched here.
+LC_HOOK lc_test_estep_refusal(int DP, int DC, int K, int raw, int sparse, i64 nrg, i64* grid) {
+  if (!grid || K < 1 || nrg < 1) return -1;
+  lck::EstepLaunch a{};
+  a.DP = DP;
+  a.DC = DC;
+  a.K = K;
+  a.raw = raw ? 1 : 0;
+  a.sparse = sparse ? 1 : 0;
+  a.nrg = nrg;
+  if (lck::estep_plan(a).ok) return -1;
+  *grid = lck::estep_grid(a);
+  return (int)lck::launch_estep(a, nullptr);
 }

@@ -1,7 +1,8 @@
 """ctypes prototypes and numpy-in / numpy-out wrappers for the lc_test_* entry points of libcluster_hip_testhooks.so
 (libcluster_amd/csrc/lc_testhooks.hip): one launcher of lc_kernels_aux.hip, lc_kernels_predict.hip or lc_kernels_topic.hip per
-call, on host arrays.  A plain helper module of tests/test_gpu_aux_kernels.py and tests/test_gpu_predict_kernels.py (and of
-the symbol test in tests/test_host.py); no fixtures, no pytest hooks.
+call, on host arrays, and the two launch plans (tests/test_gpu_launch_plans.py).  A plain helper module of
+tests/test_gpu_aux_kernels.py and tests/test_gpu_predict_kernels.py (and of the symbol test in tests/test_host.py); no
+fixtures, no pytest hooks.
 
 Every wrapper returns the hook's status first (0, -1 = refused by the host-side validation, or a HIP error code); arrays
 the caller passes as destinations are uploaded as they are and overwritten with what the device left in them."""
@@ -32,6 +33,10 @@ TI_KR = 16
 TOPIC_E_LDS = 128
 TOPIC_LDS_BYTES = 40 * 1024
 HIP_ERROR_INVALID_VALUE = 1
+# (lc_kernels.h: the statistics plan, tests/test_gpu_launch_plans.py)
+SS_BR = 32
+SS_ROUTES = ("per_cluster", "feat", "quad", "wide")            # SuffstatRoute, in the order of the enum
+SS_MODES = ("dense", "masked_dense", "zero_skip", "work_list")  # SuffstatMode
 _M64 = (1 << 64) - 1
 
 _P, _I, _L, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_double
@@ -64,6 +69,8 @@ PROTOTYPES = {
     "lc_test_predict_cond": [_P, _I, _I, _I, _I, _I, _I, _P, _L, _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P],
     "lc_test_topic_plan": [_I, _I, _I, _P, _I, _P, _P],
     "lc_test_topic_infer": [_P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _I, _D, _I, _I, _L, _P, _P, _P, _P, _P],
+    "lc_test_suffstat_plan": [_I, _I, _L, _I, _I, _P, _P],
+    "lc_test_estep_refusal": [_I, _I, _I, _I, _I, _L, _P],
 }
 
 _lib = None
@@ -397,3 +404,24 @@ def topic_infer(col, NP, K, T, goff, nrows, a, E, max_sweeps, tol, keep_q, threa
         assert label.size == logZ.size == NP and qY.shape == (docs, T) and F.shape == (docs, 2) and dint.shape == (docs, 2)
     return hooks().lc_test_topic_infer(_p(col), col.shape[1], NP, K, T, docs, _p(goff), _p(nrows), _p(a), _p(E), max_sweeps, tol,
                                        int(keep_q), threads, lds_request, _p(label), _p(logZ), _p(qY), _p(F), _p(dint))
+
+
+def suffstat_plan(DP, DC, NP, K, mode):
+    """suffstat_plan(DP, DC, NP, K, mode) as a dict: route and mode by name (SS_ROUTES, SS_MODES), nchunks, chunk_rows, extra,
+    klast0, KR, clusters_per_block, name"""
+    out = np.full(7, -7, dtype=i64)
+    name = C.create_string_buffer(32)
+    rc = hooks().lc_test_suffstat_plan(DP, DC, NP, K, SS_MODES.index(mode), _p(out), C.addressof(name))
+    assert rc == 0, rc
+    keys = ("route", "nchunks", "chunk_rows", "extra", "klast0", "KR", "clusters_per_block")
+    d = dict(zip(keys, (int(v) for v in out)), name=name.value.decode(), mode=mode)
+    d["route"] = SS_ROUTES[d["route"]]
+    return d
+
+
+def estep_refusal(DP, DC, K, nrg, raw=False, sparse=False):
+    """-> launch_estep's return value for a launch without buffers that estep_plan refuses (-1: the plan accepts it, nothing
+    was handed on) and estep_grid of that launch"""
+    grid = C.c_longlong(-7)
+    rc = hooks().lc_test_estep_refusal(DP, DC, K, int(raw), int(sparse), nrg, C.addressof(grid))
+    return rc, grid.value

@@ -819,7 +819,7 @@ print(json.dumps(dict(F=[float(v) for v in tr])))
 @pytest.mark.parametrize("N,D,K", [(150_000, 64, 16), (120_000, 57, 8), (100_000, 80, 12), (90_000, 72, 7), (100_001, 64, 21)])
 def test_four_row_group_estep_at_64_and_80_columns_agrees_with_the_three_row_group_one(N, D, K, tmp_path):
     """D = 64 / 80 with 6 ... 21 / 12 clusters run estep_kernel's four-row-group scheme (log q~ table in LDS, one
-    exponential per entry, selector-chain epilogue: lc_kernels_estep.hip, estep_four_groups) since round 6; LC_ES_R4=0
+    exponential per entry, selector-chain epilogue: lc_kernels_estep.hip, estep_plan(a).four_groups) since round 6; LC_ES_R4=0
     (test-hooks library) keeps three row groups per wave.  On inputs far beyond the oracle's reach the two must agree to
     rounding (one against two exponentials per entry: a few ulp in q) over three whole iterations -- both are held to the
     oracle at small sizes by the random-shape test above."""

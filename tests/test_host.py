@@ -65,8 +65,10 @@ def test_aux_hooks_constants_are_those_of_the_sources():
         assert len(m) == 1, (name, m)
         return int(m[0], 0)
 
-    for name in ("REDUCE_TMP_ELEMS", "SEL_ROWS", "GCS_SLICES", "BOUND_MAX_COLS", "BOUND_MAX_K", "QHASH_SEED"):
+    for name in ("REDUCE_TMP_ELEMS", "SEL_ROWS", "GCS_SLICES", "BOUND_MAX_COLS", "BOUND_MAX_K", "QHASH_SEED", "SS_BR"):
         assert const(name) == getattr(aux_hooks, name), name
+    assert "enum SuffstatRoute { SS_PER_CLUSTER = 0, SS_FEAT = 1, SS_QUAD = 2, SS_WIDE = 3 };" in text
+    assert "enum SuffstatMode { SS_DENSE = 0, SS_MASKED_DENSE = 1, SS_ZERO_SKIP = 2, SS_WORK_LIST = 3 };" in text
     assert const("QHASH_NONE") - (1 << 64) == aux_hooks.QHASH_NONE
     assert "if (tmp && nparts > 8192 && n <= REDUCE_TMP_ELEMS)" in text and "nparts > 512 && n <= 4096" in text
     assert "rows >= (int64_t)J * 65536" in text and "if (J > 1024)" in text  # the boundaries the test file names
