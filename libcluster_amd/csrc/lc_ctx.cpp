@@ -1215,9 +1215,10 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
     sspart_reserve((size_t)std::max(nrec, 1) * SS);
     if (extra > 0) ssext_.reserve((size_t)KR * SS);
     a.KR = KR;
-    // active width below the padded one: the feature-GEMM kernel never writes the record entries of the idle columns --
-    // they have to BE zero (every other Gauss-Wishart writer of this buffer stores zeros there; the separable families and
-    // the fused pass, which keep other layouts in it, mark it dirty)
+    // active width below the padded one: the feature-GEMM and the few-cluster kernels never write the record entries of the
+    // idle columns -- they have to BE zero (the per-cluster kernel stores zeros there, and an idle entry sits at the same
+    // offset of every record whatever K and the chunking; the separable families and the fused pass, which keep other
+    // layouts in the buffer, mark it dirty; tests/test_gpu_hot_kernels.py pins what each kernel leaves there)
     if (DC_ < DP_ && !sspart_clean_) {
       LC_HIP(hipMemsetAsync(sspart_.p, 0, sspart_.cap * sizeof(double), stream_));
       sspart_clean_ = true;

@@ -5,8 +5,8 @@
 // test comes back as -1 and a failed assertion, never as a memory fault.  Buffers marked "io" are uploaded as the
 // caller filled them (sentinels) and downloaded whole, so that a write outside the intended entries shows.
 // Python side: tests/aux_hooks.py; cases: tests/test_gpu_aux_kernels.py, tests/test_gpu_predict_kernels.py for the
-// launchers of lc_kernels_predict.hip and lc_kernels_topic.hip, and tests/test_gpu_launch_plans.py for the two launch plans
-// at the end of this file.
+// launchers of lc_kernels_predict.hip and lc_kernels_topic.hip, tests/test_gpu_launch_plans.py for the two launch plans, and
+// tests/test_gpu_hot_kernels.py for launch_estep, launch_suffstat (with launch_fold_extra) and launch_fused at the end of this file.
 #include <algorithm>
 #include <cstdio>
 #include <vector>
@@ -656,4 +656,221 @@ LC_HOOK lc_test_estep_refusal(int DP, int DC, int K, int raw, int sparse, i64 nr
   if (lck::estep_plan(a).ok) return -1;
   *grid = lck::estep_grid(a);
   return (int)lck::launch_estep(a, nullptr);
+}
+
+// ---- the hot path: E-step, statistics pass, fused pass (tests/test_gpu_hot_kernels.py) ---------------------------------------------
+namespace {
+
+// widths a Gauss-Wishart launch can have: the padded layouts, and for the narrow ones the active widths with an instance
+bool gw_width_ok(int DP, int DC) {
+  if (DP > 128) return DP % 64 == 0 && DP <= lck::GW_MAX_DP && (DC == 0 || DC == DP);
+  if (DP < 16 || lck::padded_dim(DP) != DP) return false;
+  return DC == 0 || DC == DP || (DP >= 32 && DC == DP - 8) || ((DP == 32 || DP == 48) && (DC == DP - 4 || DC == DP - 12));
+}
+constexpr size_t HOT_LDS_LIMIT = 160 * 1024;  // gfx950: LDS a workgroup can be granted
+constexpr i64 HOT_MAX_NRG = (i64)1 << 22;     // 64M rows: far beyond any test, keeps every product below 2^63
+
+}  // namespace
+
+// estep_plan itself: out [8] = ok, rows_per_block, grid, four_groups, DC, lq_lds, lds_bytes, estep_pstride(DP, DC) (-1 when !ok)
+LC_HOOK lc_test_estep_plan(int DP, int DC, int K, int raw, int sparse, i64 nrg, i64* out) {
+  if (!out || K < 1 || nrg < 1 || DP < 1 || DC < 0) return -1;
+  lck::EstepLaunch a{};
+  a.DP = DP;
+  a.DC = DC;
+  a.K = K;
+  a.raw = raw ? 1 : 0;
+  a.sparse = sparse ? 1 : 0;
+  a.nrg = nrg;
+  const lck::EstepPlan p = lck::estep_plan(a);
+  out[0] = p.ok ? 1 : 0, out[1] = p.rows_per_block, out[2] = p.grid, out[3] = p.four_groups ? 1 : 0, out[4] = p.DC;
+  out[5] = p.lq_lds, out[6] = (i64)p.lds_bytes;
+  out[7] = p.ok ? (i64)lck::estep_pstride(DP, p.DC) : -1;
+  return 0;
+}
+// X [nrg * 16 x DP]; params [K x estep_pstride(DP, DC)]; ctab [J x K]; rginfo [nrg] or null (then nrows, J = 1); qZ (io)
+// [Kbuf x ldq], Kbuf >= K, ldq >= nrg * 16; fz_part (io) [nfz >= grid]; ll_part (io) [nll >= grid * K] or null.  A launch
+// estep_plan refuses comes back as -1 (lc_test_estep_refusal hands those to the launcher, without buffers).
+LC_HOOK lc_test_estep(const double* X, int DP, int DC, i64 nrg, const double* params, const double* ctab, int J, const int* rginfo,
+                      i64 nrows, int K, int raw, int sparse, double* qZ, int Kbuf, i64 ldq, double* fz_part, i64 nfz, double* ll_part,
+                      i64 nll) {
+  if (!X || !params || !ctab || !qZ || !fz_part || K < 1 || K > 4096 || Kbuf < K || Kbuf > 8192 || J < 1 || J > (1 << 20)) return -1;
+  if (nrg < 1 || nrg > HOT_MAX_NRG || ldq < nrg * RG || !gw_width_ok(DP, DC)) return -1;
+  if (rginfo ? !rginfo_ok(rginfo, nrg, J) : (J != 1 || nrows < 0 || nrows > nrg * RG)) return -1;
+  lck::EstepLaunch a{};
+  a.DP = DP;
+  a.DC = DC;
+  a.K = K;
+  a.raw = raw ? 1 : 0;
+  a.sparse = sparse ? 1 : 0;
+  a.nrg = nrg;
+  a.nrows = nrows;
+  a.ldq = ldq;
+  const lck::EstepPlan p = lck::estep_plan(a);
+  if (!p.ok || p.grid < 1 || p.lds_bytes > HOT_LDS_LIMIT) return -1;
+  if (nfz < p.grid || (ll_part && nll < p.grid * K)) return -1;
+  Scope s;
+  a.X = s.in(X, (size_t)(nrg * RG) * DP);
+  a.params = s.in(params, (size_t)K * (size_t)lck::estep_pstride(DP, p.DC));
+  a.ctab = s.in(ctab, (size_t)J * K);
+  a.rginfo = rginfo ? s.in(rginfo, (size_t)nrg) : nullptr;
+  a.qZ = s.io(qZ, (size_t)Kbuf * (size_t)ldq);
+  a.fz_part = s.io(fz_part, (size_t)nfz);
+  a.ll_part = ll_part ? s.io(ll_part, (size_t)nll) : nullptr;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_estep(a, nullptr));
+}
+
+// rec (io) [nrec doubles >= (K + extra) * SS]: launch_fold_extra alone
+LC_HOOK lc_test_fold_extra(double* rec, i64 nrec, i64 SS, int K, int klast0, int extra) {
+  if (!rec || SS < 1 || SS > ((i64)1 << 24) || K < 1 || K > 4096 || klast0 < 0 || klast0 >= K || extra < 0 || extra > 4096) return -1;
+  if (nrec < (i64)(K + extra) * SS) return -1;
+  Scope s;
+  double* d = s.io(rec, (size_t)nrec);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_fold_extra(d, SS, K, klast0, extra, nullptr));
+}
+
+// One statistics pass as Context::suffstat runs it.  X [NP x DP]; qZ [K x ldq]; mode = SuffstatMode; rginfo [NP / 16] and
+// smask [J x K] with SS_MASKED_DENSE (optional with SS_ZERO_SKIP, absent otherwise); SS_WORK_LIST: nitems items as the
+// parallel arrays r0 / r1 / kofs / kcnt / rec0, klist [nklist], nrec records in all -- checked against what
+// Context::build_sparse_worklist produces and suffstat_kernel relies on: row ranges inside NP made of whole row groups,
+// 1 ... clusters_per_block clusters per item taken from klist, every cluster below K, the items' records disjoint and
+// inside the buffer.  partial (io) [npartial >= records * stat_stride(DP)].  plan_out [7] = suffstat_plan's numbers (route
+// first), computed here.  fold: the reductions Context::suffstat chains behind the pass (launch_reduce_partials, or
+// launch_reduce_records for a work list; launch_fold_extra when the plan has extra records) into folded (io) [nfolded >= K * SS].
+LC_HOOK lc_test_suffstat(const double* X, int DP, int DC, i64 NP, const double* qZ, int K, i64 ldq, int mode, const int* rginfo,
+                         const unsigned char* smask, int J, int nitems, const i64* r0, const i64* r1, const int* kofs, const int* kcnt,
+                         const i64* rec0, const int* klist, int nklist, int nrec_listed, int skip_listed, double* partial, i64 npartial,
+                         int fold, double* folded, i64 nfolded, i64* plan_out) {
+  if (!X || !qZ || !partial || !plan_out || K < 1 || K > 4096 || mode < 0 || mode > 3 || !gw_width_ok(DP, DC)) return -1;
+  if (NP < RG || NP % RG || NP > HOT_MAX_NRG * RG || ldq < NP || ldq % 2) return -1;  // (the quad and feature kernels read q in 16-byte pieces)
+  const lck::SuffstatMode m = (lck::SuffstatMode)mode;
+  const bool listed = m == lck::SS_WORK_LIST;
+  const bool masked = !listed && smask != nullptr;
+  if (m == lck::SS_DENSE && smask) return -1;
+  if (m == lck::SS_MASKED_DENSE && !smask) return -1;
+  if (masked && (!rginfo || J < 1 || J > (1 << 20) || !rginfo_ok(rginfo, NP / RG, J))) return -1;
+  if (fold && (!folded || nfolded < (i64)K * lck::stat_stride(DP))) return -1;
+  const lck::SuffstatPlan p = lck::suffstat_plan(DP, DC, NP, K, m);
+  plan_out[0] = p.route, plan_out[1] = p.nchunks, plan_out[2] = p.chunk_rows, plan_out[3] = p.extra, plan_out[4] = p.klast0;
+  plan_out[5] = p.KR, plan_out[6] = p.clusters_per_block;
+  if (p.nchunks < 1 || p.chunk_rows < lck::SS_BR || p.chunk_rows % lck::SS_BR || (i64)p.nchunks * p.chunk_rows < NP) return -1;
+  const i64 SS = lck::stat_stride(DP);
+  i64 nrec = (i64)p.nchunks * p.KR;
+  std::vector<lck::SSItem> items;
+  std::vector<int> kptr, krec;
+  if (listed) {
+    if (!r0 || !r1 || !kofs || !kcnt || !rec0 || !klist || nitems < 1 || nklist < 1 || nrec_listed < 1) return -1;
+    nrec = nrec_listed;
+    for (int t = 0; t < nklist; ++t)
+      if (klist[t] < 0 || klist[t] >= K) return -1;
+    std::vector<char> used((size_t)nrec, 0);
+    std::vector<std::vector<int>> recs((size_t)K);
+    for (int i = 0; i < nitems; ++i) {
+      if (r0[i] < 0 || r0[i] > r1[i] || r1[i] > NP || r0[i] % RG || r1[i] % RG) return -1;
+      if (kcnt[i] < 1 || kcnt[i] > p.clusters_per_block || kofs[i] < 0 || kofs[i] > nklist - kcnt[i]) return -1;
+      if (rec0[i] < 0 || rec0[i] > nrec - kcnt[i]) return -1;
+      for (int t = 0; t < kcnt[i]; ++t) {
+        if (used[(size_t)(rec0[i] + t)]) return -1;
+        used[(size_t)(rec0[i] + t)] = 1;
+        recs[(size_t)klist[kofs[i] + t]].push_back((int)(rec0[i] + t));
+      }
+      items.push_back(lck::SSItem{r0[i], r1[i], kofs[i], kcnt[i], rec0[i]});
+    }
+    kptr.assign((size_t)K + 1, 0);
+    for (int k = 0; k < K; ++k) {
+      krec.insert(krec.end(), recs[(size_t)k].begin(), recs[(size_t)k].end());
+      kptr[(size_t)k + 1] = (int)krec.size();
+    }
+  }
+  if (npartial < nrec * SS) return -1;
+  Scope s;
+  lck::SuffstatLaunch a{};
+  a.DP = DP;
+  a.DC = DC;
+  a.X = s.in(X, (size_t)NP * DP);
+  a.NP = NP;
+  a.qZ = s.in(qZ, (size_t)K * (size_t)ldq);
+  a.ldq = ldq;
+  a.K = K;
+  a.mode = m;
+  a.rginfo = masked ? s.in(rginfo, (size_t)(NP / RG)) : nullptr;
+  a.smask = masked ? s.in(smask, (size_t)J * K) : nullptr;
+  a.partial = s.io(partial, (size_t)npartial);
+  a.nchunks = p.nchunks;
+  a.KR = p.KR;
+  a.chunk_rows = p.chunk_rows;
+  const int* dkptr = nullptr;
+  const int* dkrec = nullptr;
+  if (listed) {
+    a.items = s.in(items.data(), items.size());
+    a.klist = s.in(klist, (size_t)nklist);
+    a.nitems = nitems;
+    a.skip_listed = skip_listed ? 1 : 0;
+    if (fold) {
+      dkptr = s.in(kptr.data(), kptr.size());
+      dkrec = s.in(krec.data(), krec.size());
+    }
+  }
+  double* dfold = fold ? s.io(folded, (size_t)nfolded) : nullptr;
+  double* ext = fold && !listed && p.extra > 0 ? s.scratch<double>((size_t)p.KR * (size_t)SS) : nullptr;
+  if (!s.ok()) return s.finish(hipSuccess);
+  hipError_t e = lck::launch_suffstat(a, p, nullptr);
+  if (e == hipSuccess && fold) {
+    if (listed) {
+      e = lck::launch_reduce_records(a.partial, SS, K, dkptr, dkrec, dfold, nullptr);
+    } else if (p.extra > 0) {
+      e = lck::launch_reduce_partials(a.partial, p.nchunks, (i64)p.KR * SS, ext, nullptr);
+      if (e == hipSuccess) e = lck::launch_fold_extra(ext, SS, K, p.klast0, p.extra, nullptr);
+      if (e == hipSuccess) e = hipMemcpyAsync(dfold, ext, (size_t)K * (size_t)SS * sizeof(double), hipMemcpyDeviceToDevice, nullptr);
+    } else {
+      e = lck::launch_reduce_partials(a.partial, p.nchunks, (i64)K * SS, dfold, nullptr);
+    }
+  }
+  return s.finish(e);
+}
+
+// out [4] = fused_eligible, fused_plan's grid, compute units of the device, fused_record(DP, K)
+LC_HOOK lc_test_fused_plan(int DP, i64 nrg, int K, i64* out) {
+  if (!out || K < 1 || K > 4096 || nrg < 0 || nrg > HOT_MAX_NRG || DP < 1 || DP > 1024) return -1;
+  out[0] = lck::fused_eligible(DP, K) ? 1 : 0;
+  out[1] = lck::fused_plan(DP, nrg, K);
+  out[2] = lck::current_device_cus();
+  out[3] = (i64)lck::fused_record(DP, K);
+  return 0;
+}
+// X [nrg * 16 x 16]; params [K x pstride(16)]; ctab [J x K]; rginfo [nrg] or null (then nrows, J = 1); grid: 0 = fused_plan's,
+// otherwise 1 <= grid <= fused_plan's (which never exceeds the number of 256-row tiles); qZ (io) [Kbuf x ldq]; partial (io)
+// [npartial >= grid x fused_record(16, K)]; *grid_used: the blocks launched
+LC_HOOK lc_test_fused(const double* X, int D, i64 nrg, const double* params, const double* ctab, int J, const int* rginfo, i64 nrows,
+                      int K, int want_ll, int grid, double* qZ, int Kbuf, i64 ldq, double* partial, i64 npartial, int* grid_used) {
+  const int DP = 16;
+  if (!X || !params || !ctab || !qZ || !partial || !grid_used || D < 1 || D > DP || K < 1 || Kbuf < K || Kbuf > 8192) return -1;
+  if (nrg < 1 || nrg > HOT_MAX_NRG || ldq < nrg * RG || J < 1 || J > (1 << 20) || !lck::fused_eligible(DP, K)) return -1;
+  if (rginfo ? !rginfo_ok(rginfo, nrg, J) : (J != 1 || nrows < 0 || nrows > nrg * RG)) return -1;
+  const int plan = lck::fused_plan(DP, nrg, K);
+  if (plan < 1 || grid < 0 || grid > plan) return -1;
+  const int g = grid ? grid : plan;
+  if (npartial < (i64)g * lck::fused_record(DP, K)) return -1;
+  *grid_used = g;
+  Scope s;
+  lck::FusedLaunch a{};
+  a.DP = DP;
+  a.D = D;
+  a.X = s.in(X, (size_t)(nrg * RG) * DP);
+  a.nrg = nrg;
+  a.rginfo = rginfo ? s.in(rginfo, (size_t)nrg) : nullptr;
+  a.nrows = nrows;
+  a.params = s.in(params, (size_t)K * (size_t)lck::pstride(DP));
+  a.ctab = s.in(ctab, (size_t)J * K);
+  a.K = K;
+  a.qZ = s.io(qZ, (size_t)Kbuf * (size_t)ldq);
+  a.ldq = ldq;
+  a.partial = s.io(partial, (size_t)npartial);
+  a.want_ll = want_ll != 0;
+  a.grid = g;
+  a.ngroups = J;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_fused(a, nullptr));
 }

@@ -37,6 +37,19 @@ HIP_ERROR_INVALID_VALUE = 1
 SS_BR = 32
 SS_ROUTES = ("per_cluster", "feat", "quad", "wide")            # SuffstatRoute, in the order of the enum
 SS_MODES = ("dense", "masked_dense", "zero_skip", "work_list")  # SuffstatMode
+# (lc_kernels.h, lc_kernels_fused.hip, lc_kernels_estep.hip: the hot path, tests/test_gpu_hot_kernels.py)
+FUSED_ROWS, FUSED_KMAX, FUSED_CT_CAP = 256, 16, 1024
+FUSED_YSHARE = 410  # per mille of a CU's tiles for its second block when the grid is two blocks per CU (launch_fused)
+ES_LQ_LDS_CAP = 80 * 1024
+WIDE_R, WIDE_WAVES, WIDE_CHUNK = 2, 4, 256 * 16 + 64
+
+
+def estep_cfg_r(DP):
+    return 4 if DP <= 48 else 3 if DP <= 96 else 2
+
+
+def estep_cfg_waves(DP):
+    return 4 if DP <= 96 else 8
 _M64 = (1 << 64) - 1
 
 _P, _I, _L, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_double
@@ -71,6 +84,12 @@ PROTOTYPES = {
     "lc_test_topic_infer": [_P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _I, _D, _I, _I, _L, _P, _P, _P, _P, _P],
     "lc_test_suffstat_plan": [_I, _I, _L, _I, _I, _P, _P],
     "lc_test_estep_refusal": [_I, _I, _I, _I, _I, _L, _P],
+    "lc_test_estep_plan": [_I, _I, _I, _I, _I, _L, _P],
+    "lc_test_estep": [_P, _I, _I, _L, _P, _P, _I, _P, _L, _I, _I, _I, _P, _I, _L, _P, _L, _P, _L],
+    "lc_test_fold_extra": [_P, _L, _L, _I, _I, _I],
+    "lc_test_suffstat": [_P, _I, _I, _L, _P, _I, _L, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _I, _P, _L, _P],
+    "lc_test_fused_plan": [_I, _L, _I, _P],
+    "lc_test_fused": [_P, _I, _L, _P, _P, _I, _P, _L, _I, _I, _I, _P, _I, _L, _P, _L, _P],
 }
 
 _lib = None
@@ -425,3 +444,75 @@ def estep_refusal(DP, DC, K, nrg, raw=False, sparse=False):
     grid = C.c_longlong(-7)
     rc = hooks().lc_test_estep_refusal(DP, DC, K, int(raw), int(sparse), nrg, C.addressof(grid))
     return rc, grid.value
+
+
+# ---- the hot path: E-step, statistics pass, fused pass (tests/test_gpu_hot_kernels.py) ----------------------------------------
+def estep_plan(DP, DC, K, nrg, raw=False, sparse=False):
+    """estep_plan of a launch as a dict: ok, rows_per_block, grid, four_groups, DC, lq_lds, lds_bytes, pstride"""
+    out = np.full(8, -7, dtype=i64)
+    rc = hooks().lc_test_estep_plan(DP, DC, K, int(raw), int(sparse), nrg, _p(out))
+    assert rc == 0, rc
+    return dict(zip(("ok", "rows_per_block", "grid", "four_groups", "DC", "lq_lds", "lds_bytes", "pstride"), (int(v) for v in out)))
+
+
+def estep(X, DC, params, ctab, K, qZ, fz_part, ll_part=None, rginfo=None, nrows=0, raw=False, sparse=False):
+    """X [nrg * 16 x DP]; params [K x pstride]; ctab [J x K]; qZ [Kbuf x ldq], fz_part, ll_part (or None) in place"""
+    X, pr, ct, rg = _a(X, f64), _a(params, f64), _a(ctab, f64), _a(rginfo, i32)
+    q, fz, ll = _io(qZ, f64), _io(fz_part, f64), _io(ll_part, f64)
+    NP, DP = X.shape
+    assert NP % 16 == 0 and ct.ndim == 2 and ct.shape[1] == K and pr.ndim == 2 and pr.shape[0] == K
+    assert rg is None or rg.size == NP // 16
+    return hooks().lc_test_estep(_p(X), DP, DC, NP // 16, _p(pr), _p(ct), ct.shape[0], _p(rg), int(nrows), K, int(raw), int(sparse),
+                                 _p(q), q.shape[0], q.shape[1], _p(fz), fz.size, _p(ll), 0 if ll is None else ll.size)
+
+
+def fold_extra(rec, SS, K, klast0, extra):
+    """rec (flat, in place): launch_fold_extra alone"""
+    rec = _io(rec, f64)
+    return hooks().lc_test_fold_extra(_p(rec), rec.size, SS, K, klast0, extra)
+
+
+def suffstat(X, DC, qZ, K, mode, partial, rginfo=None, smask=None, items=None, klist=None, nrec=0, skip_listed=False,
+             folded=None):
+    """One statistics pass.  X [NP x DP]; qZ [K x ldq]; partial (flat) and folded (flat, or None: no fold) in place; items: a
+    list of (r0, r1, kofs, kcnt, rec0) for mode "work_list".  -> status, the plan as suffstat_plan() returns it (without name)"""
+    X, q, rg, sm = _a(X, f64), _a(qZ, f64), _a(rginfo, i32), _a(smask, u8)
+    part, fo = _io(partial, f64), _io(folded, f64)
+    NP, DP = X.shape
+    assert q.shape[0] == K and (sm is None or (sm.ndim == 2 and sm.shape[1] == K)) and (rg is None or rg.size == NP // 16)
+    it = [None] * 5
+    kl = _a(klist, i32)
+    if items is not None:
+        cols = list(zip(*items))
+        it = [_a(cols[0], i64), _a(cols[1], i64), _a(cols[2], i32), _a(cols[3], i32), _a(cols[4], i64)]
+    out = np.full(7, -7, dtype=i64)
+    rc = hooks().lc_test_suffstat(_p(X), DP, DC, NP, _p(q), K, q.shape[1], SS_MODES.index(mode), _p(rg), _p(sm),
+                                  0 if sm is None else sm.shape[0], 0 if items is None else len(items), _p(it[0]), _p(it[1]),
+                                  _p(it[2]), _p(it[3]), _p(it[4]), _p(kl), 0 if kl is None else kl.size, int(nrec),
+                                  int(skip_listed), _p(part), part.size, int(fo is not None), _p(fo), 0 if fo is None else fo.size,
+                                  _p(out))
+    keys = ("route", "nchunks", "chunk_rows", "extra", "klast0", "KR", "clusters_per_block")
+    d = dict(zip(keys, (int(v) for v in out)), mode=mode)
+    d["route"] = SS_ROUTES[d["route"]] if 0 <= d["route"] < 4 else None
+    return rc, d
+
+
+def fused_plan(nrg, K, DP=16):
+    """-> dict: eligible, grid (fused_plan), cus, record (fused_record)"""
+    out = np.full(4, -7, dtype=i64)
+    rc = hooks().lc_test_fused_plan(DP, nrg, K, _p(out))
+    assert rc == 0, rc
+    return dict(zip(("eligible", "grid", "cus", "record"), (int(v) for v in out)))
+
+
+def fused(X, D, params, ctab, K, qZ, partial, want_ll=False, grid=0, rginfo=None, nrows=0):
+    """X [nrg * 16 x 16]; qZ [Kbuf x ldq] and partial (flat) in place -> status, blocks launched"""
+    X, pr, ct, rg = _a(X, f64), _a(params, f64), _a(ctab, f64), _a(rginfo, i32)
+    q, part = _io(qZ, f64), _io(partial, f64)
+    NP, DP = X.shape
+    assert DP == 16 and NP % 16 == 0 and ct.ndim == 2 and ct.shape[1] == K and pr.shape[0] == K
+    assert rg is None or rg.size == NP // 16
+    g = C.c_int(-7)
+    rc = hooks().lc_test_fused(_p(X), D, NP // 16, _p(pr), _p(ct), ct.shape[0], _p(rg), int(nrows), K, int(want_ll), grid, _p(q),
+                               q.shape[0], q.shape[1], _p(part), part.size, C.addressof(g))
+    return rc, g.value

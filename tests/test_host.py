@@ -85,6 +85,20 @@ def test_aux_hooks_constants_are_those_of_the_sources():
     assert "default: hipLaunchKernelGGL((predict_diag_kernel<MODE, 0>)" in text
     assert "a.DP % PRED_RENORM != 0" in text
     assert "x[g][s] = c < a.Da ? a.X[(size_t)xrow[g] * a.DP + c] : c == a.Da ? 1.0 : 0.0;" in text  # the ones column
+    # the hot path (tests/test_gpu_hot_kernels.py): tile and table sizes of the fused pass, the instances of the E-step
+    text = "".join((csrc / f).read_text() for f in ("lc_kernels.h", "lc_kernels_fused.hip", "lc_kernels_estep.hip"))
+    for name in ("FUSED_ROWS", "FUSED_KMAX", "FUSED_CT_CAP", "SS_BR"):
+        assert const(name) == getattr(aux_hooks, name), name
+    assert "constexpr int WIDE_R = 2, WIDE_WAVES = 4;" in text and (aux_hooks.WIDE_R, aux_hooks.WIDE_WAVES) == (2, 4)
+    assert "constexpr int WIDE_CHUNK = 256 * 16 + 64;" in text and aux_hooks.WIDE_CHUNK == 256 * 16 + 64
+    assert "constexpr size_t ES_LQ_LDS_CAP = 80 * 1024;" in text and aux_hooks.ES_LQ_LDS_CAP == 80 * 1024
+    assert "constexpr int estep_cfg_r(int DP) { return DP <= 48 ? 4 : DP <= 96 ? 3 : 2; }" in text
+    assert "constexpr int estep_cfg_waves(int DP) { return DP <= 96 ? 4 : 8; }" in text
+    assert [aux_hooks.estep_cfg_r(d) for d in (16, 48, 64, 96, 112, 128)] == [4, 4, 3, 3, 2, 2]
+    assert [aux_hooks.estep_cfg_waves(d) for d in (16, 96, 112, 128)] == [4, 4, 8, 8]
+    assert 'atoi(test_switch("LC_FUSED_YSHARE")) : 410;' in text and aux_hooks.FUSED_YSHARE == 410
+    assert "a.yshare = a.grid == 2 * cus ? ys : 0;" in text
+    assert "(DP == 64 || DP == 80) && !a.sparse && a.K >= 6 && lq_fits(4, 4)" in text  # K = 6: where the four-row-group instance starts
     # the workgroup size the API picks, which lc_test_topic_infer restates for threads = 0
     pick = "maxN <= 64 ? 64 : maxN <= 128 ? 128 : 256;"
     assert pick in (csrc / "lc_topic_predict.cpp").read_text() and pick in (csrc / "lc_testhooks.hip").read_text()
