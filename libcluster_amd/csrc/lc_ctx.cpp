@@ -1954,26 +1954,11 @@ void Context::estep_diag(int K, const double* av, const double* w2, const double
     bool use = nw > 0 && force != 0;
     std::vector<double> muv((size_t)DP, 0.0);
     if (use && mode != 2) {
-      double cond = 0.0;
-      for (int d = 0; d < D; ++d) {
-        double m = 0.0;
-        for (int k = 0; k < K; ++k) m += av[(size_t)k * D + d];
-        m /= K;
-        muv[(size_t)d] = m;
-        double wmax = 0.0, reach = 0.0;
-        for (int k = 0; k < K; ++k) {
-          const double w = std::fabs(w2[(size_t)k * D + d]);
-          wmax = std::max(wmax, w);
-          const double sig = w > 0 ? std::sqrt(0.5 / w) : 0.0;
-          reach = std::max(reach, std::fabs(av[(size_t)k * D + d] - m) + 6.0 * sig);
-        }
-        cond = std::max(cond, wmax * reach * reach);
-      }
+      const double cond = lck::estep_diag_centre(D, DP, K, mode, av, w2, muv.data());
       if (!(cond <= 4096.0) && force != 1) use = false;  // (NaN-safe)
     }
     if (use) {
       if (timing_) times_.estep_diag_mfma_calls += 1;
-      const int NT = DP / 4, NTF = mode == 2 ? NT : 2 * NT, KT = (K + 3) / 4;
       const size_t base = hpack_.size();
       mu_off = base;
       ck_off = mu_off + (size_t)DP;
@@ -1990,34 +1975,7 @@ void Context::estep_diag(int K, const double* av, const double* w2, const double
         std::copy(w1 + (size_t)k * D, w1 + (size_t)(k + 1) * D, P + (size_t)2 * K * DP);
       }
       std::copy(muv.begin(), muv.end(), hpack_.begin() + mu_off);
-      double* ck = hpack_.data() + ck_off;
-      double* wt = hpack_.data() + wt_off;
-      std::fill(ck, ck + K + 1, 0.0);
-      std::fill(wt, wt + nw, 0.0);
-      // W[k][f]: f < NT*4 quadratic weights (w2), then linear weights (w1 - 2 w2 a'); tile (it, jt) element
-      // (lo, hh) = W[4 it + lo][column 16 q + jr + 4 hh of its half], jt = 4 q + jr: the kernel's column groups (a lane
-      // holds four contiguous columns per sixteen)
-      auto put = [&](int k, int f, double v) {
-        const int it = k >> 2, lo = k & 3, half = f / DP, d = f % DP;
-        const int jt = half * NT + 4 * (d / 16) + (d % 4), hh = (d % 16) / 4;
-        wt[((size_t)it * NTF + jt) * 16 + lo + 4 * hh] = v;
-      };
-      (void)KT;
-      for (int k = 0; k < K; ++k) {
-        double cs = 0.0;
-        for (int d = 0; d < D; ++d) {
-          const double a2 = w2[(size_t)k * D + d], a1 = w1[(size_t)k * D + d];
-          const double ac = av[(size_t)k * D + d] - muv[(size_t)d];
-          if (mode == 2) {
-            put(k, d, a1);
-          } else {
-            put(k, d, a2);
-            put(k, DP + d, a1 - 2.0 * a2 * ac);
-            cs += a2 * ac * ac + a1 * muv[(size_t)d];
-          }
-        }
-        ck[k] = cs;
-      }
+      lck::estep_diag_pack(D, DP, K, mode, av, w2, w1, muv.data(), hpack_.data() + ck_off, hpack_.data() + wt_off, nw);
     }
   }
   params_.reserve(hpack_.size());
@@ -2192,4 +2150,59 @@ const char* test_switch(const char* name) {
   return nullptr;
 #endif
 }
+
+// ---- the packed operands of the matrix-pipe E-step of the separable families (estep_diag_mfma_kernel) ----
+// centre = the mean of the cluster centres; the figure that decides the path: max_d max_k |w2_kd| reach_d^2, reach_d = the
+// farthest 6-sigma edge of any cluster from the centre
+double estep_diag_centre(int D, int DP, int K, int mode, const double* av, const double* w2, double* muv) {
+  std::fill(muv, muv + DP, 0.0);
+  if (mode == 2) return 0.0;
+  double cond = 0.0;
+  for (int d = 0; d < D; ++d) {
+    double m = 0.0;
+    for (int k = 0; k < K; ++k) m += av[(size_t)k * D + d];
+    m /= K;
+    muv[(size_t)d] = m;
+    double wmax = 0.0, reach = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const double w = std::fabs(w2[(size_t)k * D + d]);
+      wmax = std::max(wmax, w);
+      const double sig = w > 0 ? std::sqrt(0.5 / w) : 0.0;
+      reach = std::max(reach, std::fabs(av[(size_t)k * D + d] - m) + 6.0 * sig);
+    }
+    cond = std::max(cond, wmax * reach * reach);
+  }
+  return cond;
+}
+
+void estep_diag_pack(int D, int DP, int K, int mode, const double* av, const double* w2, const double* w1, const double* muv,
+                     double* ck, double* wt, int64_t nw) {
+  const int NT = DP / 4, NTF = mode == 2 ? NT : 2 * NT;
+  std::fill(ck, ck + K + 1, 0.0);
+  std::fill(wt, wt + nw, 0.0);
+  // W[k][f]: f < NT*4 quadratic weights (w2), then linear weights (w1 - 2 w2 a'); tile (it, jt) element
+  // (lo, hh) = W[4 it + lo][column 16 q + jr + 4 hh of its half], jt = 4 q + jr: the kernel's column groups (a lane
+  // holds four contiguous columns per sixteen)
+  auto put = [&](int k, int f, double v) {
+    const int it = k >> 2, lo = k & 3, half = f / DP, d = f % DP;
+    const int jt = half * NT + 4 * (d / 16) + (d % 4), hh = (d % 16) / 4;
+    wt[((size_t)it * NTF + jt) * 16 + lo + 4 * hh] = v;
+  };
+  for (int k = 0; k < K; ++k) {
+    double cs = 0.0;
+    for (int d = 0; d < D; ++d) {
+      const double a2 = w2[(size_t)k * D + d], a1 = w1[(size_t)k * D + d];
+      const double ac = av[(size_t)k * D + d] - muv[(size_t)d];
+      if (mode == 2) {
+        put(k, d, a1);
+      } else {
+        put(k, d, a2);
+        put(k, DP + d, a1 - 2.0 * a2 * ac);
+        cs += a2 * ac * ac + a1 * muv[(size_t)d];
+      }
+    }
+    ck[k] = cs;
+  }
+}
+
 }  // namespace lck

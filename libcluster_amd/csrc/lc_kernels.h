@@ -327,7 +327,40 @@ struct DiagEstepLaunch {
 constexpr int EDM_CT_CAP = 1024;
 inline int64_t estep_diag_grid(int64_t nrg) { return (nrg * RG + 63) / 64; }
 int64_t estep_diag_mfma_weights(int DP, int K, int mode);
+// ONE decision per launch, taken by estep_diag_plan and switched on by launch_estep_diag: a function of DP, K, mode, nrg,
+// raw, ngroups and of which of wt / rginfo / ll_part are set (the pointers themselves are not followed).
+// instance of estep_diag_mfma_kernel: generic (raw or LL_k, or K > 32), plain (the VBEM iterations', the table c_jk read
+// from global memory), tabled (the table waits in LDS), one-group (no row-group table at all)
+enum DiagEstepInstance { EDI_NONE = 0, EDI_GENERIC = 1, EDI_PLAIN = 2, EDI_TABLED = 3, EDI_ONEGROUP = 4 };
+struct DiagEstepPlan {
+  bool ok;           // false: no instance serves this launch (launch_estep_diag returns hipErrorInvalidValue)
+  bool mfma;         // the matrix-pipe kernel (wt set)
+  int mode;          // 0 / 1 / 2 as the kernels see it
+  int64_t grid;      // blocks launched (0: nothing to run)
+  size_t lds_bytes;  // dynamic LDS of the launch
+  const char* name;  // the kernel a profiler will list
+  // difference-form VALU kernels
+  bool wide;         // estep_diag_wide_kernel (DP > 128)
+  int KT;            // clusters per tile
+  bool REG;          // log q~ stays in registers
+  // matrix-pipe kernel
+  int NT;            // 4-column feature tiles per half (DP / 4)
+  bool QUAD;         // the quadratic half of the features too (mode != 2)
+  int R, KTM;        // row groups per wave; cluster tiles kept in registers (0: per-lane LDS slots, any K)
+  int instance;      // DiagEstepInstance
+  int64_t nslots;    // partial slots the kernel fills or zeroes (estep_diag_grid)
+  int per_cu;        // resident blocks per compute unit the grid is sized by
+  int64_t block_cap; // compute units x per_cu: the most blocks a launch gets (more tiles: several tiles per block)
+};
+DiagEstepPlan estep_diag_plan(const DiagEstepLaunch& a);
 hipError_t launch_estep_diag(const DiagEstepLaunch& a, hipStream_t stream);
+// The packed operands of the matrix-pipe path (host; Context::estep_diag).  a / w2 / w1: [K x D].
+// estep_diag_centre: mu [DP] = the mean of the cluster centres (pad columns and mode 2: zero); returns the conditioning
+// figure max_d max_k |w2_kd| reach_d^2 (0 in mode 2) that decides between the two paths.
+// estep_diag_pack: constk [K + 1] and the weight tiles wt [estep_diag_mfma_weights(DP, K, mode)] around that centre.
+double estep_diag_centre(int D, int DP, int K, int mode, const double* a, const double* w2, double* mu);
+void estep_diag_pack(int D, int DP, int K, int mode, const double* a, const double* w2, const double* w1, const double* mu,
+                     double* constk, double* wt, int64_t nw);
 
 struct DiagStatLaunch {
   int DP;
@@ -346,6 +379,21 @@ struct DiagStatLaunch {
   int ldx = 0, col0 = 0, DPT = 0;  // ditto: row stride of X, first column and total padded width (wide D)
 };
 int suffstat_diag_rsplit(int K);
+// ONE decision per statistics pass of the separable families (launch_suffstat_diag switches on it)
+struct DiagStatPlan {
+  bool ok;             // false: no instance for this width
+  int nslice, rsplit;  // blocks per row chunk (64 clusters each); row classes = partial records per chunk
+  int second;
+  int nblocks;         // launches: 1, or (DP > 128) one per block of 128 columns ...
+  int width, last_width;  // ... of `width` columns each, the last one of `last_width` (128 or 64)
+  // of the launch that owns the first column (the one that writes N_k) / of the last column block
+  int BR, BR_last;           // rows staged per batch
+  bool nstage, nstage_last;  // N_k summed where q is staged: the records of the row classes >= 1 carry N_k = 0
+  bool deep, deep_last;      // two batches in flight
+  size_t lds_bytes;          // of the first launch
+  const char* name;
+};
+DiagStatPlan suffstat_diag_plan(int DP, int K, int second);
 hipError_t launch_suffstat_diag(const DiagStatLaunch& a, hipStream_t stream);
 
 // ---- split-search data passes (partobs / splitobs / auglabels on the device) ----

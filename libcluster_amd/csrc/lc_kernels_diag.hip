@@ -881,81 +881,78 @@ static size_t edm_lds_bytes(int NT, int NTF, int KT, int R, bool slots, bool tab
           (table ? EDM_CT_CAP : 0) + 64) * sizeof(double);
 }
 
-template <int NT, bool QUAD, int R, int KTM>
-static hipError_t launch_edm_k(const DiagEstepLaunch& a, hipStream_t stream) {
-  const int KT = (a.K + 3) / 4, NTF = QUAD ? 2 * NT : NT;
-  size_t shmem = edm_lds_bytes(NT, NTF, KT, R, KTM == 0);
+// row groups per wave by the register budget (R x NTF feature fragments of two registers each): two sets of R x NT
+// fragments live (current tile, next tile in flight)
+constexpr int edm_r(int NT) { return NT <= 16 ? 2 : 1; }
+constexpr int EDM_KTM = 8;                       // cluster tiles the register instances hold: K <= 4 EDM_KTM
+constexpr size_t EDM_LDS_LIMIT = 150 * 1024;     // what a block of the matrix-pipe kernel may ask for
+constexpr size_t EDM_LDS_TWO_BLOCKS = 80 * 1024; // up to here two blocks are resident per compute unit
 #ifndef LC_EDM_PLAIN_QUAD
 #define LC_EDM_PLAIN_QUAD 1  // (with unconditional stores the plain instance wins for both: linear features 10 %, with the quadratic half 6.5 %; it lost 4 % there before)
 #endif
-  const bool plain = KTM > 0 && !a.raw && !a.ll_part && (!QUAD || LC_EDM_PLAIN_QUAD);
-  const bool onegrp = plain && !a.rginfo;
-  const bool tabled = plain && a.rginfo && (int64_t)a.ngroups * a.K <= EDM_CT_CAP &&
-                      edm_lds_bytes(NT, NTF, KT, R, KTM == 0, true) <= 150 * 1024;
-  if (tabled) shmem = edm_lds_bytes(NT, NTF, KT, R, KTM == 0, true);
+
+template <int NT, bool QUAD, int R, int KTM>
+static hipError_t launch_edm_k(const DiagEstepLaunch& a, const DiagEstepPlan& p, hipStream_t stream) {
   if (!a.sink) return hipErrorInvalidValue;
+  const bool onegrp = p.instance == EDI_ONEGROUP, tabled = p.instance == EDI_TABLED, plain = p.instance != EDI_GENERIC;
   auto kern = onegrp   ? estep_diag_mfma_kernel<NT, QUAD, R, KTM, (KTM > 0), (KTM > 0 ? 0 : 2)>
               : tabled ? estep_diag_mfma_kernel<NT, QUAD, R, KTM, (KTM > 0), (KTM > 0 ? 1 : 2)>
               : plain  ? estep_diag_mfma_kernel<NT, QUAD, R, KTM, (KTM > 0)>
                        : estep_diag_mfma_kernel<NT, QUAD, R, KTM>;
   static LdsGrant grants[4];
-  if (hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(kern), shmem, grants[onegrp ? 3 : tabled ? 2 : plain ? 1 : 0]);
+  if (hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(kern), p.lds_bytes, grants[onegrp ? 3 : tabled ? 2 : plain ? 1 : 0]);
       e != hipSuccess)
     return e;
-  const int64_t ntile = (a.nrg + 4 * R - 1) / (4 * R);
-  const int64_t nslots = estep_diag_grid(a.nrg);
-  const int cus = current_device_cus();
-  // persistent blocks (the weights are staged once per block): as many as are resident, a few tiles each
-  const int per_cu = shmem <= 80 * 1024 ? 2 : 1;
-  int64_t grid = std::min<int64_t>(std::min<int64_t>(ntile, nslots), (int64_t)cus * per_cu);
-  if (grid <= 0) return hipSuccess;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), shmem, stream, a.X, a.wt, a.mu, a.constk, a.ctab, a.rginfo,
-                     a.qZ, a.fz_part, a.ll_part, a.K, a.nrg, a.nrows, a.ldq, a.raw, nslots, a.sink, a.ngroups);
+  if (p.grid <= 0) return hipSuccess;
+  hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(256), p.lds_bytes, stream, a.X, a.wt, a.mu, a.constk, a.ctab, a.rginfo,
+                     a.qZ, a.fz_part, a.ll_part, a.K, a.nrg, a.nrows, a.ldq, a.raw, p.nslots, a.sink, a.ngroups);
   return hipGetLastError();
 }
 
 template <int NT, bool QUAD>
-static hipError_t launch_edm_q(const DiagEstepLaunch& a, hipStream_t stream) {
-  // row groups per wave by the register budget (R x NTF feature fragments of two registers each)
-  constexpr int R = NT <= 16 ? 2 : 1;  // two sets of R x NT fragments live (current tile, next tile in flight)
-  if (a.K <= 32) return launch_edm_k<NT, QUAD, R, 8>(a, stream);
-  return launch_edm_k<NT, QUAD, R, 0>(a, stream);
+static hipError_t launch_edm_q(const DiagEstepLaunch& a, const DiagEstepPlan& p, hipStream_t stream) {
+  constexpr int R = edm_r(NT);
+  if (p.R != R) return hipErrorInvalidValue;
+  if (p.KTM == EDM_KTM) return launch_edm_k<NT, QUAD, R, EDM_KTM>(a, p, stream);
+  return launch_edm_k<NT, QUAD, R, 0>(a, p, stream);
 }
 
 template <int NT>
-static hipError_t launch_edm_t(const DiagEstepLaunch& a, hipStream_t stream) {
-  return a.mode == 2 ? launch_edm_q<NT, false>(a, stream) : launch_edm_q<NT, true>(a, stream);
+static hipError_t launch_edm_t(const DiagEstepLaunch& a, const DiagEstepPlan& p, hipStream_t stream) {
+  return p.QUAD ? launch_edm_q<NT, true>(a, p, stream) : launch_edm_q<NT, false>(a, p, stream);
 }
 
 // doubles of the packed weight tiles lc_ctx.cpp uploads for the matrix-pipe path; 0: this shape has no such path
 int64_t estep_diag_mfma_weights(int DP, int K, int mode) {
   if (DP > 128 || DP % 16 || K < 1) return 0;
   const int NT = DP / 4, NTF = mode == 2 ? NT : 2 * NT, KT = (K + 3) / 4;
-  const int R = NT <= 16 ? 2 : 1;
+  const int R = edm_r(NT);
   // the weights of all clusters, every lane's split-ordering sums and (K > 32) its log q~ slots must fit in the CU's LDS
-  if (edm_lds_bytes(NT, NTF, KT, R, K > 32) > 150 * 1024) return 0;
+  if (edm_lds_bytes(NT, NTF, KT, R, K > 4 * EDM_KTM) > EDM_LDS_LIMIT) return 0;
   return (int64_t)KT * NTF * 16;
 }
 
-static hipError_t launch_estep_diag_mfma(const DiagEstepLaunch& a, hipStream_t stream) {
-  switch (a.DP) {
-    case 16: return launch_edm_t<4>(a, stream);
-    case 32: return launch_edm_t<8>(a, stream);
-    case 48: return launch_edm_t<12>(a, stream);
-    case 64: return launch_edm_t<16>(a, stream);
-    case 80: return launch_edm_t<20>(a, stream);
-    case 96: return launch_edm_t<24>(a, stream);
-    case 112: return launch_edm_t<28>(a, stream);
-    case 128: return launch_edm_t<32>(a, stream);
+static hipError_t launch_estep_diag_mfma(const DiagEstepLaunch& a, const DiagEstepPlan& p, hipStream_t stream) {
+  switch (p.NT) {
+    case 4: return launch_edm_t<4>(a, p, stream);
+    case 8: return launch_edm_t<8>(a, p, stream);
+    case 12: return launch_edm_t<12>(a, p, stream);
+    case 16: return launch_edm_t<16>(a, p, stream);
+    case 20: return launch_edm_t<20>(a, p, stream);
+    case 24: return launch_edm_t<24>(a, p, stream);
+    case 28: return launch_edm_t<28>(a, p, stream);
+    case 32: return launch_edm_t<32>(a, p, stream);
   }
   return hipErrorInvalidValue;
 }
 
 template <int MODE, int KT, bool REG>
-static hipError_t launch_ed_t(const DiagEstepLaunch& a, int64_t grid, size_t shmem, hipStream_t stream) {
-  auto kern = a.DP > 128 ? estep_diag_wide_kernel<MODE, KT, REG> : estep_diag_kernel<MODE, KT, REG>;
+static hipError_t launch_ed_t(const DiagEstepLaunch& a, const DiagEstepPlan& p, hipStream_t stream) {
+  const int64_t grid = p.grid;
+  const size_t shmem = p.lds_bytes;
+  auto kern = p.wide ? estep_diag_wide_kernel<MODE, KT, REG> : estep_diag_kernel<MODE, KT, REG>;
   static LdsGrant grants[2];  // per kernel (narrow, wide)
-  if (hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(kern), shmem, grants[a.DP > 128 ? 1 : 0]); e != hipSuccess)
+  if (hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(kern), shmem, grants[p.wide ? 1 : 0]); e != hipSuccess)
     return e;
   const double* PA = a.params;
   const double* PW2 = PA + (int64_t)a.K * a.DP;
@@ -966,27 +963,71 @@ static hipError_t launch_ed_t(const DiagEstepLaunch& a, int64_t grid, size_t shm
 }
 
 template <int MODE>
-static hipError_t launch_ed_m(const DiagEstepLaunch& a, int64_t grid, size_t shmem, hipStream_t stream) {
-  // clusters per tile: every wave should have work (K >= 4*KT), registers hold 4*DIAG_MAXT*KT columns
-  if (a.K <= 4) return launch_ed_t<MODE, 1, true>(a, grid, shmem, stream);
-  if (a.K <= 8) return launch_ed_t<MODE, 2, true>(a, grid, shmem, stream);
-  if (a.K <= 4 * DIAG_MAXT * 4) return launch_ed_t<MODE, 4, true>(a, grid, shmem, stream);
-  return launch_ed_t<MODE, 4, false>(a, grid, shmem, stream);
+static hipError_t launch_ed_m(const DiagEstepLaunch& a, const DiagEstepPlan& p, hipStream_t stream) {
+  if (p.KT == 1 && p.REG) return launch_ed_t<MODE, 1, true>(a, p, stream);
+  if (p.KT == 2 && p.REG) return launch_ed_t<MODE, 2, true>(a, p, stream);
+  if (p.KT == 4 && p.REG) return launch_ed_t<MODE, 4, true>(a, p, stream);
+  if (p.KT == 4) return launch_ed_t<MODE, 4, false>(a, p, stream);
+  return hipErrorInvalidValue;
+}
+
+DiagEstepPlan estep_diag_plan(const DiagEstepLaunch& a) {
+  DiagEstepPlan p{};
+  p.ok = true;
+  p.mfma = a.wt != nullptr;
+  p.name = p.mfma ? "estep_diag_mfma_kernel" : a.DP > 128 ? "estep_diag_wide_kernel" : "estep_diag_kernel";
+  p.nslots = estep_diag_grid(a.nrg);
+  const int64_t rows_grid = (a.nrg * RG + 63) / 64;
+  if (rows_grid <= 0) return p;  // nothing to run (grid = 0), whatever the rest says
+  if (!p.mfma) {
+    p.mode = a.mode == 1 ? 1 : a.mode == 2 ? 2 : 0;
+    p.grid = rows_grid;
+    p.wide = a.DP > 128;
+    const int DC = a.DP < 128 ? a.DP : 128;
+    p.lds_bytes = (size_t)(64 * (DC + 1) + 256 + a.K) * sizeof(double);
+    // clusters per tile: every wave should have work (K >= 4*KT), registers hold 4*DIAG_MAXT*KT columns
+    p.KT = a.K <= 4 ? 1 : a.K <= 8 ? 2 : 4;
+    p.REG = a.K <= 4 * DIAG_MAXT * 4;
+    return p;
+  }
+  p.mode = a.mode;
+  if (a.DP < 16 || a.DP > 128 || a.DP % 16) {
+    p.ok = false;
+    return p;
+  }
+  p.NT = a.DP / 4;
+  p.QUAD = a.mode != 2;
+  p.R = edm_r(p.NT);
+  p.KTM = a.K <= 4 * EDM_KTM ? EDM_KTM : 0;
+  const int KT = (a.K + 3) / 4, NTF = p.QUAD ? 2 * p.NT : p.NT;
+  p.lds_bytes = edm_lds_bytes(p.NT, NTF, KT, p.R, p.KTM == 0);
+  const bool plain = p.KTM > 0 && !a.raw && !a.ll_part && (!p.QUAD || LC_EDM_PLAIN_QUAD);
+  const bool onegrp = plain && !a.rginfo;
+  const bool tabled = plain && a.rginfo && (int64_t)a.ngroups * a.K <= EDM_CT_CAP &&
+                      edm_lds_bytes(p.NT, NTF, KT, p.R, p.KTM == 0, true) <= EDM_LDS_LIMIT;
+  if (tabled) p.lds_bytes = edm_lds_bytes(p.NT, NTF, KT, p.R, p.KTM == 0, true);
+  p.instance = onegrp ? EDI_ONEGROUP : tabled ? EDI_TABLED : plain ? EDI_PLAIN : EDI_GENERIC;
+  const int64_t ntile = (a.nrg + 4 * p.R - 1) / (4 * p.R);
+  // persistent blocks (the weights are staged once per block): as many as are resident, a few tiles each
+  p.per_cu = p.lds_bytes <= EDM_LDS_TWO_BLOCKS ? 2 : 1;
+  p.block_cap = (int64_t)current_device_cus() * p.per_cu;
+  p.grid = std::min<int64_t>(std::min<int64_t>(ntile, p.nslots), p.block_cap);
+  if (p.grid < 0) p.grid = 0;
+  return p;
 }
 
 hipError_t launch_estep_diag(const DiagEstepLaunch& a, hipStream_t stream) {
-  const int64_t grid = (a.nrg * RG + 63) / 64;
-  if (grid <= 0) return hipSuccess;
-  if (a.wt) return launch_estep_diag_mfma(a, stream);
-  const int DC = a.DP < 128 ? a.DP : 128;
-  const size_t shmem = (size_t)(64 * (DC + 1) + 256 + a.K) * sizeof(double);
-  switch (a.mode) {
+  const DiagEstepPlan p = estep_diag_plan(a);
+  if (!p.ok) return hipErrorInvalidValue;
+  if (p.nslots <= 0) return hipSuccess;
+  if (p.mfma) return launch_estep_diag_mfma(a, p, stream);
+  switch (p.mode) {
     case 1:
-      return launch_ed_m<1>(a, grid, shmem, stream);
+      return launch_ed_m<1>(a, p, stream);
     case 2:
-      return launch_ed_m<2>(a, grid, shmem, stream);
+      return launch_ed_m<2>(a, p, stream);
     default:
-      return launch_ed_m<0>(a, grid, shmem, stream);
+      return launch_ed_m<0>(a, p, stream);
   }
 }
 
@@ -1004,6 +1045,11 @@ hipError_t launch_estep_diag(const DiagEstepLaunch& a, hipStream_t stream) {
 // X batches (BR rows) and the slice's q columns are staged through LDS, next batch in flight in registers,
 // the same scheme as suffstat_kernel.
 constexpr int SD_QMAX = 64;  // clusters per block
+// per instance, shared by the kernel and by suffstat_diag_plan: rows staged per batch; two batches in flight; N_k summed
+// where q is staged (see the kernel)
+__host__ __device__ constexpr int sd_br(int DP) { return DP <= 64 ? 32 : 16; }
+__host__ __device__ constexpr bool sd_deep(int DP) { return DP <= 96; }
+__host__ __device__ constexpr bool sd_nstage(int DP, int RS) { return DP <= 96 && !(DP >= 64 && RS == 1); }
 // RS (row classes: 1, 2 or 4) is a template parameter so that a wave's steps of a batch are a compile-time list: the
 // operands of its next step (NB x fragments, CT q fragments) are read while the current step's MFMAs issue (fenced;
 // hipcc reads them right in front of their use otherwise, and every step of 32 MFMAs started with an exposed LDS round
@@ -1011,7 +1057,7 @@ constexpr int SD_QMAX = 64;  // clusters per block
 template <int DP, bool SECOND, int RS>
 __global__ void __launch_bounds__(256, 2) suffstat_diag_kernel(DiagStatLaunch a) {
   constexpr int NB = DP / 16, CT = 4;
-  constexpr int BR = DP <= 64 ? 32 : 16;
+  constexpr int BR = sd_br(DP);
   constexpr int LD = lds_row_stride(DP), XBUF = BR * LD;
   constexpr int NV2 = BR * DP / 2, NPRE = (NV2 + 255) / 256;   // double2 per thread and batch
   constexpr int QCAP = SD_QMAX / RS;                           // clusters a block with RS row classes can hold (suffstat_diag_rsplit)
@@ -1044,7 +1090,7 @@ __global__ void __launch_bounds__(256, 2) suffstat_diag_kernel(DiagStatLaunch a)
   // trip under load, so the kernel sat at 3.8 TB/s waiting for its single batch.  Set (b & 1) now receives batch b + 2
   // while batch b is multiplied out of LDS and batch b + 1 moves from the other set into the other LDS buffer; the batch
   // loop is unrolled twice so that set and buffer are compile-time names (registers, not scratch).
-  constexpr bool DEEP = DP <= 96;
+  constexpr bool DEEP = sd_deep(DP);
   constexpr int NSET = DEEP ? 2 : 1, AHEAD = DEEP ? 2 : 1;
   double pre[NSET][NPRE][2], qpre[NSET][NQ];
   // N_k is summed where q is staged (NQ adds per thread and batch) and not next to the MFMAs, where the A fragment is
@@ -1052,7 +1098,7 @@ __global__ void __launch_bounds__(256, 2) suffstat_diag_kernel(DiagStatLaunch a)
   // the fp64 VALU's price in matrix-pipe time (16 of a wave's 48 non-MFMA fp64 instructions per batch at D = 64)
   // (where NQ more registers would spill -- a block of more than 32 clusters at D >= 64, D >= 112 -- the sum stays in the
   //  step loop)
-  constexpr bool NSTAGE = DP <= 96 && !(DP >= 64 && RS == 1);
+  constexpr bool NSTAGE = sd_nstage(DP, RS);
   double nq[NSTAGE ? NQ : 1], nacc[NSTAGE ? 1 : CT];
 #pragma unroll
   for (int i = 0; i < (NSTAGE ? NQ : 1); ++i) nq[i] = 0.0;
@@ -1287,6 +1333,10 @@ __global__ void __launch_bounds__(256, 2) suffstat_diag_kernel(DiagStatLaunch a)
   }
 }
 
+static size_t sd_lds_bytes(int DP) {
+  return (size_t)(2 * sd_br(DP) * lds_row_stride(DP) + 2 * SD_QMAX * (sd_br(DP) + 4)) * sizeof(double);
+}
+
 int suffstat_diag_rsplit(int K) {  // row classes per block: waves left over by the cluster groups split the rows
   const int groups = ((K < SD_QMAX ? K : SD_QMAX) + 15) / 16;
   return groups >= 3 ? 1 : groups == 2 ? 2 : 4;
@@ -1294,8 +1344,7 @@ int suffstat_diag_rsplit(int K) {  // row classes per block: waves left over by 
 
 template <int DP, int RS>
 static hipError_t launch_sd_r(const DiagStatLaunch& a, hipStream_t stream) {
-  constexpr int BR = DP <= 64 ? 32 : 16;
-  const size_t shmem = (size_t)(2 * BR * lds_row_stride(DP) + 2 * SD_QMAX * (BR + 4)) * sizeof(double);
+  const size_t shmem = sd_lds_bytes(DP);
   static LdsGrant grants[2];
   if (hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(suffstat_diag_kernel<DP, true, RS>), shmem, grants[0]);
       e != hipSuccess)
@@ -1315,19 +1364,40 @@ static hipError_t launch_sd_t(const DiagStatLaunch& a, hipStream_t stream) {
   return a.rsplit == 1 ? launch_sd_r<DP, 1>(a, stream) : a.rsplit == 2 ? launch_sd_r<DP, 2>(a, stream) : launch_sd_r<DP, 4>(a, stream);
 }
 
+DiagStatPlan suffstat_diag_plan(int DP, int K, int second) {
+  DiagStatPlan p{};
+  p.second = second ? 1 : 0;
+  p.name = "suffstat_diag_kernel";
+  if (K < 1 || DP < 16 || (DP <= 128 ? DP % 16 : DP % 64)) return p;  // (ok = false)
+  p.ok = true;
+  p.nslice = (K + SD_QMAX - 1) / SD_QMAX;
+  p.rsplit = suffstat_diag_rsplit(K);
+  // wide observations: one launch per block of 128 columns (q is re-read; X is read once in total); the width is a
+  // multiple of 64, so the last block may be a half one
+  p.nblocks = DP > 128 ? (DP + 127) / 128 : 1;
+  p.width = DP > 128 ? 128 : DP;
+  p.last_width = DP > 128 ? (DP % 128 ? 64 : 128) : DP;
+  p.BR = sd_br(p.width), p.BR_last = sd_br(p.last_width);
+  p.nstage = sd_nstage(p.width, p.rsplit), p.nstage_last = sd_nstage(p.last_width, p.rsplit);
+  p.deep = sd_deep(p.width), p.deep_last = sd_deep(p.last_width);
+  p.lds_bytes = sd_lds_bytes(p.width);
+  return p;
+}
+
 hipError_t launch_suffstat_diag(const DiagStatLaunch& a0, hipStream_t stream) {
   if (a0.K <= 0 || a0.nchunks <= 0) return hipSuccess;
   if (a0.chunk_rows % 32) return hipErrorInvalidValue;
+  const DiagStatPlan p = suffstat_diag_plan(a0.DP, a0.K, a0.second);
+  if (!p.ok) return hipErrorInvalidValue;
   DiagStatLaunch a = a0;
-  a.nslice = (a.K + SD_QMAX - 1) / SD_QMAX;
-  a.rsplit = suffstat_diag_rsplit(a.K);
+  a.nslice = p.nslice;
+  a.rsplit = p.rsplit;
   a.ldx = a0.DP;
   a.DPT = a0.DP;
-  if (a0.DP > 128) {  // wide observations: one launch per block of 128 columns (q is re-read; X is read once in total)
-    if (a0.DP % 64) return hipErrorInvalidValue;
-    for (int c0 = 0; c0 < a0.DP; c0 += 128) {
-      a.col0 = c0;
-      a.DP = a0.DP - c0 < 128 ? 64 : 128;  // (a multiple of 64: the last block may be a half one)
+  if (p.nblocks > 1) {
+    for (int b = 0; b < p.nblocks; ++b) {
+      a.col0 = b * p.width;
+      a.DP = b + 1 < p.nblocks ? p.width : p.last_width;
       hipError_t e = a.DP == 128 ? launch_sd_t<128>(a, stream) : launch_sd_t<64>(a, stream);
       if (e != hipSuccess) return e;
     }

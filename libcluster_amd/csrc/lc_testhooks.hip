@@ -6,7 +6,8 @@
 // caller filled them (sentinels) and downloaded whole, so that a write outside the intended entries shows.
 // Python side: tests/aux_hooks.py; cases: tests/test_gpu_aux_kernels.py, tests/test_gpu_predict_kernels.py for the
 // launchers of lc_kernels_predict.hip and lc_kernels_topic.hip, tests/test_gpu_launch_plans.py for the two launch plans, and
-// tests/test_gpu_hot_kernels.py for launch_estep, launch_suffstat (with launch_fold_extra) and launch_fused at the end of this file.
+// tests/test_gpu_hot_kernels.py for launch_estep, launch_suffstat (with launch_fold_extra) and launch_fused, and
+// tests/test_gpu_diag_kernels.py for launch_estep_diag, launch_suffstat_diag and the host packer at the end of this file.
 #include <algorithm>
 #include <cstdio>
 #include <vector>
@@ -874,3 +875,153 @@ LC_HOOK lc_test_fused(const double* X, int D, i64 nrg, const double* params, con
   if (!s.ok()) return s.finish(hipSuccess);
   return s.finish(lck::launch_fused(a, nullptr));
 }
+
+// ---- the separable families: E-step (both paths) and statistics pass (tests/test_gpu_diag_kernels.py) ------------------------------
+namespace {
+
+bool diag_width_ok(int DP) { return DP >= 16 && (DP <= 128 ? DP % 16 == 0 : (DP % 64 == 0 && DP <= 1024)); }
+
+void diag_estep_plan_out(const lck::DiagEstepPlan& p, i64* out, char* name) {
+  out[0] = p.ok ? 1 : 0, out[1] = p.mfma ? 1 : 0, out[2] = p.mode, out[3] = p.grid, out[4] = (i64)p.lds_bytes;
+  out[5] = p.wide ? 1 : 0, out[6] = p.KT, out[7] = p.REG ? 1 : 0, out[8] = p.NT, out[9] = p.QUAD ? 1 : 0, out[10] = p.R;
+  out[11] = p.KTM, out[12] = p.instance, out[13] = p.nslots, out[14] = p.per_cu, out[15] = p.block_cap;
+  if (name) snprintf(name, 32, "%s", p.name ? p.name : "");
+}
+void diag_stat_plan_out(const lck::DiagStatPlan& p, i64* out, char* name) {
+  out[0] = p.ok ? 1 : 0, out[1] = p.nslice, out[2] = p.rsplit, out[3] = p.second, out[4] = p.nblocks, out[5] = p.width;
+  out[6] = p.last_width, out[7] = p.BR, out[8] = p.BR_last, out[9] = p.nstage ? 1 : 0, out[10] = p.nstage_last ? 1 : 0;
+  out[11] = p.deep ? 1 : 0, out[12] = p.deep_last ? 1 : 0, out[13] = (i64)p.lds_bytes;
+  if (name) snprintf(name, 32, "%s", p.name ? p.name : "");
+}
+constexpr int DIAG_SINK = 256, DIAG_SINK_GUARD = 64;
+
+}  // namespace
+
+// estep_diag_plan itself, of a launch described by numbers alone (mfma / want_ll / grouped: whether wt / ll_part / rginfo
+// would be set): out [16] = ok, mfma, mode, grid, lds_bytes, wide, KT, REG, NT, QUAD, R, KTM, instance, nslots, per_cu,
+// block_cap; name [32].  The matrix-pipe plan asks the device for its compute units.
+LC_HOOK lc_test_estep_diag_plan(int DP, int K, int mode, i64 nrg, int mfma, int raw, int want_ll, int grouped, int ngroups,
+                                i64* out, char* name) {
+  if (!out || !name || K < 1 || K > 4096 || nrg < 0 || nrg > HOT_MAX_NRG || DP < 1 || DP > 1024 || mode < 0 || mode > 2 || ngroups < 1)
+    return -1;
+  static double some;
+  static int somei;
+  lck::DiagEstepLaunch a{};
+  a.DP = DP, a.D = DP, a.K = K, a.mode = mode, a.nrg = nrg, a.raw = raw ? 1 : 0, a.ngroups = ngroups;
+  a.wt = mfma ? &some : nullptr;
+  a.ll_part = want_ll ? &some : nullptr;
+  a.rginfo = grouped ? &somei : nullptr;
+  diag_estep_plan_out(lck::estep_diag_plan(a), out, name);
+  return 0;
+}
+// One launch_estep_diag.  X [nrg * 16 x DP]; params [3][K][DP] (a, w2, w1); ctab [J x K]; rginfo [nrg] or null (then nrows,
+// J = 1); wt null: the difference-form kernels; otherwise wt [nwt = estep_diag_mfma_weights(DP, K, mode) > 0], mu [DP]
+// (mode 2: may be null), constk [K] and sink (io) [256 + 64 guard doubles].  qZ (io) [Kbuf x ldq]; fz_part (io) [nfz >=
+// estep_diag_grid(nrg)]; ll_part (io) [nll >= estep_diag_grid(nrg) x K] or null.  plan_out [16] / name [32] as
+// lc_test_estep_diag_plan.  A launch whose dynamic LDS exceeds what a workgroup can be granted is refused here.
+LC_HOOK lc_test_estep_diag(const double* X, int DP, i64 nrg, const double* params, int mode, const double* ctab, int J,
+                           const int* rginfo, i64 nrows, int K, int raw, const double* wt, i64 nwt, const double* mu,
+                           const double* constk, double* qZ, int Kbuf, i64 ldq, double* fz_part, i64 nfz, double* ll_part, i64 nll,
+                           double* sink, i64* plan_out, char* name) {
+  if (!X || !params || !ctab || !qZ || !fz_part || !plan_out || !name || K < 1 || K > 4096 || Kbuf < K || Kbuf > 8192) return -1;
+  if (J < 1 || J > (1 << 20) || mode < 0 || mode > 2 || nrg < 1 || nrg > HOT_MAX_NRG || nrg * RG > ldq) return -1;
+  if (!diag_width_ok(DP)) return -1;
+  if (rginfo ? !rginfo_ok(rginfo, nrg, J) : (J != 1 || nrows < 0 || nrows > nrg * RG)) return -1;
+  if (wt) {
+    const i64 nw = lck::estep_diag_mfma_weights(DP, K, mode);
+    if (nw <= 0 || nwt != nw || !constk || !sink || (mode != 2 && !mu)) return -1;
+  } else if (nwt != 0 || mu || constk || sink) {
+    return -1;
+  }
+  lck::DiagEstepLaunch a{};
+  a.DP = DP, a.D = DP, a.K = K, a.mode = mode, a.nrg = nrg, a.nrows = nrows, a.raw = raw ? 1 : 0, a.ngroups = J, a.ldq = ldq;
+  static double some;
+  a.wt = wt ? &some : nullptr;
+  a.ll_part = ll_part ? &some : nullptr;
+  a.rginfo = rginfo;
+  const lck::DiagEstepPlan p = lck::estep_diag_plan(a);
+  diag_estep_plan_out(p, plan_out, name);
+  if (!p.ok || p.grid < 1 || p.grid > p.nslots || p.lds_bytes > HOT_LDS_LIMIT) return -1;
+  if (nfz < p.nslots || (ll_part && nll < p.nslots * K)) return -1;
+  Scope s;
+  a.X = s.in(X, (size_t)(nrg * RG) * DP);
+  a.params = s.in(params, (size_t)3 * K * DP);
+  a.ctab = s.in(ctab, (size_t)J * K);
+  a.rginfo = rginfo ? s.in(rginfo, (size_t)nrg) : nullptr;
+  a.qZ = s.io(qZ, (size_t)Kbuf * (size_t)ldq);
+  a.fz_part = s.io(fz_part, (size_t)nfz);
+  a.ll_part = ll_part ? s.io(ll_part, (size_t)nll) : nullptr;
+  a.wt = nullptr;
+  if (wt) {
+    a.wt = s.in(wt, (size_t)nwt);
+    std::vector<double> zero((size_t)DP, 0.0);
+    a.mu = s.in(mu ? mu : zero.data(), (size_t)DP);
+    a.constk = s.in(constk, (size_t)K);
+    a.sink = s.io(sink, (size_t)(DIAG_SINK + DIAG_SINK_GUARD));
+  }
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_estep_diag(a, nullptr));
+}
+
+// suffstat_diag_plan itself: out [14] = ok, nslice, rsplit, second, nblocks, width, last_width, BR, BR_last, nstage,
+// nstage_last, deep, deep_last, lds_bytes; name [32]
+LC_HOOK lc_test_suffstat_diag_plan(int DP, int K, int second, i64* out, char* name) {
+  if (!out || !name) return -1;
+  diag_stat_plan_out(lck::suffstat_diag_plan(DP, K, second), out, name);
+  return 0;
+}
+// One launch_suffstat_diag.  X [NP x DP]; qZ [K x ldq]; rginfo [NP / 16] and smask [J x K] together or neither; partial (io)
+// [npartial >= nchunks x rsplit x K x (1 + 2 DP)]; fold: the launch_reduce_partials Context::suffstat_diag chains behind
+// it, into folded (io) [nfolded >= K x (1 + 2 DP)].  plan_out [14] as lc_test_suffstat_diag_plan.
+LC_HOOK lc_test_suffstat_diag(const double* X, int DP, i64 NP, const double* qZ, int K, i64 ldq, const int* rginfo,
+                              const unsigned char* smask, int J, int nchunks, i64 chunk_rows, int second, double* partial,
+                              i64 npartial, int fold, double* folded, i64 nfolded, i64* plan_out) {
+  if (!X || !qZ || !partial || !plan_out || K < 1 || K > 4096 || !diag_width_ok(DP)) return -1;
+  if (NP < RG || NP % RG || NP > HOT_MAX_NRG * RG || ldq < NP) return -1;
+  if (nchunks < 1 || chunk_rows < 32 || chunk_rows % 32 || chunk_rows > HOT_MAX_NRG * RG) return -1;
+  if (!((i64)(nchunks - 1) * chunk_rows < NP && NP <= (i64)nchunks * chunk_rows)) return -1;
+  if ((smask != nullptr) != (rginfo != nullptr)) return -1;
+  if (smask && (J < 1 || J > (1 << 20) || !rginfo_ok(rginfo, NP / RG, J))) return -1;
+  const lck::DiagStatPlan p = lck::suffstat_diag_plan(DP, K, second);
+  diag_stat_plan_out(p, plan_out, nullptr);
+  if (!p.ok || p.lds_bytes > HOT_LDS_LIMIT) return -1;
+  const i64 SS = 1 + 2 * (i64)DP;
+  const i64 nparts = (i64)nchunks * p.rsplit;
+  if (npartial < nparts * K * SS || nparts > (1 << 24)) return -1;
+  if (fold && (!folded || nfolded < (i64)K * SS)) return -1;
+  Scope s;
+  lck::DiagStatLaunch a{};
+  a.DP = DP;
+  a.X = s.in(X, (size_t)NP * DP);
+  a.NP = NP;
+  a.qZ = s.in(qZ, (size_t)K * (size_t)ldq);
+  a.ldq = ldq;
+  a.K = K;
+  a.rginfo = smask ? s.in(rginfo, (size_t)(NP / RG)) : nullptr;
+  a.smask = smask ? s.in(smask, (size_t)J * K) : nullptr;
+  a.partial = s.io(partial, (size_t)npartial);
+  a.nchunks = nchunks;
+  a.chunk_rows = chunk_rows;
+  a.second = second ? 1 : 0;
+  double* dfold = fold ? s.io(folded, (size_t)nfolded) : nullptr;
+  if (!s.ok()) return s.finish(hipSuccess);
+  hipError_t e = lck::launch_suffstat_diag(a, nullptr);
+  if (e == hipSuccess && fold) e = lck::launch_reduce_partials(a.partial, (int)nparts, (i64)K * SS, dfold, nullptr);
+  return s.finish(e);
+}
+
+// The host packer of the matrix-pipe path (no device): a / w2 / w1 [K x D] -> mu [DP], constk [K + 1], wt [nwt =
+// estep_diag_mfma_weights(DP, K, mode) > 0], *cond (estep_diag_centre's figure)
+LC_HOOK lc_test_diag_pack(int D, int DP, int K, int mode, const double* a_, const double* w2, const double* w1, double* mu,
+                          double* constk, double* wt, i64 nwt, double* cond) {
+  if (!a_ || !w2 || !w1 || !mu || !constk || !wt || !cond || K < 1 || K > 4096 || mode < 0 || mode > 2) return -1;
+  if (D < 1 || D > DP || DP > 128 || DP % 16) return -1;
+  const i64 nw = lck::estep_diag_mfma_weights(DP, K, mode);
+  if (nw <= 0 || nwt != nw) return -1;
+  *cond = lck::estep_diag_centre(D, DP, K, mode, a_, w2, mu);
+  lck::estep_diag_pack(D, DP, K, mode, a_, w2, w1, mu, constk, wt, nw);
+  return 0;
+}
+
+// estep_diag_mfma_weights itself (no device)
+LC_HOOK lc_test_diag_weights(int DP, int K, int mode) { return (int)lck::estep_diag_mfma_weights(DP, K, mode); }

@@ -2,7 +2,7 @@
 (libcluster_amd/csrc/lc_testhooks.hip): one launcher of lc_kernels_aux.hip, lc_kernels_predict.hip or lc_kernels_topic.hip per
 call, on host arrays, and the two launch plans (tests/test_gpu_launch_plans.py).  A plain helper module of
 tests/test_gpu_aux_kernels.py and tests/test_gpu_predict_kernels.py (and of the symbol test in tests/test_host.py); no
-fixtures, no pytest hooks.
+fixtures, no pytest hooks.  The launchers of lc_kernels_diag.hip (tests/test_gpu_diag_kernels.py) are at the end.
 
 Every wrapper returns the hook's status first (0, -1 = refused by the host-side validation, or a HIP error code); arrays
 the caller passes as destinations are uploaded as they are and overwritten with what the device left in them."""
@@ -90,6 +90,12 @@ PROTOTYPES = {
     "lc_test_suffstat": [_P, _I, _I, _L, _P, _I, _L, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _I, _P, _L, _P],
     "lc_test_fused_plan": [_I, _L, _I, _P],
     "lc_test_fused": [_P, _I, _L, _P, _P, _I, _P, _L, _I, _I, _I, _P, _I, _L, _P, _L, _P],
+    "lc_test_estep_diag_plan": [_I, _I, _I, _L, _I, _I, _I, _I, _I, _P, _P],
+    "lc_test_estep_diag": [_P, _I, _L, _P, _I, _P, _I, _P, _L, _I, _I, _P, _L, _P, _P, _P, _I, _L, _P, _L, _P, _L, _P, _P, _P],
+    "lc_test_suffstat_diag_plan": [_I, _I, _I, _P, _P],
+    "lc_test_suffstat_diag": [_P, _I, _L, _P, _I, _L, _P, _P, _I, _I, _L, _I, _P, _L, _I, _P, _L, _P],
+    "lc_test_diag_pack": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P],
+    "lc_test_diag_weights": [_I, _I, _I],
 }
 
 _lib = None
@@ -516,3 +522,88 @@ def fused(X, D, params, ctab, K, qZ, partial, want_ll=False, grid=0, rginfo=None
     rc = hooks().lc_test_fused(_p(X), D, NP // 16, _p(pr), _p(ct), ct.shape[0], _p(rg), int(nrows), K, int(want_ll), grid, _p(q),
                                q.shape[0], q.shape[1], _p(part), part.size, C.addressof(g))
     return rc, g.value
+
+
+# ---- the separable families: lc_kernels_diag.hip (tests/test_gpu_diag_kernels.py, tests/test_diag_refs_host.py) ------------------
+DIAG_SINK, DIAG_SINK_GUARD = 256, 64
+EDI_NAMES = ("none", "generic", "plain", "tabled", "one_group")  # DiagEstepInstance, in the order of the enum
+_EDP_KEYS = ("ok", "mfma", "mode", "grid", "lds_bytes", "wide", "KT", "REG", "NT", "QUAD", "R", "KTM", "instance", "nslots", "per_cu",
+             "block_cap")
+_SDP_KEYS = ("ok", "nslice", "rsplit", "second", "nblocks", "width", "last_width", "BR", "BR_last", "nstage", "nstage_last", "deep",
+             "deep_last", "lds_bytes")
+
+
+def _edp(out, name):
+    d = dict(zip(_EDP_KEYS, (int(v) for v in out)), name=name.value.decode())
+    d["instance"] = EDI_NAMES[d["instance"]] if 0 <= d["instance"] < len(EDI_NAMES) else None
+    return d
+
+
+def estep_diag_plan(DP, K, mode, nrg, mfma, raw=False, want_ll=False, grouped=False, ngroups=1):
+    """estep_diag_plan of a launch described by numbers alone, as a dict (instance by name).  The matrix-pipe plan needs a device."""
+    out = np.full(16, -7, dtype=i64)
+    name = C.create_string_buffer(32)
+    rc = hooks().lc_test_estep_diag_plan(DP, K, mode, nrg, int(mfma), int(raw), int(want_ll), int(grouped), ngroups, _p(out),
+                                         C.addressof(name))
+    assert rc == 0, rc
+    return _edp(out, name)
+
+
+def estep_diag(X, params, mode, ctab, K, qZ, fz_part, ll_part=None, rginfo=None, nrows=0, raw=False, wt=None, mu=None, constk=None,
+               sink=None):
+    """One launch_estep_diag.  X [nrg * 16 x DP]; params [3][K][DP]; ctab [J x K]; qZ [Kbuf x ldq], fz_part, ll_part (or None), sink
+    ([DIAG_SINK + DIAG_SINK_GUARD], with wt) in place; wt None: the difference-form kernels.  -> status, the plan"""
+    X, pr, ct, rg = _a(X, f64), _a(params, f64), _a(ctab, f64), _a(rginfo, i32)
+    wt, mu, ck = _a(wt, f64), _a(mu, f64), _a(constk, f64)
+    q, fz, ll, sk = _io(qZ, f64), _io(fz_part, f64), _io(ll_part, f64), _io(sink, f64)
+    NP, DP = X.shape
+    assert NP % 16 == 0 and ct.ndim == 2 and ct.shape[1] == K and pr.shape == (3, K, DP)
+    assert rg is None or rg.size == NP // 16
+    assert mu is None or mu.size == DP
+    assert ck is None or ck.size >= K
+    assert sk is None or sk.size == DIAG_SINK + DIAG_SINK_GUARD
+    out = np.full(16, -7, dtype=i64)
+    name = C.create_string_buffer(32)
+    rc = hooks().lc_test_estep_diag(_p(X), DP, NP // 16, _p(pr), mode, _p(ct), ct.shape[0], _p(rg), int(nrows), K, int(raw), _p(wt),
+                                    0 if wt is None else wt.size, _p(mu), _p(ck), _p(q), q.shape[0], q.shape[1], _p(fz), fz.size,
+                                    _p(ll), 0 if ll is None else ll.size, _p(sk), _p(out), C.addressof(name))
+    return rc, _edp(out, name)
+
+
+def suffstat_diag_plan(DP, K, second):
+    out = np.full(14, -7, dtype=i64)
+    name = C.create_string_buffer(32)
+    rc = hooks().lc_test_suffstat_diag_plan(DP, K, int(second), _p(out), C.addressof(name))
+    assert rc == 0, rc
+    return dict(zip(_SDP_KEYS, (int(v) for v in out)), name=name.value.decode())
+
+
+def suffstat_diag(X, qZ, K, nchunks, chunk_rows, second, partial, rginfo=None, smask=None, folded=None, NP=None):
+    """One launch_suffstat_diag.  X [NP x DP]; qZ [K x ldq]; partial (flat) and folded (flat, or None: no fold) in place.
+    -> status, the plan (without name)"""
+    X, q, rg, sm = _a(X, f64), _a(qZ, f64), _a(rginfo, i32), _a(smask, u8)
+    part, fo = _io(partial, f64), _io(folded, f64)
+    NP = X.shape[0] if NP is None else NP
+    DP = X.shape[1]
+    assert q.shape[0] == K and (sm is None or (sm.ndim == 2 and sm.shape[1] == K)) and (rg is None or rg.size == NP // 16)
+    out = np.full(14, -7, dtype=i64)
+    rc = hooks().lc_test_suffstat_diag(_p(X), DP, NP, _p(q), K, q.shape[1], _p(rg), _p(sm), 0 if sm is None else sm.shape[0],
+                                       nchunks, chunk_rows, int(second), _p(part), part.size, int(fo is not None), _p(fo),
+                                       0 if fo is None else fo.size, _p(out))
+    return rc, dict(zip(_SDP_KEYS, (int(v) for v in out)))
+
+
+def diag_weights(DP, K, mode):
+    """estep_diag_mfma_weights (no device)"""
+    return hooks().lc_test_diag_weights(DP, K, mode)
+
+
+def diag_pack(a, w2, w1, DP, mode):
+    """the host packer of Context::estep_diag (no device): a / w2 / w1 [K x D] -> status, mu [DP], constk [K], wt, cond"""
+    a, w2, w1 = _a(a, f64), _a(w2, f64), _a(w1, f64)
+    K, D = a.shape
+    nw = max(diag_weights(DP, K, mode), 0)
+    mu, ck, wt = np.full(DP, np.nan), np.full(K + 1, np.nan), np.full(nw, np.nan)
+    cond = C.c_double(np.nan)
+    rc = hooks().lc_test_diag_pack(D, DP, K, mode, _p(a), _p(w2), _p(w1), _p(mu), _p(ck), _p(wt), nw, C.addressof(cond))
+    return rc, mu, ck[:K], wt, cond.value

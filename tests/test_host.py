@@ -44,6 +44,9 @@ def test_test_hooks_live_in_the_hooks_library_only(lib):
     assert not [s for s in shipped if s.startswith("lc_test_")]
     declared = set(aux_hooks.PROTOTYPES)
     assert len(declared) >= 27 and declared <= hooked, sorted(declared - hooked)
+    # the launchers of lc_kernels_diag.hip (tests/test_gpu_diag_kernels.py) and the host packer of their matrix-pipe operands
+    assert {"lc_test_estep_diag_plan", "lc_test_estep_diag", "lc_test_suffstat_diag_plan", "lc_test_suffstat_diag", "lc_test_diag_pack",
+            "lc_test_diag_weights"} <= declared and len(declared) >= 41
     assert {s for s in hooked if s.startswith("lc_test_")} == declared  # no hook without a prototype either
     assert {s for s in shipped if s.startswith("lc_")} == {s for s in hooked if s.startswith("lc_")} - declared
     h = aux_hooks.hooks()  # loads, and every prototype binds
@@ -99,6 +102,26 @@ def test_aux_hooks_constants_are_those_of_the_sources():
     assert 'atoi(test_switch("LC_FUSED_YSHARE")) : 410;' in text and aux_hooks.FUSED_YSHARE == 410
     assert "a.yshare = a.grid == 2 * cus ? ys : 0;" in text
     assert "(DP == 64 || DP == 80) && !a.sparse && a.K >= 6 && lq_fits(4, 4)" in text  # K = 6: where the four-row-group instance starts
+    # the separable families (tests/test_gpu_diag_kernels.py, tests/diag_refs.py): tile counts, caps and LDS limits of lc_kernels_diag.hip
+    import diag_refs
+
+    text = "".join((csrc / f).read_text() for f in ("lc_kernels.h", "lc_kernels_diag.hip"))
+    for name in ("DIAG_MAXT", "SD_QMAX", "EDM_CT_CAP", "EDM_KTM"):
+        assert const(name) == getattr(diag_refs, name), name
+    assert "constexpr size_t EDM_LDS_LIMIT = 150 * 1024;" in text and diag_refs.EDM_LDS_LIMIT == 150 * 1024
+    assert "constexpr size_t EDM_LDS_TWO_BLOCKS = 80 * 1024;" in text and diag_refs.EDM_LDS_TWO_BLOCKS == 80 * 1024
+    assert "p.per_cu = p.lds_bytes <= EDM_LDS_TWO_BLOCKS ? 2 : 1;" in text
+    assert "if (edm_lds_bytes(NT, NTF, KT, R, K > 4 * EDM_KTM) > EDM_LDS_LIMIT) return 0;" in text
+    assert "constexpr int edm_r(int NT) { return NT <= 16 ? 2 : 1; }" in text  # R = NT <= 16 ? 2 : 1
+    assert [diag_refs.edm_r(nt) for nt in (4, 16, 20, 32)] == [2, 2, 1, 1]
+    assert "constexpr int sd_br(int DP) { return DP <= 64 ? 32 : 16; }" in text and (diag_refs.sd_br(64), diag_refs.sd_br(80)) == (32, 16)
+    assert "constexpr bool sd_nstage(int DP, int RS) { return DP <= 96 && !(DP >= 64 && RS == 1); }" in text
+    assert "constexpr bool sd_deep(int DP) { return DP <= 96; }" in text
+    assert "p.KT = a.K <= 4 ? 1 : a.K <= 8 ? 2 : 4;" in text and "p.REG = a.K <= 4 * DIAG_MAXT * 4;" in text
+    assert "enum DiagEstepInstance { EDI_NONE = 0, EDI_GENERIC = 1, EDI_PLAIN = 2, EDI_TABLED = 3, EDI_ONEGROUP = 4 };" in text
+    assert diag_refs.EDI == aux_hooks.EDI_NAMES == ("none", "generic", "plain", "tabled", "one_group")
+    assert "constexpr int DIAG_SINK = 256, DIAG_SINK_GUARD = 64;" in (csrc / "lc_testhooks.hip").read_text()
+    assert (aux_hooks.DIAG_SINK, aux_hooks.DIAG_SINK_GUARD) == (256, 64)
     # the workgroup size the API picks, which lc_test_topic_infer restates for threads = 0
     pick = "maxN <= 64 ? 64 : maxN <= 128 ? 128 : 256;"
     assert pick in (csrc / "lc_topic_predict.cpp").read_text() and pick in (csrc / "lc_testhooks.hip").read_text()
