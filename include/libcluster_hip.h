@@ -193,6 +193,18 @@ int lc_ctx_set_sharding(lc_ctx* ctx, int whole_groups);
  * reference's `sparse` mode, whose point is to leave massless (group, cluster) pairs out (cluster.cpp:67-79). */
 int lc_ctx_set_skip_zero(lc_ctx* ctx, int on);
 
+/* Statistics pass, feature-GEMM kernel (dense passes at 32 <= D <= 128 and more than 12 clusters): leave out every
+ * (4-row step, cluster quad) pair whose sixteen responsibilities are all below 2^-300.  Once the posteriors have
+ * sharpened that is most of the pass.  A statistic loses at most N * 2^-300 * max |x_u x_w| in absolute terms; NaN
+ * responsibilities are kept.  A probe of qZ in front of every such pass (a fixed, strided sample of 4-row steps: a
+ * deterministic function of qZ) sends the pass to the dense kernel when fewer than a quarter of the pairs could be skipped,
+ * and passes of fewer than 4096 rows are always dense.  On by default; 0 restores the pass that multiplies every speck.
+ * The other statistics kernels are not affected.  Sub-problems of the split search inherit the setting. */
+int lc_ctx_set_speck_skip(lc_ctx* ctx, int on);
+/* How many statistics passes of this context ran the skipping kernel, and how many the probe sent to the dense one
+ * (either pointer may be NULL). */
+int lc_ctx_speck_passes(lc_ctx* ctx, int64_t* skipping, int64_t* dense);
+
 /* Device and page-locked blocks released by contexts are cached for re-use (the split search builds a context per
  * attempt); this returns all of them to the driver. */
 int lc_trim_cache(void);

@@ -186,6 +186,8 @@ def lib() -> C.CDLL:
                                       c_double_p, C.c_uint64, c_int64_p, C.c_double]
     L.lc_ctx_set_sharding.argtypes = [C.c_void_p, C.c_int]
     L.lc_ctx_set_skip_zero.argtypes = [C.c_void_p, C.c_int]
+    L.lc_ctx_set_speck_skip.argtypes = [C.c_void_p, C.c_int]
+    L.lc_ctx_speck_passes.argtypes = [C.c_void_p, c_int64_p, c_int64_p]
     L.lc_ctx_get_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p]
     L.lc_ctx_set_qz.argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_int, C.c_int64, C.c_int64]
     L.lc_ctx_get_qz.argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_int64, C.c_int64]
@@ -379,6 +381,17 @@ class Context:
     def set_skip_zero(self, on: bool = True):
         """Exact: leave out (4-row step, cluster) pairs with all-zero responsibilities in the statistics pass."""
         check(lib().lc_ctx_set_skip_zero(self._h, int(on)))
+
+    def set_speck_skip(self, on: bool = True):
+        """Feature-GEMM statistics pass: leave out (4-row step, cluster quad) pairs whose responsibilities are all below
+        2^-300 (the default); False multiplies every speck as the dense kernel always did."""
+        check(lib().lc_ctx_set_speck_skip(self._h, int(on)))
+
+    def speck_passes(self):
+        """-> (statistics passes that ran the speck-skipping kernel, passes its probe sent to the dense one)"""
+        a, b = C.c_int64(), C.c_int64()
+        check(lib().lc_ctx_speck_passes(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def set_sharding(self, whole_groups: bool):
         check(lib().lc_ctx_set_sharding(self._h, int(whole_groups)))

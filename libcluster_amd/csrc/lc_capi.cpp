@@ -460,6 +460,21 @@ int lc_ctx_set_skip_zero(lc_ctx* ctx, int on) {
   });
 }
 
+int lc_ctx_set_speck_skip(lc_ctx* ctx, int on) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.set_speck_skip(on != 0);
+  });
+}
+
+int lc_ctx_speck_passes(lc_ctx* ctx, int64_t* skipping, int64_t* dense) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    if (skipping) *skipping = ctx->impl.speck_passes_skipping();
+    if (dense) *dense = ctx->impl.speck_passes_dense();
+  });
+}
+
 int lc_ctx_get_rows(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* out) {
   return guarded([&] {
     need(ctx, "ctx");

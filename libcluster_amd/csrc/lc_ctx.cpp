@@ -1211,6 +1211,17 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
     const bool listed = a.mode == lck::SS_WORK_LIST;  // sparse work list instead of the dense (chunk, slice) grid
     const int nchunks = plan.nchunks, KR = plan.KR, extra = plan.extra;
     a.skip_listed = listed && skip_zero_;
+    if (speck_skip_ && plan.route == lck::SS_FEAT && NP_ >= lck::SPECK_PROBE_MIN_ROWS) {
+      // the selector: skip only where the probe finds at least a quarter of the sampled pairs skippable
+      speck_active_.reserve(1);
+      int64_t pairs = 0;
+      int active = 0;
+      LC_HIP(lck::launch_speck_probe(a.qZ, a.ldq, K, NP_, speck_active_.p, &pairs, stream_));
+      LC_HIP(hipMemcpyAsync(&active, speck_active_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
+      LC_HIP(hipStreamSynchronize(stream_));
+      a.speck_skip = lck::speck_probe_says_skip(active, pairs) ? 1 : 0;
+      (a.speck_skip ? speck_skipping_ : speck_dense_) += 1;
+    }
     const int nrec = listed ? build_sparse_worklist(smask, K, plan, a) : nchunks * KR;
     sspart_reserve((size_t)std::max(nrec, 1) * SS);
     if (extra > 0) ssext_.reserve((size_t)KR * SS);

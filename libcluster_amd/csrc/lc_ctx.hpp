@@ -160,6 +160,14 @@ class Context {
   // statistics pass: skip (4-row step, cluster) pairs whose responsibilities are all exactly 0.0 (bit-identical
   // results; pays off once qZ is mostly hard).  Always on in sparse mode.
   void set_skip_zero(bool on) { skip_zero_ = on; }
+  // dense statistics passes on the feature-GEMM route: leave out (4-row step, cluster quad) pairs whose responsibilities
+  // are all below 2^-300 (lck::SPECK_TAU) -- in the passes whose qZ a probe finds hard enough
+  // (lck::launch_speck_probe; soft passes and passes of fewer than SPECK_PROBE_MIN_ROWS rows run the dense instance).  On by
+  // default; the other routes keep every speck either way.
+  void set_speck_skip(bool on) { speck_skip_ = on; }
+  // statistics passes of this context that ran the skipping instance / that the probe sent to the dense one
+  int64_t speck_passes_skipping() const { return speck_skipping_; }
+  int64_t speck_passes_dense() const { return speck_dense_; }
   bool group_sharded() const { return group_sharded_ && distributed(); }
   // a context for a sub-problem of this one: same device, stream and all-reduce hook
   void inherit_comm(const Context& parent) {
@@ -168,6 +176,7 @@ class Context {
     comm_ = parent.comm_;
     group_sharded_ = parent.group_sharded_;
     skip_zero_ = parent.skip_zero_;
+    speck_skip_ = parent.speck_skip_;
   }
 
   // ---- qZ -----------------------------------------------------------------
@@ -362,6 +371,9 @@ class Context {
   std::shared_ptr<lcm::Comm> comm_;
   bool group_sharded_ = false;
   bool skip_zero_ = false;
+  bool speck_skip_ = true;
+  int64_t speck_skipping_ = 0, speck_dense_ = 0;
+  DevBuf<int> speck_active_;
 
   int J_ = 0, D_ = 0, DP_ = 0;
   int DC_ = 0;  // active width of the Gauss-Wishart E-step / feature-GEMM statistics (lck::estep_active_width): DP_ - 8 or DP_

@@ -142,6 +142,10 @@ struct SSItem {
 };
 // ---- the Gauss-Wishart statistics pass: ONE decision (suffstat_plan) for the caller's buffers, the launcher and the tests ----
 constexpr int SS_BR = 32;  // rows staged per batch: a row chunk is a whole number of them
+// The library's one "speck" threshold, 2^-300: responsibilities below it are flushed to zero by the moved-row
+// sweeps of the split search, and a (4-row step, cluster quad) pair that holds nothing else is left out of the
+// feature-GEMM statistics pass (SuffstatLaunch::speck_skip).
+constexpr double SPECK_TAU = 0x1p-300;
 // the kernel a pass runs: suffstat_kernel, suffstat_feat_kernel, suffstat_quad_kernel, suffstat_kernel's panel launches (DP > 128)
 enum SuffstatRoute { SS_PER_CLUSTER = 0, SS_FEAT = 1, SS_QUAD = 2, SS_WIDE = 3 };
 // what a pass does with the responsibilities: all of them (no mask); a [J x K] mask whose pairs are staged as zeros;
@@ -180,6 +184,9 @@ struct SuffstatLaunch {
   const SSItem* items = nullptr;
   const int* klist = nullptr;
   int nitems = 0, skip_listed = 0;  // skip_listed: the listed pairs run the zero-skipping variant too
+  // 1: leave out the (4-row step, cluster quad) pairs whose sixteen responsibilities are all below SPECK_TAU.  Only the
+  // feature GEMM (SS_FEAT) has such an instance: launch_suffstat refuses the flag on every other route.
+  int speck_skip = 0;
   // ---- written by the internal launchers, each for its own kernel (whatever the caller puts here is overwritten) ----
   int nslice = 1;                                  // blocks per row chunk
   int slice0 = 0, rs = 1, klast0 = 0, nklast = 0;  // suffstat_kernel: the row-split launch of the last slice; suffstat_feat_kernel: klast0 = first cluster of the range
@@ -188,6 +195,16 @@ struct SuffstatLaunch {
 };
 // p = suffstat_plan(a.DP, a.DC, a.NP, a.K, a.mode), computed ONCE per pass by the caller (the fill searches are not free)
 hipError_t launch_suffstat(const SuffstatLaunch& a, const SuffstatPlan& p, hipStream_t stream);
+
+// The selector in front of a speck-skipping pass: up to SPECK_PROBE_STEPS 4-row steps of qZ, evenly strided
+// over the rows, are looked at and the (step, cluster quad) pairs that would be KEPT are counted into *active (device, int,
+// zeroed here); *pairs (host) = the pairs looked at.  The pass skips when at least a quarter of them could be skipped
+// (speck_probe_says_skip): with fewer, the skipping instance's branches cost more than they save (a pass that can skip
+// nothing is 10 % slower than the dense instance).  Integer counts of a fixed sample: a deterministic function of qZ.
+constexpr int SPECK_PROBE_STEPS = 4096;
+constexpr int64_t SPECK_PROBE_MIN_ROWS = 4096;  // below: no probe, the dense instance
+hipError_t launch_speck_probe(const double* qZ, int64_t ldq, int K, int64_t NP, int* active, int64_t* pairs, hipStream_t stream);
+inline bool speck_probe_says_skip(int64_t active, int64_t pairs) { return pairs > 0 && 4 * (pairs - active) >= pairs; }
 
 // ---- tile plan of the feature-GEMM statistics kernel (suffstat_feat_kernel, lc_kernels_suffstat.hip) ----------------
 // Features of the active width DC, one per lane of a 16-feature tile (lane (lo2, blk) of tile T holds feature
@@ -206,7 +223,9 @@ enum FtKind { FT_PRODUCT = 0, FT_LINEAR = 1, FT_COUNT = 2, FT_SPARE = 3 };
 struct FtFeature {
   int u, w, kind;  // staged columns of the two factors (`one`: the column of ones)
 };
-__host__ __device__ constexpr FtFeature ft_feature(int DC, int one, int f) {
+// (always inlined: behind the long unrolled step loops of the speck-skipping instances hipcc otherwise CALLS them from the
+//  epilogue, with ft_deal's two results in scratch)
+__host__ __device__ __attribute__((always_inline)) constexpr FtFeature ft_feature(int DC, int one, int f) {
   const int noff = 16 * ft_offdiag(DC), ndiag = 10 * (DC / 4);
   if (f < noff) {
     const int p = f / 16, r = f % 16;
@@ -260,7 +279,7 @@ __host__ __device__ constexpr int ft_tpw(int DP, int DC, int NQ) {  // tiles of 
 // 4 waves (two blocks per CU, the partners belong to different blocks): TPW everywhere, the last waves of a chunk carry
 // idle tiles -- a second instance of the batch body costs more there than the idle tiles do (D = 128, 4 waves: 72.9 ->
 // 77.2 ms with an uneven deal; both bodies compete for the instruction cache).
-__host__ __device__ constexpr void ft_deal(int DP, int DC, int NQ, int slice, int wave, int* t0, int* nt) {
+__host__ __device__ __attribute__((always_inline)) constexpr void ft_deal(int DP, int DC, int NQ, int slice, int wave, int* t0, int* nt) {
   const int tiles = ft_tiles(DC), nsl = ft_nslice(DP, DC, NQ);
   if (ft_waves(DP) == 8) {
     const int ns = 4 * nsl, s = slice * 4 + (wave & 3), l = tiles / ns, r = tiles % ns;

@@ -724,7 +724,7 @@ __global__ void __launch_bounds__(256) softmax_cached_kernel(CachedNormLaunch a)
       // GB per sweep at K = 33) although nothing above 1e-90 moved.  Flushed, such a row comes out bit for bit as it
       // was, its fingerprint matches and the sweep touches nothing of it.  The mass dropped from any statistic is below
       // 1e-90 of the row's; the reference itself loses everything below e^-745 (exp underflow, probutils.cpp:146).
-      if (!ok || (a.dq && q < 0x1p-300)) q = 0.0;
+      if (!ok || (a.dq && q < SPECK_TAU)) q = 0.0;
       v[j] = q;
       if (a.ll_part) {  // the data term of the split ordering (cluster.cpp:407-410), as estep_kernel's sweep forms it
         const double ll = wave_sum(q > 0.0 ? q * (lq - crow[j]) : 0.0);

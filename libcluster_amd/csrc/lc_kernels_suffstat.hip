@@ -548,9 +548,24 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? (HALF != 0 ? 3 : 2) : (HALF !
 #ifndef LC_FT_BR128
 #define LC_FT_BR128 32
 #endif
+// Loop order of the instances that skip specks (suffstat_feat_kernel<..., SPECK>) at the grouped widths.  Quad-major
+// (ft_quad_major): all products of a step first, then ONE guarded block of NT MFMAs per quad -- 8 branches per step of 9
+// tiles x 8 quads.  Timed on one box against tile groups with one branch per (group, quad) -- pairs 40, threes 24 branches
+// per step -- at the north star (profiles/stats_speck_skip_quad_major.txt): pairs 15.7, threes 13.84, quad-major 12.31 ms per
+// hard pass.  D = 48 keeps tile pairs (ft_group_speck): <48,40,5> spills 8 registers in quad-major order, and with threes
+// <48,44,8> and <48,40,5> spill.  -DLC_FT_QUAD_MAJOR=0 (tools/variants.py) builds the tile-group layout everywhere, with
+// LC_FT_GROUP_SPECK tiles per group at D = 64.
+#ifndef LC_FT_GROUP_SPECK
+#define LC_FT_GROUP_SPECK 3
+#endif
+#ifndef LC_FT_QUAD_MAJOR
+#define LC_FT_QUAD_MAJOR 1
+#endif
+__host__ __device__ constexpr bool ft_quad_major(int DP) { return LC_FT_QUAD_MAJOR != 0 && DP >= 64 && DP <= 112; }
 // tiles whose products are formed together in front of their MFMAs (suffstat_feat_kernel's step loop)
 // (round 5, K = 20 / 40 at D = 64: threes and fours for the launches of <= 6 quads measure the same as pairs, gpurun_out/r05y2)
 __host__ __device__ constexpr int ft_group(int DP) { return DP >= 48 && DP <= 112 ? 2 : 1; }
+__host__ __device__ constexpr int ft_group_speck(int DP) { return DP == 64 ? LC_FT_GROUP_SPECK : ft_group(DP); }
 // (160 KB of LDS per CU: two blocks of 4 waves or one of 8)
 __host__ __device__ constexpr int ft_batch_rows(int DP) {
   return DP == 128 && ft_waves(DP) == 8 ? LC_FT_BR128 : DP > 96 ? 24 : DP == 64 && ft_waves(DP) == 8 ? LC_FT_BR64 : LC_FT_BR;
@@ -586,7 +601,16 @@ inline bool ss_feat_eligible(int DP, int K, int DC) {
   if (DP == 128) return rem == 0 || rem >= 28 || (ft_range(DP, K) == 64 && K >= 57);
   return rem == 0 || rem >= 4;
 }
-template <int DP, int DC, int NQ>
+// SPECK (speck skipping): a (4-row step, cluster quad) pair whose sixteen responsibilities are ALL below
+// SPECK_TAU issues no MFMA -- once the posteriors have sharpened every row has one owner and K - 1 specks of 1e-100 and
+// less, and most of a step's quads hold nothing else.  The A operand is the same sixteen values for every tile and every
+// wave of the block, so the decision is wave-uniform and all waves skip the same quads (ft_deal's balance stands).  The
+// staging threads form the step's mask (a thread holds the four rows of one cluster, a wave 32 clusters x 2 row quads or
+// 64 x 1: one compare per value and a ballot) and one lane per step stores it -- a byte, two at 16 quads -- in the spare
+// columns of the staged q batch's first row; the batch body fetches the 16 bytes once into four SGPRs, and the step loop
+// tests compile-time bits of them: no VALU work in the loop.  "Kept" is "not (q < tau)": a NaN is kept and poisons its
+// record as it always did; specks inside a kept pair are accumulated as before.
+template <int DP, int DC, int NQ, bool SPECK>
 __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(SuffstatLaunch a) {
   static_assert(DC % 4 == 0 && DC <= DP && DC > DP - 16, "active width");
   constexpr int FTW = ft_waves(DP);
@@ -650,6 +674,9 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
   static_assert(NTHR % TPR == 0 || NPRE * NTHR >= NV2, "staging");
   constexpr int QCL = NQ > 8 ? 64 : 32;
   static_assert(BR / 4 <= NTHR / QCL && 2 * BR <= NTHR, "q staging / ones column");
+  // the steps' masks: bytes (16 quads: shorts) in the spare columns QCL ... QCL + 3 of the batch's first q row
+  constexpr int MBITS = NQ > 8 ? 16 : 8;
+  static_assert(QLD - QCL == 4 && (BR / 4) * MBITS <= 128, "room for the step masks");
   double pre[NPRE][2], qpre[4];
   const int qcl = tid % QCL, qrq = tid / QCL;
   const bool qthr = qrq < BR / 4;
@@ -695,6 +722,19 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
 #pragma unroll
       for (int i = 0; i < 4; ++i) qdst[buf * QBUF + i * QLD] = qpre[i];
     }
+    if constexpr (SPECK) {
+      // (threads that stage nothing, clusters past the range and rows past the chunk hold zeros: not kept)
+      const bool keep = !(qpre[0] < SPECK_TAU) || !(qpre[1] < SPECK_TAU) || !(qpre[2] < SPECK_TAU) || !(qpre[3] < SPECK_TAU);
+      unsigned long long bal = __ballot(keep);
+      if constexpr (QCL == 32) bal = (bal >> (32 * (lane >> 5))) & 0xffffffffull;  // this thread's row quad
+      unsigned m = 0;
+#pragma unroll
+      for (int c = 0; c < NQ; ++c) m |= ((bal >> (4 * c)) & 0xfull) != 0 ? 1u << c : 0u;
+      if (qthr && qcl == 0) {
+        if constexpr (MBITS == 8) reinterpret_cast<unsigned char*>(qbuf + buf * QBUF + QCL)[qrq] = (unsigned char)m;
+        else reinterpret_cast<unsigned short*>(qbuf + buf * QBUF + QCL)[qrq] = (unsigned short)m;
+      }
+    }
   };
   if (tid < 2 * BR) xbuf[(tid / BR) * XBUF + (tid % BR) * LD + ONE] = 1.0;
   if (r0 < r1) {
@@ -712,6 +752,24 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
   constexpr bool ONEQ = NQ > 8;
   auto batch = [&](auto bsel, auto ntsel) {
     constexpr int B = decltype(bsel)::value, XO = B * XBUF, QO = B * QBUF, NT = decltype(ntsel)::value;
+    // the batch's step masks in four SGPRs; on(st, c): does step st issue the MFMAs of quad c (a compile-time bit)
+    unsigned mw0 = 0u, mw1 = 0u, mw2 = 0u, mw3 = 0u;
+    if constexpr (SPECK) {
+      const uint4 mv = *reinterpret_cast<const uint4*>(qbuf + QO + QCL);
+      mw0 = __builtin_amdgcn_readfirstlane(mv.x), mw1 = __builtin_amdgcn_readfirstlane(mv.y);
+      mw2 = __builtin_amdgcn_readfirstlane(mv.z), mw3 = __builtin_amdgcn_readfirstlane(mv.w);
+    }
+    // the test of quad c's bit of step st: s_bitcmp + s_cbranch_scc on a compile-time bit, no VALU work.  (The word is made
+    // opaque for EVERY test: hipcc otherwise threads the tests of one bit by a step's tile groups into each other and carries
+    // the outcomes as lane masks, with VALU selects between the MFMAs -- and with one opaque word per group it moves the
+    // MFMAs out of line, two taken branches per active quad.)
+    auto on = [&](int st, int c) {
+      if constexpr (!SPECK) return true;
+      const int bit = st * MBITS + c;
+      unsigned w = bit < 32 ? mw0 : bit < 64 ? mw1 : bit < 96 ? mw2 : mw3;
+      asm volatile("" : "+s"(w));
+      return ((w >> (bit & 31)) & 1u) != 0;
+    };
     if constexpr (!ONEQ && ft_group(DP) > 1) {
       // Tiles in groups of G: the group's products first, then its G x NQ MFMAs.  Next to the matrix pipe a VALU
       // instruction is paid per switch between the two kinds, not per instruction (tools/mfma_batch_probe.hip: ~ 12 clocks
@@ -721,7 +779,42 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
       // Measured (N = 10M, D = 64, K = 32; gpurun_out/r05e): pairs 21.61 -> 21.22 ms, threes 21.30, fours 21.51, fives 21.79
       // -- the multiplies were a third of what the step loses, and larger groups expose the fragment reads; D = 48 gains
       // 1 % with pairs, D = 80 ... 112 1-2 %, D = 32 and D = 128 nothing (ft_group).
-      constexpr int G = ft_group(DP), TOT = (BR / 4) * NT;
+      if constexpr (SPECK && ft_quad_major(DP)) {
+        // the step's NT products (fragments read one tile ahead), then per quad one test and NT MFMAs; quad c's register
+        // takes the next step's quad c right behind its block, whatever was skipped
+        double qa[NQ], u[2], w[2], pp[NT];
+        u[0] = pu[0][XO];
+        w[0] = pw[0][XO];
+#pragma unroll
+        for (int c = 0; c < NQ; ++c) qa[c] = pq[QO + 4 * c];
+#pragma unroll
+        for (int st = 0; st < BR / 4; ++st) {
+#pragma unroll
+          for (int t = 0; t < NT; ++t) {
+            const int cur = (st * NT + t) & 1, nxt = cur ^ 1;
+            pp[t] = u[cur] * w[cur];
+            if (t + 1 < NT) {
+              u[nxt] = pu[t + 1][XO + st * 4 * LD];
+              w[nxt] = pw[t + 1][XO + st * 4 * LD];
+            } else if (st + 1 < BR / 4) {
+              u[nxt] = pu[0][XO + (st + 1) * 4 * LD];
+              w[nxt] = pw[0][XO + (st + 1) * 4 * LD];
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int c = 0; c < NQ; ++c) {
+            if (on(st, c)) {
+#pragma unroll
+              for (int t = 0; t < NT; ++t) acc[t][c] = mfma4(qa[c], pp[t], acc[t][c]);
+            }
+            if (st + 1 < BR / 4) qa[c] = pq[QO + (st + 1) * 4 * QLD + 4 * c];
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+        return;
+      }
+      constexpr int G = SPECK ? ft_group_speck(DP) : ft_group(DP), TOT = (BR / 4) * NT;
       double qa[NQ], u[G], w[G], pp[G];
 #pragma unroll
       for (int g = 0; g < G; ++g)
@@ -753,6 +846,25 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
           }
           const bool refill = nst != st && nst < BR / 4;
           __builtin_amdgcn_sched_barrier(0);
+          if constexpr (SPECK) {
+            // one scalar branch around each quad's MFMAs of the group; the q quads are refilled whatever was skipped
+#pragma unroll
+            for (int c4 = 0; c4 < NQ; c4 += 4) {
+#pragma unroll
+              for (int c = c4; c < c4 + 4 && c < NQ; ++c)
+                if (on(st, c)) {
+#pragma unroll
+                  for (int g = 0; g < G; ++g)
+                    if (g < ng) acc[t0 + g][c] = mfma4(qa[c], pp[g], acc[t0 + g][c]);
+                }
+              if (refill) {
+#pragma unroll
+                for (int c = c4; c < c4 + 4 && c < NQ; ++c) qa[c] = pq[QO + nst * 4 * QLD + 4 * c];
+              }
+              __builtin_amdgcn_sched_barrier(0);
+            }
+            continue;
+          }
 #pragma unroll
           for (int g = 0; g < G; ++g)
             if (g < ng) {
@@ -803,7 +915,8 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
 #pragma unroll
           for (int c4 = 0; c4 < NQ; c4 += 4) {
 #pragma unroll
-            for (int c = c4; c < c4 + 4; ++c) acc[t][c] = mfma4(qa[0][c], p, acc[t][c]);
+            for (int c = c4; c < c4 + 4; ++c)
+              if (on(st, c)) acc[t][c] = mfma4(qa[0][c], p, acc[t][c]);
             if (refill) {
 #pragma unroll
               for (int c = c4; c < c4 + 4; ++c) qa[0][c] = pq[QO + (st + 1) * 4 * QLD + 4 * c];
@@ -812,7 +925,8 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
           }
         } else {
 #pragma unroll
-          for (int c = 0; c < NQ; ++c) acc[t][c] = mfma4(qa[st & 1][c], p, acc[t][c]);
+          for (int c = 0; c < NQ; ++c)
+            if (on(st, c)) acc[t][c] = mfma4(qa[st & 1][c], p, acc[t][c]);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -864,15 +978,53 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
   }
 }
 
-template <int DP, int DC, int NQ>
-static hipError_t launch_ss_feat_q(const SuffstatLaunch& b, hipStream_t stream) {
+// launch_speck_probe: one thread per (sampled step, cluster quad), one atomic per wave
+__global__ void __launch_bounds__(256) speck_probe_kernel(const double* qZ, int64_t ldq, int K, int64_t stride, int nsteps, int nq,
+                                                           int* active) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool keep = false;
+  if (t < (int64_t)nsteps * nq) {
+    const int c = (int)(t % nq);
+    const int64_t row = 4 * stride * (t / nq);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int k = 4 * c + i;
+      if (k < K) {
+        const double2* qp = reinterpret_cast<const double2*>(qZ + (int64_t)k * ldq + row);
+        const double2 v0 = qp[0], v1 = qp[1];
+        keep = keep || !(v0.x < SPECK_TAU) || !(v0.y < SPECK_TAU) || !(v1.x < SPECK_TAU) || !(v1.y < SPECK_TAU);
+      }
+    }
+  }
+  const unsigned long long b = __ballot(keep);
+  if ((threadIdx.x & 63) == 0 && b != 0) atomicAdd(active, __popcll(b));
+}
+hipError_t launch_speck_probe(const double* qZ, int64_t ldq, int K, int64_t NP, int* active, int64_t* pairs, hipStream_t stream) {
+  const int64_t steps = NP / 4;
+  *pairs = 0;
+  if (hipError_t e = hipMemsetAsync(active, 0, sizeof(int), stream); e != hipSuccess) return e;
+  if (steps < 1 || K < 1) return hipSuccess;
+  const int nsteps = (int)(steps < SPECK_PROBE_STEPS ? steps : SPECK_PROBE_STEPS), nq = (K + 3) / 4;
+  const int64_t stride = steps / nsteps;  // (the last sampled step: stride * (nsteps - 1) < steps)
+  *pairs = (int64_t)nsteps * nq;
+  hipLaunchKernelGGL(speck_probe_kernel, dim3((unsigned)((*pairs + 255) / 256)), dim3(256), 0, stream, qZ, ldq, K, stride, nsteps, nq,
+                     active);
+  return hipGetLastError();
+}
+
+template <int DP, int DC, int NQ, bool SPECK>
+static hipError_t launch_ss_feat_i(const SuffstatLaunch& b, hipStream_t stream) {
   constexpr int BR = ft_batch_rows(DP), LD = lds_row_stride(DP);
   const size_t shmem = (size_t)(2 * BR * LD + 2 * BR * ft_qld(NQ)) * sizeof(double);
-  auto kern = suffstat_feat_kernel<DP, DC, NQ>;
+  auto kern = suffstat_feat_kernel<DP, DC, NQ, SPECK>;
   static LdsGrant grant;
   if (hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(kern), shmem, grant); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)(b.nchunks * ft_nslice(DP, DC, NQ))), dim3(64 * ft_waves(DP)), shmem, stream, b);
   return hipGetLastError();
+}
+template <int DP, int DC, int NQ>
+static hipError_t launch_ss_feat_q(const SuffstatLaunch& b, hipStream_t stream) {
+  return b.speck_skip ? launch_ss_feat_i<DP, DC, NQ, true>(b, stream) : launch_ss_feat_i<DP, DC, NQ, false>(b, stream);
 }
 template <int DP, int DC>
 static hipError_t launch_ss_feat_d(const SuffstatLaunch& a, hipStream_t stream) {
@@ -1432,6 +1584,7 @@ hipError_t launch_suffstat(const SuffstatLaunch& a, const SuffstatPlan& p, hipSt
   if (a.DP > 128 && a.DP % 64) return hipErrorInvalidValue;
   // the launch has to be the one its plan describes: mask and work list as the mode says, the plan's records and chunks
   if ((p.route == SS_WIDE) != (a.DP > 128) || (p.route != SS_WIDE && p.route != SS_PER_CLUSTER && a.mode != SS_DENSE)) return hipErrorInvalidValue;
+  if (a.speck_skip && p.route != SS_FEAT) return hipErrorInvalidValue;  // (only the feature GEMM has a speck-skipping instance)
   const bool listed = a.mode == SS_WORK_LIST;
   if (listed != (a.items != nullptr) || a.KR != p.KR) return hipErrorInvalidValue;
   if (a.mode != SS_ZERO_SKIP && (a.smask != nullptr) != (a.mode == SS_MASKED_DENSE)) return hipErrorInvalidValue;
