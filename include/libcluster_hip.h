@@ -198,7 +198,9 @@ int lc_ctx_set_skip_zero(lc_ctx* ctx, int on);
  * sharpened that is most of the pass.  A statistic loses at most N * 2^-300 * max |x_u x_w| in absolute terms; NaN
  * responsibilities are kept.  A probe of qZ in front of every such pass (a fixed, strided sample of 4-row steps: a
  * deterministic function of qZ) sends the pass to the dense kernel when fewer than a quarter of the pairs could be skipped,
- * and passes of fewer than 4096 rows are always dense.  On by default; 0 restores the pass that multiplies every speck.
+ * and passes of fewer than 4096 rows are always dense.  Where the probe finds at most half of the pairs kept and D < 128,
+ * the skipping kernel sorts the rows of every staged batch (32 or 48 rows) by the cluster quad that owns them before it
+ * forms the 4-row steps, when every row of the batch has at most one such quad; the bound above holds either way.  On by default; 0 restores the pass that multiplies every speck.
  * The other statistics kernels are not affected.  Sub-problems of the split search inherit the setting. */
 int lc_ctx_set_speck_skip(lc_ctx* ctx, int on);
 /* How many statistics passes of this context ran the skipping kernel, and how many the probe sent to the dense one

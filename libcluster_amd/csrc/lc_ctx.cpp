@@ -1219,7 +1219,11 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
       LC_HIP(lck::launch_speck_probe(a.qZ, a.ldq, K, NP_, speck_active_.p, &pairs, stream_));
       LC_HIP(hipMemcpyAsync(&active, speck_active_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
       LC_HIP(hipStreamSynchronize(stream_));
-      a.speck_skip = lck::speck_probe_says_skip(active, pairs) ? 1 : 0;
+      // sorted batches (mode 2) where at most half of the sampled pairs are kept: with more, few batches can be sorted (a row
+      // that keeps two quads leaves its batch in order) and the sort's barrier is paid for nothing -- and only below D = 128,
+      // where two blocks share a compute unit: alone on its unit a block idles the matrix pipe at that barrier
+      const bool sort_pays = 2 * (int64_t)active <= pairs && DP < 128;
+      a.speck_skip = !lck::speck_probe_says_skip(active, pairs) ? 0 : sort_pays ? lck::speck_skip_mode() : 1;
       (a.speck_skip ? speck_skipping_ : speck_dense_) += 1;
     }
     const int nrec = listed ? build_sparse_worklist(smask, K, plan, a) : nchunks * KR;

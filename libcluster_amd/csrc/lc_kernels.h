@@ -186,6 +186,8 @@ struct SuffstatLaunch {
   int nitems = 0, skip_listed = 0;  // skip_listed: the listed pairs run the zero-skipping variant too
   // 1: leave out the (4-row step, cluster quad) pairs whose sixteen responsibilities are all below SPECK_TAU.  Only the
   // feature GEMM (SS_FEAT) has such an instance: launch_suffstat refuses the flag on every other route.
+  // 2: the same, and a staged batch whose rows all have at most one kept quad is sorted by that quad first (stable; the
+  // steps are then groups of four rows AS PLACED).  Other values are refused.
   int speck_skip = 0;
   // ---- written by the internal launchers, each for its own kernel (whatever the caller puts here is overwritten) ----
   int nslice = 1;                                  // blocks per row chunk
@@ -205,6 +207,9 @@ constexpr int SPECK_PROBE_STEPS = 4096;
 constexpr int64_t SPECK_PROBE_MIN_ROWS = 4096;  // below: no probe, the dense instance
 hipError_t launch_speck_probe(const double* qZ, int64_t ldq, int K, int64_t NP, int* active, int64_t* pairs, hipStream_t stream);
 inline bool speck_probe_says_skip(int64_t active, int64_t pairs) { return pairs > 0 && 4 * (pairs - active) >= pairs; }
+// SuffstatLaunch::speck_skip of a pass that skips: 2 (sorted batches); 1 in a build with -DLC_FT_SPECK_SORT=0 (decided in
+// lc_kernels_suffstat.hip, a device source, so that tools/variants.py can build the unsorted rule for a same-visit A/B)
+int speck_skip_mode();
 
 // ---- tile plan of the feature-GEMM statistics kernel (suffstat_feat_kernel, lc_kernels_suffstat.hip) ----------------
 // Features of the active width DC, one per lane of a 16-feature tile (lane (lo2, blk) of tile T holds feature

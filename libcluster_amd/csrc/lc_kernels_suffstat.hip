@@ -562,6 +562,11 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? (HALF != 0 ? 3 : 2) : (HALF !
 #define LC_FT_QUAD_MAJOR 1
 #endif
 __host__ __device__ constexpr bool ft_quad_major(int DP) { return LC_FT_QUAD_MAJOR != 0 && DP >= 64 && DP <= 112; }
+// -DLC_FT_SPECK_SORT=0 (tools/variants.py): the context's skipping passes leave the rows of a batch as they come
+#ifndef LC_FT_SPECK_SORT
+#define LC_FT_SPECK_SORT 1
+#endif
+int speck_skip_mode() { return LC_FT_SPECK_SORT != 0 ? 2 : 1; }
 // tiles whose products are formed together in front of their MFMAs (suffstat_feat_kernel's step loop)
 // (round 5, K = 20 / 40 at D = 64: threes and fours for the launches of <= 6 quads measure the same as pairs, gpurun_out/r05y2)
 __host__ __device__ constexpr int ft_group(int DP) { return DP >= 48 && DP <= 112 ? 2 : 1; }
@@ -682,6 +687,75 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
   const bool qthr = qrq < BR / 4;
   const int xr0 = tid / TPR, xc2 = tid % TPR;  // (DP = 80, 112: 256 is not a multiple of TPR -- the generic index below)
   double* const qdst = qbuf + (4 * qrq) * QLD + qcl;
+  // Sorted batches (SuffstatLaunch::speck_skip == 2): the batch's rows are PLACED by the one quad that keeps
+  // them, so that the four rows of a step share their owner and the step keeps one quad, not four.  Row masks (bit c: the
+  // row has a value of quad c that is not below SPECK_TAU) go through the row's own spare q columns; behind one more block
+  // barrier every wave works out the same slots for itself: a stable counting sort by owning quad, rows that keep nothing
+  // last -- or, when ANY row of the batch keeps more than one quad, the rows as they come (slot = row: the steps and sums
+  // of the unsorted rule).  A step's mask is the OR of the masks of the rows placed in it, so every kept value is summed
+  // wherever its row lands; the placement decides only how much is skipped.
+  [[maybe_unused]] const bool sortb = SPECK && a.speck_skip == 2;
+  auto lstore_sorted = [&](int buf) {
+    if constexpr (SPECK) {
+      // the thread's places are worked out again from an opaque copy of its index: hoisted in front of the batch body, the
+      // addresses and lane tests below would sit in registers next to the accumulators
+      int ts = tid;
+      asm volatile("" : "+v"(ts));
+      const int ln = ts & 63, sqcl = ts % QCL, sqrq = ts / QCL;
+      const bool sqthr = sqrq < BR / 4;
+      // a row's mask: ballot of its kept values (one lane per cluster), then lane n < 16 tests nibble n = quad n of that word
+      // (32 cluster columns: the low byte of the second ballot belongs to the wave's first row quad, the high byte to its second)
+      unsigned rm[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const unsigned long long bal = __ballot(!(qpre[i] < SPECK_TAU));
+        rm[i] = (unsigned)__ballot(ln < 16 && ((bal >> (4 * (ln & 15))) & 0xfull) != 0);
+      }
+      if (sqthr && sqcl < 4) {
+        unsigned v = sqcl == 0 ? rm[0] : sqcl == 1 ? rm[1] : sqcl == 2 ? rm[2] : rm[3];
+        if constexpr (QCL == 32) v = (v >> (8 * (ln >> 5))) & 0xffu;
+        *reinterpret_cast<unsigned*>(qbuf + buf * QBUF + (4 * sqrq + sqcl) * QLD + QCL + 2) = v;
+      }
+      __syncthreads();
+      const bool valid = ln < BR;
+      const unsigned mask = valid ? *reinterpret_cast<const unsigned*>(qbuf + buf * QBUF + ln * QLD + QCL + 2) : 0u;
+      const bool mixed = __ballot(__popc(mask) > 1) != 0;
+      int slot = ln;
+      if (!mixed) {
+        const int myq = mask ? __ffs(mask) - 1 : NQ;  // (NQ: the bin of the rows that keep nothing, padding rows among them)
+        int start = 0;
+#pragma unroll
+        for (int c = 0; c <= NQ; ++c) {
+          const unsigned long long b = __ballot(valid && myq == c);
+          const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+          if (valid && myq == c) slot = start + rank;
+          start += __popcll(b);
+        }
+      }
+      if ((ts >> 6) == FTW - 1) {
+        // the step masks, where the batch body reads them: every row's mask to the lane of its slot, OR over four lanes
+        unsigned m = (unsigned)__builtin_amdgcn_ds_permute(4 * slot, (int)mask);
+        m |= (unsigned)__shfl_xor((int)m, 1);
+        m |= (unsigned)__shfl_xor((int)m, 2);
+        if (valid && (ln & 3) == 0) {
+          if constexpr (MBITS == 8) reinterpret_cast<unsigned char*>(qbuf + buf * QBUF + QCL)[ln >> 2] = (unsigned char)m;
+          else reinterpret_cast<unsigned short*>(qbuf + buf * QBUF + QCL)[ln >> 2] = (unsigned short)m;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < NPRE; ++i) {
+        const int idx = ts + i * NTHR;
+        const int row = idx / TPR, c2 = idx % TPR;
+        const int srow = mixed ? row : __shfl(slot, row);
+        if (row < BR) *reinterpret_cast<double2*>(xbuf + buf * XBUF + srow * LD + 2 * c2) = make_double2(pre[i][0], pre[i][1]);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int srow = mixed ? 4 * sqrq + i : __shfl(slot, 4 * sqrq + i);
+        if (sqthr && sqcl < 4 * NQ) qbuf[buf * QBUF + srow * QLD + sqcl] = qpre[i];
+      }
+    }
+  };
   auto gload = [&](int64_t b0) {
 #pragma unroll
     for (int i = 0; i < NPRE; ++i) {
@@ -707,6 +781,12 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
     }
   };
   auto lstore = [&](int buf) {
+    if constexpr (SPECK) {
+      if (sortb) {  // (block-uniform)
+        lstore_sorted(buf);
+        return;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < NPRE; ++i) {
       int row, c2;
@@ -1585,6 +1665,7 @@ hipError_t launch_suffstat(const SuffstatLaunch& a, const SuffstatPlan& p, hipSt
   // the launch has to be the one its plan describes: mask and work list as the mode says, the plan's records and chunks
   if ((p.route == SS_WIDE) != (a.DP > 128) || (p.route != SS_WIDE && p.route != SS_PER_CLUSTER && a.mode != SS_DENSE)) return hipErrorInvalidValue;
   if (a.speck_skip && p.route != SS_FEAT) return hipErrorInvalidValue;  // (only the feature GEMM has a speck-skipping instance)
+  if (a.speck_skip < 0 || a.speck_skip > 2) return hipErrorInvalidValue;
   const bool listed = a.mode == SS_WORK_LIST;
   if (listed != (a.items != nullptr) || a.KR != p.KR) return hipErrorInvalidValue;
   if (a.mode != SS_ZERO_SKIP && (a.smask != nullptr) != (a.mode == SS_MASKED_DENSE)) return hipErrorInvalidValue;

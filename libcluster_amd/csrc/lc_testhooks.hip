@@ -740,8 +740,8 @@ LC_HOOK lc_test_fold_extra(double* rec, i64 nrec, i64 SS, int K, int klast0, int
 // inside the buffer.  partial (io) [npartial >= records * stat_stride(DP)].  plan_out [7] = suffstat_plan's numbers (route
 // first), computed here.  fold: the reductions Context::suffstat chains behind the pass (launch_reduce_partials, or
 // launch_reduce_records for a work list; launch_fold_extra when the plan has extra records) into folded (io) [nfolded >= K * SS].
-// lcx_test_suffstat_speck: the same with SuffstatLaunch::speck_skip given explicitly (0 / 1; 1 on a route without a skipping
-// instance is launch_suffstat's to refuse); lc_test_suffstat follows the context's default: on where the plan takes the
+// lcx_test_suffstat_speck: the same with SuffstatLaunch::speck_skip given explicitly (0 / 1 / 2; 1 or 2 on a route without a
+// skipping instance is launch_suffstat's to refuse); lc_test_suffstat follows the context's default: on where the plan takes the
 // feature GEMM.  (lcx_: tests/aux_hooks.py declares every lc_test_* export, and this one is bound by its own test file.)
 static int test_suffstat(const double* X, int DP, int DC, i64 NP, const double* qZ, int K, i64 ldq, int mode, const int* rginfo,
                          const unsigned char* smask, int J, int nitems, const i64* r0, const i64* r1, const int* kofs, const int* kcnt,
@@ -805,7 +805,7 @@ static int test_suffstat(const double* X, int DP, int DC, i64 NP, const double* 
   a.nchunks = p.nchunks;
   a.KR = p.KR;
   a.chunk_rows = p.chunk_rows;
-  a.speck_skip = speck_skip < 0 ? (p.route == lck::SS_FEAT ? 1 : 0) : speck_skip;
+  a.speck_skip = speck_skip < 0 ? (p.route == lck::SS_FEAT ? lck::speck_skip_mode() : 0) : speck_skip;
   const int* dkptr = nullptr;
   const int* dkrec = nullptr;
   if (listed) {
@@ -846,7 +846,7 @@ LC_HOOK lcx_test_suffstat_speck(const double* X, int DP, int DC, i64 NP, const d
                                 const unsigned char* smask, int J, int nitems, const i64* r0, const i64* r1, const int* kofs,
                                 const int* kcnt, const i64* rec0, const int* klist, int nklist, int nrec_listed, int skip_listed,
                                double* partial, i64 npartial, int fold, double* folded, i64 nfolded, i64* plan_out, int speck_skip) {
-  if (speck_skip != 0 && speck_skip != 1) return -1;
+  if (speck_skip < 0 || speck_skip > 2) return -1;
   return test_suffstat(X, DP, DC, NP, qZ, K, ldq, mode, rginfo, smask, J, nitems, r0, r1, kofs, kcnt, rec0, klist, nklist, nrec_listed,
                        skip_listed, partial, npartial, fold, folded, nfolded, plan_out, speck_skip);
 }
