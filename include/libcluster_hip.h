@@ -342,6 +342,31 @@ int lc_model_predict_conditional(lc_model* m, lc_ctx* ctx, const int* groups /* 
  * between rows (>= ntarget), logp n values; either may be NULL.  LC_EINVAL: no conditional prediction on ctx, a row
  * range out of bounds. */
 int lc_ctx_get_conditional(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* mean, int64_t row_stride, double* logp);
+/* ---- rows whose unknown columns differ from row to row (nothing in the reference corresponds).  Gauss-Wishart
+ * models only.  ctx holds the rows at the model's FULL width D; a NaN marks an unknown value ("hole"), +-inf is data.  A row
+ * may have up to LC_HOLES_MAX holes and needs at least one known column; every row has its own set.  Block b of ctx is mixed
+ * with the weights of learned group groups[b] (NULL: group 0).  With a = the known columns of a row, b = its holes, nb = |b|
+ * and P_k,a, M_k as in lc_model_predict_conditional above, after the call
+ *   the context's observations hold the completed rows: every NaN is replaced by E[x_b | x_a, training data] =
+ *     sum_k r_k M_k(x_a); every other value keeps its bits (lc_ctx_get_rows and lc_ctx_get_completed return them)
+ *   logp = log p(x_a | training data) per row and the per-row hole records (count, columns) are on the device.  A row
+ *     without holes has the logp of lc_model_predict.
+ * All K clusters take part, also for sparse models.  Works for the same models as lc_model_predict.  Replaces any prediction
+ * ctx held (lc_ctx_get_predictions and lc_ctx_get_conditional report none afterwards); a call that fails leaves none, and
+ * leaves the observations untouched, NaNs included.  The context's qZ holds intermediate values afterwards.  A second call
+ * on the same context finds no NaN any more: it scores the completed rows as fully observed (every count 0).
+ * An empty context is LC_OK.  LC_EINVAL: clusters that are not Gauss-Wishart, D mismatch ("Mismatched dims. of cluster
+ * params and obs.!"), a group index outside [0, J), a freed model, and a row with more than LC_HOLES_MAX NaNs or without a
+ * known column -- the message names block, row and count of the first such row in (block, row) order; for a pattern shared
+ * by all rows, of any size, there is lc_model_predict_conditional. */
+#define LC_HOLES_MAX 8
+int lc_model_predict_incomplete(lc_model* m, lc_ctx* ctx, const int* groups /* [J of ctx] or NULL */);
+/* rows [row0, row0+n) of block j after the last lc_model_predict_incomplete on ctx: rows is n x D (the completed rows) with
+ * row_stride doubles between rows (>= D), logp n values, count n values (the holes the row had), cols n x LC_HOLES_MAX (their
+ * columns, ascending, -1 beyond count).  Any output may be NULL.  LC_EINVAL: no such prediction on ctx, a row range out of
+ * bounds, row_stride < D. */
+int lc_ctx_get_completed(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* rows, int64_t row_stride, double* logp,
+                         int32_t* count, int32_t* cols);
 /* ---- ranking on the device (nothing in the reference corresponds): the m best rows of each of C device-resident
  * columns, 1 <= m <= 64, without bringing the columns to the host.  Entry a is better than entry b when its score is larger
  * (largest != 0; smaller otherwise), or the scores compare equal (+0.0 and -0.0 do) and a comes first in the context (lower
@@ -460,6 +485,17 @@ int lc_gw_mstep(double clustwidth, int D, double Ns, const double* xs, const dou
 int lc_gw_conditional(int D, double nu, double beta, const double* m, const double* iW, const int* given, int ngiven,
                       const int* target, int ntarget, double* A, double* ma, double* B, double* mb, double* G, double* s,
                       double* e);
+/* The host table of lc_model_predict_incomplete from one Gauss-Wishart posterior (nu, beta, m [D], iW [D x D]); with
+ * nu' = nu + 1 - D and, for nb = 0 ... LC_HOLES_MAX holes, Da = D - nb known columns:
+ *   P [D x D] row-major = nu iW^-1 (symmetric; the square A^T A of the E-step whitener of lc_gw_mstep)
+ *   e[nb] = (nu' + Da) / 2,  s = beta / ((1 + beta) nu)
+ *   G[nb] = lgamma(e[nb]) - lgamma(nu'/2) - (Da/2) log(nu' pi) + (Da log(nu' beta / (1 + beta)) - log|iW| + nb log nu) / 2
+ *           (NaN where nb > D)
+ * so that log P_a(x_a) = G[nb] - log|P_bb| / 2 - e[nb] log1p(s d_a^2) for the holes b of a row, d_a^2 = d^2 - u^T P_bb^-1 u,
+ * u = (P (x - m))_b and d^2 = (x - m)^T P (x - m) with any finite values in the holes of x.  G and e have LC_HOLES_MAX + 1
+ * entries.  Any output may be NULL.  LC_EINVAL: nu <= D - 1, beta <= 0, iW not positive definite. */
+int lc_gw_precision(int D, double nu, double beta, const double* m, const double* iW, double* P, double* G, double* s,
+                    double* e);
 /* NormGamma: addobs sums -> update() (distributions.cpp:441-464), fenergy (:508-517), Eloglike constant (:486-488).
  * xs, xxs: D values each (sum q x, sum q x.^2). */
 int lc_ng_mstep(double clustwidth, int D, double Ns, const double* xs, const double* xxs, double* nu, double* beta,

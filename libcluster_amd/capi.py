@@ -45,6 +45,19 @@ class Conditional(NamedTuple):
     logp: np.ndarray
 
 
+class Completion(NamedTuple):
+    """Per-row outputs of Model.predict_incomplete (lc_model_predict_incomplete): rows (N, D) = the rows with every NaN
+    replaced by E[x_unknown | x_known, training data], logp (N,) = log p(x_known | training data), count (N,) int32 = the
+    NaNs the row had, cols (N, HOLES_MAX) int32 = their columns, ascending, -1 beyond count."""
+    rows: np.ndarray
+    logp: np.ndarray
+    count: np.ndarray
+    cols: np.ndarray
+
+
+HOLES_MAX = 8  # LC_HOLES_MAX: the NaNs one row may hold
+
+
 class TopRows(NamedTuple):
     """The m best rows of each of C columns (lc_ctx_top_rows, lc_model_exemplars), best first: count (C,) int32, group
     (C, m) int32 (block of the context / of X), row (C, m) int64 (row of that block), score (C, m); the entries past
@@ -271,6 +284,11 @@ def lib() -> C.CDLL:
     L.lc_gw_conditional.argtypes = [C.c_int, C.c_double, C.c_double, c_double_p, c_double_p, c_int_p, C.c_int, c_int_p,
                                     C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                     c_double_p]
+    L.lc_model_predict_incomplete.argtypes = [C.c_void_p, C.c_void_p, c_int_p]
+    L.lc_ctx_get_completed.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, C.c_int64, c_double_p,
+                                       c_int32_p, c_int32_p]
+    L.lc_gw_precision.argtypes = [C.c_int, C.c_double, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p,
+                                  c_double_p, c_double_p]
     _lib = L
     return L
 
@@ -615,6 +633,17 @@ class Context:
         check(lib().lc_ctx_get_conditional(self._h, j, row0, n, dptr(mean), ntarget, dptr(logp)))
         return Conditional(mean, logp)
 
+    def get_completed(self, j, row0, n):
+        """Rows [row0, row0+n) of block j after the last Model.predict_incomplete_context on this context ->
+        Completion(rows (n, D), logp (n,), count (n,), cols (n, HOLES_MAX))."""
+        D = self.dims()[1]
+        rows, logp = np.zeros((n, D)), np.zeros(n)
+        count, cols = np.zeros(n, dtype=np.int32), np.full((n, HOLES_MAX), -1, dtype=np.int32)
+        c_int32_p = C.POINTER(C.c_int32)
+        check(lib().lc_ctx_get_completed(self._h, j, row0, n, dptr(rows), D, dptr(logp), count.ctypes.data_as(c_int32_p),
+                                         cols.ctypes.data_as(c_int32_p)))
+        return Completion(rows, logp, count, cols)
+
     def top_rows(self, m, by="qz", largest=True, ncols=None, by_label=False):
         """TopRows of the m best rows (1 ... 64) of each column, ranked on the device (lc_ctx_top_rows): by="qz" the first
         ncols columns of qZ (None: all), by="logz" / "logp" the per-row outputs of the last prediction on this context
@@ -823,7 +852,7 @@ class Model:
     def impute(self, X, missing, groups=None, device=0):
         """A copy of the full-width rows X ((N, D) array or a list of blocks) with the columns `missing` replaced by
         their conditional mean given the other columns (predict_conditional).  What X holds in the missing columns is
-        not looked at (NaN is fine)."""
+        not looked at (NaN is fine).  Rows whose missing columns differ from row to row: predict_incomplete."""
         blocks = isinstance(X, (list, tuple))
         D = self.dims()[2]
         Xs = [np.array(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (X if blocks else [X])]
@@ -833,6 +862,32 @@ class Model:
         for x, r in zip(Xs, res):
             x[:, miss] = r.mean
         return Xs if blocks else Xs[0]
+
+    # -- rows with holes -------------------------------------------------------------------------------
+    def predict_incomplete_context(self, ctx, groups=None):
+        """Complete the full-width rows resident in ctx in place: every NaN (up to HOLES_MAX per row, every row its own
+        set) becomes E[x_unknown | x_known, training data] (lc_model_predict_incomplete).  Nothing is downloaded: read
+        the rows with ctx.get_completed.  A second call on the same context finds no NaN any more."""
+        g = None
+        if groups is not None:
+            garr = np.ascontiguousarray(groups, dtype=np.int32)
+            if garr.shape != (ctx.dims()[0],):
+                raise ValueError("groups needs one learned group index per block of the context")
+            g = garr.ctypes.data_as(c_int_p)
+        check(lib().lc_model_predict_incomplete(self._h, ctx._h, g))
+
+    def predict_incomplete(self, X, groups=None, device=0):
+        """Completion(rows, logp, count, cols) for the host rows X ((N, D) array, NaN = unknown), or a list of them for a
+        list of blocks (block b mixed with learned group groups[b], default 0).  rows is a filled copy: X keeps its NaNs."""
+        blocks = isinstance(X, (list, tuple))
+        Xs = self._blocks(X)
+        if not Xs:
+            return []
+        with Context(device) as ctx:
+            ctx.set_data(Xs)
+            self.predict_incomplete_context(ctx, groups)
+            out = [ctx.get_completed(j, 0, x.shape[0]) for j, x in enumerate(Xs)]
+        return out if blocks else out[0]
 
     # -- ranking (DESIGN 4.13) -------------------------------------------------------------------------------------
     def _blocks(self, X):
@@ -939,6 +994,17 @@ def gw_conditional(nu, beta, m, iW, given, target=None):
                                   None if tv is None else tv.ctypes.data_as(c_int_p), 0 if tv is None else tv.size,
                                   dptr(A), dptr(ma), dptr(B), dptr(mb), C.byref(G), C.byref(s), C.byref(e)))
     return {"A": A, "ma": ma, "B": B, "mb": mb, "G": G.value, "s": s.value, "e": e.value, "target": tg}
+
+
+def gw_precision(nu, beta, m, iW):
+    """The host table of the prediction of rows with holes (lc_gw_precision) from one Gauss-Wishart posterior:
+    P (D, D) = nu iW^-1, G and e (HOLES_MAX + 1 values: one per hole count), s."""
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    iW = np.ascontiguousarray(iW, dtype=np.float64)
+    D = m.size
+    P, G, e, s = np.zeros((D, D)), np.zeros(HOLES_MAX + 1), np.zeros(HOLES_MAX + 1), C.c_double()
+    check(lib().lc_gw_precision(D, nu, beta, dptr(m), dptr(iW), dptr(P), dptr(G), C.byref(s), dptr(e)))
+    return {"P": P, "G": G, "s": s.value, "e": e}
 
 
 def ng_mstep(clustwidth, Ns, xs, xxs):

@@ -1147,6 +1147,26 @@ int lc_ctx_get_conditional(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* 
   });
 }
 
+// ---- rows with holes -------------------------------------------------
+static_assert(LC_HOLES_MAX == lck::HOLES_MAX, "the header and the kernels agree on the holes a row may have");
+int lc_model_predict_incomplete(lc_model* m, lc_ctx* ctx, const int* groups) {
+  return guarded([&] {
+    need(m, "model");
+    need(ctx, "ctx");
+    ctx->impl.predict_clear();  // (a failure leaves no prediction behind)
+    if (!model_alive(m)) throw std::invalid_argument("the model was freed");
+    lcp::predict_incomplete(ctx->impl, m->model, groups);
+  });
+}
+
+int lc_ctx_get_completed(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* rows, int64_t row_stride, double* logp,
+                         int32_t* count, int32_t* cols) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.get_completed(j, row0, n, rows, row_stride, logp, count, cols);
+  });
+}
+
 // ---- ranking -----------------------------------------------------
 int lc_ctx_top_rows(lc_ctx* ctx, int what, int ncols, int m, int largest, int by_label, int32_t* count, int32_t* group,
                     int64_t* row, double* score) {
@@ -1257,6 +1277,16 @@ int lc_gw_conditional(int D, double nu, double beta, const double* m, const doub
     if (D < 1) throw std::invalid_argument("D must be >= 1!");
     const std::vector<int> tg = lcp::conditional_split(D, given, ngiven, target, ntarget);
     lcp::gw_conditional(D, nu, beta, m, iW, std::vector<int>(given, given + ngiven), tg, A, ma, B, mb, G, s, e);
+  });
+}
+
+int lc_gw_precision(int D, double nu, double beta, const double* m, const double* iW, double* P, double* G, double* s,
+                    double* e) {
+  return guarded([&] {
+    need(m, "m");
+    need(iW, "iW");
+    if (D < 1) throw std::invalid_argument("D must be >= 1!");
+    lcp::gw_precision(D, nu, beta, iW, P, G, s, e);
   });
 }
 

@@ -276,6 +276,7 @@ class Context {
     pred_vb_ = pred_logp_ = false;
     pred_docs_T_ = 0;
     pred_cond_ = 0;
+    pred_holes_ = false;
   }
   // Conditional prediction: after a raw E-step with zero constants over the context's (given) columns left
   // Kp columns in qZ, per row E[x_target | x_given] (Db columns) and log p(x_given) into the context's conditional outputs
@@ -286,6 +287,20 @@ class Context {
   // rows [row0, row0+n) of group j of the last conditional prediction (either output may be null)
   void get_conditional(int j, int64_t row0, int64_t n, double* mean, int64_t row_stride, double* logp) const;
   int conditional_width() const { return pred_cond_; }  // target columns of the conditional prediction held (0: none)
+  // Rows with holes (a NaN in X is an unknown value).  holes_scan: one read of X leaves the per-row hole
+  // records on the device and returns the number of rows with holes, the largest count and the first row (in block, row
+  // order) that has more than lck::HOLES_MAX holes or no known column (*bad_block = -1: none), with its count.
+  // holes_fill: fill[c] (D host values) into the recorded positions.  predict_holes: after a raw E-step with zero constants
+  // over the filled rows left Kp columns in qZ, the completed rows into X in place and log p(x_known) per row
+  // (lck::PredictHolesLaunch for the tables: tt J x NH x Kp, ps Kp, pe NH x Kp, mean Kp x D, P Kp x D x D host arrays,
+  // NH = lck::HOLES_MAX + 1).  qZ is left holding the raw columns.
+  void holes_scan(int64_t* holed_rows, int* max_count, int* bad_block, int64_t* bad_row, int* bad_count);
+  void holes_fill(const double* fill);
+  void predict_holes(int Kp, const double* tt, const double* ps, const double* pe, const double* mean, const double* P);
+  // rows [row0, row0+n) of group j after the last predict_holes (any output may be null): the completed rows (row_stride
+  // >= D doubles apart), logp, count and cols [n x lck::HOLES_MAX] (ascending, -1 beyond count)
+  void get_completed(int j, int64_t row0, int64_t n, double* rows, int64_t row_stride, double* logp, int32_t* count,
+                     int32_t* cols) const;
   // ---- ranking ----------------------------------------------------------------------------------------------
   // The m best rows of each column (lck::TopRowsLaunch for the order): what = 0 the first ncols columns of qZ, 1 / 2 the
   // logZ / logp of the last prediction (one column; ncols is not looked at).  by_label: column c only sees the rows the
@@ -457,6 +472,12 @@ class Context {
   // ... of the last conditional prediction: mean [NP x pred_cond_] and log p(x_given) [NP]; pred_cond_ = 0: none
   DevBuf<double> pcmean_, pclogp_;
   int pred_cond_ = 0;
+  // ... of the last prediction of rows with holes: count [NP], cols [NP x HOLES_MAX], log p(x_known) [NP], the scan's
+  // three integers; pred_holes_: X holds the completed rows of such a prediction
+  DevBuf<int> hcount_, hcols_;
+  DevBuf<double> hlogp_;
+  DevBuf<int64_t> hscan_;
+  bool pred_holes_ = false;
   // top_rows: the first stage's partial lists and the result [C x m scores | C x m positions]
   DevBuf<double> topkey_, topout_;
   DevBuf<int64_t> toppos_;

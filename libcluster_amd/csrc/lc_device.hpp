@@ -329,5 +329,38 @@ __device__ __forceinline__ double wave_sum(double v) {
   v = sum_over_lo4(v);
   return sum_over_hi(v);
 }
+// largest value of the wave, in every lane
+__device__ __forceinline__ double wave_max(double v) {
+  for (int d = 1; d < 64; d <<= 1) v = fmax(v, __shfl_xor(v, d));
+  return v;
+}
+
+// group of a padded row and whether it holds an observation (rginfo: lck::rginfo_pack per row group, or null for a single
+// group of nrows rows)
+__device__ __forceinline__ bool row_valid(int64_t row, const int* rginfo, int64_t nrows, int& j) {
+  const int64_t g = row / RG;
+  const int r = (int)(row - g * RG);
+  int nv;
+  if (rginfo) {
+    const int w = rginfo[g];
+    j = w >> 5;
+    nv = w & 31;
+  } else {
+    j = 0;
+    const int64_t rem = nrows - g * RG;
+    nv = rem >= RG ? RG : rem > 0 ? (int)rem : 0;
+  }
+  return r < nv;
+}
+
+// online log-sum-exp: the terms pushed so far sum to s * exp(m); one exponential per term.  -inf terms add nothing
+// (with m = -inf too, d is NaN: not `up`, and exp_nonpos clamps NaN to exp(-750) = 0).
+__device__ __forceinline__ void lse_push(double v, double& m, double& s, const double* etab) {
+  const double d = v - m;
+  const bool up = d > 0.0;
+  const double e = exp_nonpos(up ? -d : d, etab);
+  s = up ? fma(s, e, 1.0) : s + e;
+  m = up ? v : m;
+}
 
 }  // namespace lck

@@ -19,32 +19,7 @@ namespace {
 constexpr int PR_THREADS = 256;
 constexpr int PR_COLS = 8;  // predict_rows_kernel: columns loaded per batch
 
-// group of a padded row and whether it holds an observation
-__device__ __forceinline__ bool row_valid(int64_t row, const int* rginfo, int64_t nrows, int& j) {
-  const int64_t g = row / RG;
-  const int r = (int)(row - g * RG);
-  int nv;
-  if (rginfo) {
-    const int w = rginfo[g];
-    j = w >> 5;
-    nv = w & 31;
-  } else {
-    j = 0;
-    const int64_t rem = nrows - g * RG;
-    nv = rem >= RG ? RG : rem > 0 ? (int)rem : 0;
-  }
-  return r < nv;
-}
-
-// online log-sum-exp: the terms pushed so far sum to s * exp(m); one exponential per term.  -inf terms add nothing
-// (with m = -inf too, d is NaN: not `up`, and exp_nonpos clamps NaN to exp(-750) = 0).
-__device__ __forceinline__ void lse_push(double v, double& m, double& s, const double* etab) {
-  const double d = v - m;
-  const bool up = d > 0.0;
-  const double e = exp_nonpos(up ? -d : d, etab);
-  s = up ? fma(s, e, 1.0) : s + e;
-  m = up ? v : m;
-}
+// (row_valid and lse_push: lc_device.hpp, shared with lc_kernels_holes.hip)
 
 __global__ __launch_bounds__(PR_THREADS) void predict_rows_kernel(PredictRowsLaunch a) {
   __shared__ double etab[64];

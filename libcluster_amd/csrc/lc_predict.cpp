@@ -199,6 +199,145 @@ void Context::get_conditional(int j, int64_t row0, int64_t n, double* mean, int6
   LC_HIP(hipStreamSynchronize(stream_));
 }
 
+void Context::holes_scan(int64_t* holed_rows, int* max_count, int* bad_block, int64_t* bad_row, int* bad_count) {
+  use_device();
+  pred_holes_ = false;
+  *holed_rows = 0;
+  *max_count = 0;
+  *bad_block = -1;
+  *bad_row = -1;
+  *bad_count = 0;
+  if (NP_ == 0) return;
+  hcount_.reserve((size_t)NP_);
+  hcols_.reserve((size_t)NP_ * lck::HOLES_MAX);
+  hscan_.reserve(3);
+  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the scan's integers travel in int64 slots");
+  lck::HolesScanLaunch a;
+  a.X = X_.p;
+  a.DP = DP_;
+  a.D = D_;
+  a.nrg = NP_ / lck::RG;
+  a.rginfo = J_ > 1 ? rginfo_.p : nullptr;
+  a.nrows = Nj_[0];
+  a.count = hcount_.p;
+  a.cols = hcols_.p;
+  a.out = reinterpret_cast<unsigned long long*>(hscan_.p);
+  LC_HIP(lck::launch_holes_scan(a, stream_));
+  int64_t out[3];
+  LC_HIP(hipMemcpyAsync(out, hscan_.p, sizeof(out), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+  *holed_rows = out[0];
+  *max_count = (int)out[1];
+  if (out[2] < 0) return;  // (~0: no offending row)
+  const int64_t pos = out[2];
+  const int j = (int)(std::upper_bound(goff_.begin(), goff_.end(), pos) - goff_.begin()) - 1;
+  if (pos >= NP_ || j < 0 || j >= J_ || pos - goff_[(size_t)j] >= Nj_[(size_t)j])
+    throw std::logic_error("holes_scan: the offending position is no observation");
+  int cnt = 0;
+  LC_HIP(hipMemcpyAsync(&cnt, hcount_.p + pos, sizeof(int), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+  *bad_block = j;
+  *bad_row = pos - goff_[(size_t)j];
+  *bad_count = cnt;
+}
+
+void Context::holes_fill(const double* fill) {
+  use_device();
+  if (NP_ == 0) return;
+  if (!hcount_.p || !hcols_.p) throw std::logic_error("holes_fill: no hole records");
+  hpack_.resize((size_t)D_);
+  std::copy(fill, fill + D_, hpack_.data());
+  ptab_.reserve(hpack_.size());
+  LC_HIP(hipMemcpyAsync(ptab_.p, hpack_.data(), hpack_.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+  lck::HolesFillLaunch a;
+  a.X = X_.p;
+  a.DP = DP_;
+  a.nrg = NP_ / lck::RG;
+  a.rginfo = J_ > 1 ? rginfo_.p : nullptr;
+  a.nrows = Nj_[0];
+  a.count = hcount_.p;
+  a.cols = hcols_.p;
+  a.fill = ptab_.p;
+  LC_HIP(lck::launch_holes_fill(a, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ and ptab_ are free again)
+  dcache_invalidate();                    // (the observations changed)
+}
+
+void Context::predict_holes(int Kp, const double* tt, const double* ps, const double* pe, const double* mean,
+                            const double* P) {
+  use_device();
+  if (Kp < 1) throw std::invalid_argument("K must be >= 1");
+  pred_holes_ = false;
+  if (NP_ == 0) {
+    pred_holes_ = true;
+    return;
+  }
+  if (qz_[cur_].cap < Kp || !qz_[cur_].buf.p) throw std::logic_error("predict_holes: no raw E-step columns");
+  if (!hcount_.p || !hcols_.p) throw std::logic_error("predict_holes: no hole records");
+  constexpr int NH = lck::HOLES_MAX + 1;
+  const int D = D_, DP = DP_;
+  hlogp_.reserve((size_t)NP_);
+  // tables: [tt J x NH x Kp | ps Kp | pe NH x Kp | mean Kp x DP | P Kp x DP x DP], the pads zero
+  const size_t nt = (size_t)J_ * NH * Kp, ne = (size_t)NH * Kp, nm = (size_t)Kp * DP, nP = nm * DP;
+  hpack_.assign(nt + (size_t)Kp + ne + nm + nP, 0.0);
+  double* h = hpack_.data();
+  std::copy(tt, tt + nt, h);
+  std::copy(ps, ps + Kp, h + nt);
+  std::copy(pe, pe + ne, h + nt + Kp);
+  double* hm = h + nt + Kp + ne;
+  double* hP = hm + nm;
+  for (int k = 0; k < Kp; ++k) {
+    std::copy(mean + (size_t)k * D, mean + (size_t)(k + 1) * D, hm + (size_t)k * DP);
+    for (int r = 0; r < D; ++r)
+      std::copy(P + ((size_t)k * D + r) * D, P + ((size_t)k * D + r + 1) * D, hP + ((size_t)k * DP + r) * DP);
+  }
+  ptab_.reserve(hpack_.size());
+  LC_HIP(hipMemcpyAsync(ptab_.p, hpack_.data(), hpack_.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+  lck::PredictHolesLaunch a;
+  a.X = X_.p;
+  a.DP = DP;
+  a.Kp = Kp;
+  a.col = qz_[cur_].buf.p;
+  a.ldq = NP_;
+  a.nrg = NP_ / lck::RG;
+  a.rginfo = J_ > 1 ? rginfo_.p : nullptr;
+  a.nrows = Nj_[0];
+  a.count = hcount_.p;
+  a.cols = hcols_.p;
+  a.ttab = ptab_.p;
+  a.pscale = ptab_.p + nt;
+  a.pexp = ptab_.p + nt + Kp;
+  a.mean = ptab_.p + nt + Kp + ne;
+  a.P = a.mean + nm;
+  a.logp = hlogp_.p;
+  LC_HIP(lck::launch_predict_holes(a, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ and ptab_ are free again)
+  qz_[cur_].K = Kp;
+  qz_[cur_].hash_ok = false;
+  dcache_invalidate();  // (the observations changed)
+  pred_holes_ = true;
+}
+
+void Context::get_completed(int j, int64_t row0, int64_t n, double* rows, int64_t row_stride, double* logp, int32_t* count,
+                            int32_t* cols) const {
+  use_device();
+  if (!pred_holes_) throw std::invalid_argument("the context holds no completed rows (lc_model_predict_incomplete)");
+  if (j < 0 || j >= J_ || row0 < 0 || n < 0 || row0 + n > Nj_[j]) throw std::invalid_argument("row range out of bounds");
+  if (rows && row_stride < D_) throw std::invalid_argument("row_stride is smaller than the number of columns");
+  if (n == 0) return;
+  const size_t at = (size_t)(goff_[j] + row0);
+  static_assert(sizeof(int) == sizeof(int32_t), "the hole records are int32");
+  if (rows)
+    LC_HIP(hipMemcpy2DAsync(rows, (size_t)row_stride * sizeof(double), X_.p + at * DP_, (size_t)DP_ * sizeof(double),
+                            (size_t)D_ * sizeof(double), (size_t)n, hipMemcpyDeviceToHost, stream_));
+  if (logp) LC_HIP(hipMemcpyAsync(logp, hlogp_.p + at, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  if (count) LC_HIP(hipMemcpyAsync(count, hcount_.p + at, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, stream_));
+  if (cols)
+    LC_HIP(hipMemcpyAsync(cols, hcols_.p + at * lck::HOLES_MAX, (size_t)n * lck::HOLES_MAX * sizeof(int),
+                          hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+}
+
 void Context::top_rows(int what, int ncols, int m, bool largest, bool by_label, int32_t* count, int32_t* group,
                        int64_t* row, double* score) {
   use_device();
@@ -539,6 +678,109 @@ void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* 
   // one raw E-step over the given columns with the marginal whiteners: -d^2 / 2 per column
   ctx.estep(Kp, A.data(), ma.data(), zero.data(), nullptr, nullptr, /*raw=*/true);
   ctx.predict_cond(Kp, Db, tt.data(), ps.data(), pe.data(), ma.data(), B.data(), mb.data());
+}
+
+void gw_precision(int D, double nu, double beta, const double* iW, double* P, double* G, double* s, double* e) {
+  constexpr int NH = lck::HOLES_MAX + 1;
+  const double nup = nu + 1 - D;  // Student-t degrees of freedom: of the FULL model's width (a marginal keeps them)
+  if (!(nup > 0.0) || !(beta > 0.0)) throw std::invalid_argument("nu must exceed D - 1 and beta must be positive");
+  std::vector<double> L(iW, iW + (size_t)D * D);
+  if (!lch::cholesky(L, D)) throw std::invalid_argument("Matrix A is not positive definite");  // (iW = L L^T)
+  double logdet = 0.0;
+  for (int i = 0; i < D; ++i) logdet += std::log(L[(size_t)i * D + i]);
+  logdet *= 2.0;
+  if (P) {  // nu Li^T Li: the square of GaussWishState::whitener()
+    const std::vector<double> Li = lch::tril_inverse(L, D);
+    for (int i = 0; i < D; ++i)
+      for (int c = 0; c <= i; ++c) {
+        double v = 0.0;
+        for (int k = i; k < D; ++k) v += Li[(size_t)k * D + i] * Li[(size_t)k * D + c];
+        P[(size_t)i * D + c] = P[(size_t)c * D + i] = nu * v;
+      }
+  }
+  for (int nb = 0; nb < NH; ++nb) {
+    const int Da = D - nb;
+    if (G)
+      G[nb] = Da < 0 ? std::numeric_limits<double>::quiet_NaN()
+                     : lch::lgam((nup + Da) / 2) - lch::lgam(nup / 2) - 0.5 * Da * std::log(nup * lch::PI) +
+                           0.5 * (Da * std::log(nup * beta / (1 + beta)) - (logdet - nb * std::log(nu)));
+    if (e) e[nb] = (nup + Da) / 2;
+  }
+  if (s) *s = beta / ((1 + beta) * nu);
+}
+
+void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* groups) {
+  ctx.predict_clear();  // (whatever an earlier prediction left must not outlive a failure of this one)
+  constexpr int NH = lck::HOLES_MAX + 1;
+  const int K = (int)model.clusters.size(), J = (int)model.weights.size(), Jc = ctx.J();
+  if (K < 1) throw std::invalid_argument("the model has no clusters");
+  if (model.ckind != lch::C_GAUSSWISH)
+    throw std::invalid_argument("conditional prediction needs Gauss-Wishart clusters: the columns of NormGamma / ExpGamma "
+                                "clusters are independent within a cluster (not supported)");
+  const int D = model.clusters[0].gw.D;
+  if (Jc > 0 && ctx.D() != D) throw std::invalid_argument("Mismatched dims. of cluster params and obs.!");
+  for (int b = 0; b < Jc; ++b) {
+    const int j = groups ? groups[b] : 0;
+    if (j < 0 || j >= J) throw std::invalid_argument("group index out of range");
+  }
+  if (Jc < 1) return;  // (a context without observations: nothing to complete, nothing to read)
+  if (ctx.DP() > lck::GW_MAX_DP)  // (what the E-step below would refuse, said before the holes are filled)
+    throw std::invalid_argument("D > 1024 is not supported by the Gauss-Wishart kernels (the diagonal and exponential "
+                                "families take any D)");
+  std::vector<double> Epi((size_t)J * K), Erest((size_t)J);
+  bool rest = false;
+  for (int j = 0; j < J; ++j) {
+    if ((int)model.weights[(size_t)j].alpha1.size() != K) throw std::invalid_argument("weights and clusters disagree");
+    weights_predictive(model.weights[(size_t)j], Epi.data() + (size_t)j * K, &Erest[(size_t)j]);
+    rest = rest || Erest[(size_t)j] > 0.0;
+  }
+  const int Kp = K + (rest ? 1 : 0);
+  const lch::ClusterAny prior(model.ckind, model.clusters[0].prior(), D);  // clearobs state: a cluster that saw no data
+  std::vector<double> P((size_t)Kp * D * D), G((size_t)Kp * NH), ps((size_t)Kp), ek((size_t)Kp * NH);
+  std::vector<double> A((size_t)Kp * D * D), m((size_t)Kp * D);
+  for (int k = 0; k < Kp; ++k) {
+    const lch::GaussWishState& g = k < K ? model.clusters[(size_t)k].gw : prior.gw;
+    gw_precision(D, g.nu, g.beta, g.iW.data(), P.data() + (size_t)k * D * D, &G[(size_t)k * NH], &ps[(size_t)k],
+                 &ek[(size_t)k * NH]);
+    const std::vector<double> Ak = g.whitener();
+    std::copy(Ak.begin(), Ak.end(), A.begin() + (size_t)k * D * D);
+    std::copy(g.m.begin(), g.m.end(), m.begin() + (size_t)k * D);
+  }
+  // tables by hole count: tt [Jc x NH x Kp], pe [NH x Kp]
+  std::vector<double> tt((size_t)Jc * NH * Kp), pe((size_t)NH * Kp), zero((size_t)Jc * Kp, 0.0);
+  for (int nb = 0; nb < NH; ++nb) {
+    for (int k = 0; k < Kp; ++k) pe[(size_t)nb * Kp + k] = ek[(size_t)k * NH + nb];
+    for (int b = 0; b < Jc; ++b) {
+      const int j = groups ? groups[b] : 0;
+      double* t = tt.data() + ((size_t)b * NH + nb) * Kp;
+      for (int k = 0; k < K; ++k) t[k] = std::log(Epi[(size_t)j * K + k]) + G[(size_t)k * NH + nb];
+      if (rest) t[K] = std::log(Erest[(size_t)j]) + G[(size_t)K * NH + nb];
+    }
+  }
+  // what goes into the holes before the E-step: any finite value gives the same answer in exact arithmetic; one close to
+  // the data (the N_k-weighted mean of the cluster means) keeps an offset far from the origin out of d_full^2 - u^T H^-1 u
+  std::vector<double> fill((size_t)D, 0.0);
+  double wsum = 0.0;
+  for (int k = 0; k < K; ++k) wsum += model.clusters[(size_t)k].gw.N;
+  for (int k = 0; k < K; ++k) {
+    const lch::GaussWishState& g = model.clusters[(size_t)k].gw;
+    const double w = wsum > 0.0 ? g.N / wsum : 1.0 / K;
+    for (int d = 0; d < D; ++d) fill[(size_t)d] += w * g.m[(size_t)d];
+  }
+
+  int64_t holed = 0, bad_row = -1;
+  int max_count = 0, bad_block = -1, bad_count = 0;
+  ctx.holes_scan(&holed, &max_count, &bad_block, &bad_row, &bad_count);
+  if (bad_block >= 0)  // (nothing was written to X so far)
+    throw std::invalid_argument("row " + std::to_string(bad_row) + " of block " + std::to_string(bad_block) + " has " +
+                                std::to_string(bad_count) + " unknown values (NaN) among its " + std::to_string(D) +
+                                " columns: at most " + std::to_string(lck::HOLES_MAX) +
+                                " per row, and at least one known column (lc_model_predict_conditional takes a pattern "
+                                "shared by all rows, of any size)");
+  if (holed > 0) ctx.holes_fill(fill.data());
+  // one raw E-step at full width over the K clusters (+ the prior's whitener): -d_full^2 / 2 per column
+  ctx.estep(Kp, A.data(), m.data(), zero.data(), nullptr, nullptr, /*raw=*/true);
+  ctx.predict_holes(Kp, tt.data(), ps.data(), pe.data(), m.data(), P.data());
 }
 
 void exemplars(lcc::Context& ctx, const lce::Model& model, bool sparse, const int* groups, int mtop, int32_t* count,

@@ -94,6 +94,68 @@ struct PredictCondLaunch {
 };
 hipError_t launch_predict_cond(const PredictCondLaunch& a, hipStream_t stream);
 
+// ---- rows whose unknown columns differ from row to row (lc_kernels_holes.hip) ---------------------------------
+// A NaN in X marks an unknown value ("hole"); a row may hold up to HOLES_MAX of them (LC_HOLES_MAX of the C header).
+constexpr int HOLES_MAX = 8;
+// holes_scan_kernel: the one read of X that finds the holes.  Per valid row: count[row] = its number of NaNs (all of
+// them, also beyond HOLES_MAX) and cols[row][0 .. HOLES_MAX) = the first HOLES_MAX of their columns, ascending, -1 beyond
+// the count.  Pad rows and pad columns are not read.  out (cleared to {0, 0, ~0} by the launcher) receives, through integer
+// atomics only (the same values on every run):
+//   out[0] rows with at least one hole   out[1] the largest count   out[2] the smallest padded row position whose count
+//   exceeds HOLES_MAX or leaves no known column (count >= D)
+struct HolesScanLaunch {
+  const double* X = nullptr;  // [NP x DP]
+  int DP = 0;
+  int D = 0;
+  int64_t nrg = 0;
+  const int* rginfo = nullptr;
+  int64_t nrows = 0;
+  int* count = nullptr;  // [NP]
+  int* cols = nullptr;   // [NP x HOLES_MAX]
+  unsigned long long* out = nullptr;  // [3]
+};
+hipError_t launch_holes_scan(const HolesScanLaunch& a, hipStream_t stream);
+
+// holes_fill_kernel: X[row][cols[row][i]] = fill[cols[row][i]] for i < count[row] -- the recorded positions only
+struct HolesFillLaunch {
+  double* X = nullptr;
+  int DP = 0;
+  int64_t nrg = 0;
+  const int* rginfo = nullptr;
+  int64_t nrows = 0;
+  const int* count = nullptr;
+  const int* cols = nullptr;
+  const double* fill = nullptr;  // [D]
+};
+hipError_t launch_holes_fill(const HolesFillLaunch& a, hipStream_t stream);
+
+// predict_holes_kernel: after a raw E-step over the FILLED rows left -d_full^2 / 2 in column k, with b the holes of a row,
+// nb their number, y = x_filled - m_k and P_k = nu_k iW_k^-1:
+//   u = (P_k y)_b, H = (P_k)_bb = L L^T,  d_a^2 = max(d_full^2 - u^T H^-1 u, 0),  M_k = x_filled,b - H^-1 u
+//   t_k = ttab[j][nb][k] - log prod_i L_ii - pexp[nb][k] log1p(s_k d_a^2),  logp = LSE_k t_k,  x_b <- sum_k r_k M_k
+// A row without holes (nb = 0) takes predict_rows_kernel's loop, one lane per row; a row with holes is worked on by its
+// whole wave.  No atomics, no scratch: the same bits on every call.  The hole positions of X are overwritten in place.
+constexpr int PH_THREADS = 256;
+struct PredictHolesLaunch {
+  double* X = nullptr;  // [NP x DP], holes filled
+  int DP = 0;
+  int Kp = 0;
+  const double* col = nullptr;  // [Kp columns x ldq] raw E-step
+  int64_t ldq = 0;
+  int64_t nrg = 0;
+  const int* rginfo = nullptr;
+  int64_t nrows = 0;
+  const int* count = nullptr;
+  const int* cols = nullptr;
+  const double* ttab = nullptr;    // [J x (HOLES_MAX + 1) x Kp] log E[pi_jk] + G_k(nb)
+  const double* pscale = nullptr;  // [Kp] s_k
+  const double* pexp = nullptr;    // [(HOLES_MAX + 1) x Kp] e_k(nb)
+  const double* mean = nullptr;    // [Kp x DP] m_k, pad columns zero
+  const double* P = nullptr;       // [Kp x DP x DP] P_k, pad rows and columns zero
+  double* logp = nullptr;          // [NP]
+};
+hipError_t launch_predict_holes(const PredictHolesLaunch& a, hipStream_t stream);
+
 }  // namespace lck
 
 namespace lch {
@@ -125,6 +187,18 @@ void gw_conditional(int D, double nu, double beta, const double* m, const double
 // models only; all K clusters take part (and the prior component of StickBreak weights), as in predict()'s logp.
 void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* groups, const int* given, int ngiven,
                          const int* target, int ntarget);
+// The host table of one Gauss-Wishart posterior for rows with holes, NH = lck::HOLES_MAX + 1:
+//   P [D x D] = nu iW^-1 = A^T A with the whitener A (symmetric)
+//   G [NH]: G[nb] = lgam(e[nb]) - lgam(nu'/2) - (Da/2) log(nu' pi) + (Da log(nu' beta / (1 + beta)) - log|iW| + nb log nu) / 2
+//           with Da = D - nb, nu' = nu + 1 - D (NaN where Da < 0); the device adds -log|P_bb| / 2
+//   s = beta / ((1 + beta) nu),  e [NH]: e[nb] = (nu' + Da) / 2
+// Any output may be null.  Throws std::invalid_argument for nu <= D - 1, beta <= 0, iW not positive definite.
+void gw_precision(int D, double nu, double beta, const double* iW, double* P, double* G, double* s, double* e);
+// Completes the rows in ctx (the model's full width; NaN = unknown) in place and leaves log p(x_known | training data)
+// per row and the hole records in the context (Context::get_completed).  Gauss-Wishart models only; all K clusters take
+// part (and the prior component of StickBreak weights).  Throws std::invalid_argument, with the observations untouched,
+// for a row with more than lck::HOLES_MAX holes or without a known column.
+void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* groups);
 // E[pi_k] (K values) and the mass beyond the truncation E[pi_rest] of a weight distribution in its updated state:
 //   Dirichlet:  alpha_k / sum(alpha), no rest
 //   StickBreak: E[v_k] prod_{i before k} E[1 - v_i] in ordvec order (distributions.cpp:139-165), rest prod_i E[1 - v_i]

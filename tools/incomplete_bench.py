@@ -1,0 +1,175 @@
+"""Timings of the prediction of rows with holes: lc_model_predict_incomplete on device-resident rows of
+which a share holds 1 ... 8 unknown values (NaN), against lc_model_predict(keep_qz = 0) on the same rows without holes.
+
+For every shape: the model comes from a few fixed-K VBEM iterations on rows of the synthetic stream (bench.mixture +
+lc_ctx_synth), the rows to score are synthesised on the device, brought to the host once, and uploaded again per run
+with NaNs in the chosen share of the rows (a call completes the rows in place, so every run needs fresh ones).  Hole rows
+get 1 ... 8 holes, uniformly, in columns start + i * stride (mod D) with a random start and a stride coprime to D.
+Wall time around each call with the stream synchronised (host tables and uploads of the call included); the first call of
+a process runs on a small context so that no timed call loads code objects.
+
+Kernel times come from a run of their own per (shape, share): this tool starts itself under
+`rocprofv3 --kernel-trace` (--child) and sums, per kernel, the dispatches of the one timed call -- from the last
+holes_scan_kernel dispatch on -- and of the lc_model_predict that follows it.  One JSON line.
+
+    python tools/incomplete_bench.py [--configs northstar,d32] [--shares 0,1,10,100] [--reps 2] [--no-kernels]"""
+import argparse
+import csv
+import json
+import math
+import subprocess
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tools"))
+import bench  # noqa: E402
+from libcluster_amd import capi  # noqa: E402
+from predict_bench import _data, _device_name  # noqa: E402
+
+KERNELS = ("holes_scan_kernel", "holes_fill_kernel", "estep_wide_kernel", "estep_kernel", "predict_holes_kernel",
+           "predict_rows_kernel")
+
+
+def _model(name):
+    cfg = bench.CONFIGS[name]
+    N, D, K, seed = cfg["N"], cfg["D"], cfg["K"], cfg["seed"]
+    mu, L = bench.mixture(D, K, seed)
+    with capi.Context(0) as tr:
+        _data(tr, 400_000, D, K, mu, L, seed, N)  # rows N .. of the stream: not the ones scored
+        _, _, m = tr.vbem(capi.W_DIRICHLET, fixed_iters=3)
+        m.release_data()
+    with capi.Context(0) as ctx:
+        _data(ctx, N, D, K, mu, L, seed, 0)
+        X = ctx.get_rows(0, 0, N)
+    warm = X[:1000].copy()
+    warm[::3, 1] = np.nan
+    m.predict_incomplete(warm)  # (code objects, allocations)
+    m.predict(warm[1::3])
+    return m, X, (N, D, K)
+
+
+def _punch(X, share, seed):
+    """a copy of X with 1 ... 8 NaNs in about share of the rows -> (rows, number of hole rows, number of holes)"""
+    N, D = X.shape
+    rng = np.random.default_rng(seed)
+    Xh = X.copy()
+    rows = np.flatnonzero(rng.random(N) < share) if share < 1.0 else np.arange(N)
+    top = min(capi.HOLES_MAX, D - 1)
+    nb = rng.integers(1, top + 1, rows.size)
+    start = rng.integers(0, D, rows.size)
+    strides = np.array([s for s in range(1, D) if math.gcd(s, D) == 1] or [1])
+    stride = strides[rng.integers(0, strides.size, rows.size)]
+    for i in range(top):
+        sel = nb > i
+        Xh[rows[sel], (start[sel] + i * stride[sel]) % D] = np.nan
+    return Xh, int(rows.size), int(nb.sum())
+
+
+def _timed(ctx, f):
+    ctx.synchronize()
+    t0 = time.perf_counter()
+    f()
+    ctx.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def _wall(m, X, share, reps, seed):
+    Xh, nrows, nholes = _punch(X, share, seed)
+    t, tp = [], []
+    with capi.Context(0) as ctx:
+        for _ in range(reps):
+            ctx.set_data(Xh)
+            t.append(_timed(ctx, lambda: m.predict_incomplete_context(ctx)))
+        got = ctx.get_completed(0, 0, min(X.shape[0], 4096))
+        ctx.set_data(X)
+        for _ in range(reps):
+            tp.append(_timed(ctx, lambda: m.predict_context(ctx)))
+    head = Xh[: got.rows.shape[0]]
+    ok = bool(np.isfinite(got.rows).all() and np.isfinite(got.logp).all()
+              and np.array_equal(got.count, np.isnan(head).sum(axis=1)) and np.array_equal(got.rows[~np.isnan(head)], head[~np.isnan(head)]))
+    return {"hole_rows": nrows, "holes": nholes, "incomplete_ms": round(float(np.median(t)), 3),
+            "predict_ms": round(float(np.median(tp)), 3), "check_ok": ok}
+
+
+def _short(name):
+    for k in KERNELS:
+        if k in name:
+            return k
+    return None
+
+
+def _kernel_times(name, share):
+    """this tool under rocprofv3 --kernel-trace: the kernels of one timed call and of the lc_model_predict after it"""
+    with tempfile.TemporaryDirectory() as d:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "kt", "--", sys.executable,
+               str(Path(__file__).resolve()), "--child", name, str(share)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        traces = sorted(Path(d).rglob("*kernel_trace.csv"))
+        if r.returncode != 0 or not traces:
+            return {"error": (r.stderr or r.stdout)[-400:]}
+        rows = sorted(csv.DictReader(open(traces[-1])), key=lambda x: int(x["Start_Timestamp"]))
+    names = [_short(x["Kernel_Name"]) for x in rows]
+    scans = [i for i, n in enumerate(names) if n == "holes_scan_kernel"]
+    if not scans:
+        return {"error": "no holes_scan_kernel dispatch in the trace"}
+    call, after, seen_end = {}, {}, False
+    for x, n in list(zip(rows, names))[scans[-1]:]:
+        if n is None:
+            continue
+        ms = (int(x["End_Timestamp"]) - int(x["Start_Timestamp"])) / 1e6
+        dst = after if seen_end else call
+        dst[n] = round(dst.get(n, 0.0) + ms, 4)
+        seen_end = seen_end or n == "predict_holes_kernel"
+    return {"incomplete": call, "predict": after}
+
+
+def _child(name, share):
+    m, X, _ = _model(name)
+    Xh, _, _ = _punch(X, share / 100.0, 7)
+    with capi.Context(0) as ctx:
+        ctx.set_data(Xh)
+        m.predict_incomplete_context(ctx)
+        ctx.set_data(X)
+        m.predict_context(ctx)
+        ctx.synchronize()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="northstar,d32")
+    ap.add_argument("--shares", default="0,1,10,100", help="per cent of the rows that hold holes")
+    ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--child", nargs=2, metavar=("CONFIG", "SHARE"))
+    a = ap.parse_args()
+    if a.child:
+        _child(a.child[0], float(a.child[1]))
+        return
+    res, kernels = {}, {}
+    if not a.no_kernels:  # (first: the profiled runs are processes of their own, started before this one opens the device)
+        for name in a.configs.split(","):
+            kernels[name] = {s: _kernel_times(name, float(s)) for s in a.shares.split(",")}
+    for name in a.configs.split(","):
+        m, X, (N, D, K) = _model(name)
+        out = {"N": N, "D": D, "K": K, "reps": a.reps, "shares": {}}
+        for s in a.shares.split(","):
+            e = _wall(m, X, float(s) / 100.0, a.reps, 7)
+            if e["hole_rows"]:
+                e["us_per_hole_row_over_predict"] = round((e["incomplete_ms"] - e["predict_ms"]) * 1e3 / e["hole_rows"], 4)
+            out["shares"][s] = e
+            if name in kernels:
+                e["kernels_ms"] = kernels[name][s]
+        m.close()
+        del X
+        res[name] = out
+    print(json.dumps({"tool": "incomplete_bench", "device": _device_name(), "results": res}))
+
+
+if __name__ == "__main__":
+    main()
