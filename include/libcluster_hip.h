@@ -206,6 +206,11 @@ int lc_ctx_set_speck_skip(lc_ctx* ctx, int on);
 /* How many statistics passes of this context ran the skipping kernel, and how many the probe sent to the dense one
  * (either pointer may be NULL). */
 int lc_ctx_speck_passes(lc_ctx* ctx, int64_t* skipping, int64_t* dense);
+/* How many of the skipping passes took the list route: at D <= 64 (a padded width of 64 columns), where the probe finds
+ * that at least 58 of every 64 sampled rows keep values of exactly one cluster quad, the pass first writes, per row
+ * chunk and quad, the list of the rows that keep a value of that quad, and then sums every list on its own.  Same records,
+ * same bound; lc_ctx_set_speck_skip(ctx, 0) turns it off with the rest. */
+int lc_ctx_speck_list_passes(lc_ctx* ctx, int64_t* lists);
 
 /* Device and page-locked blocks released by contexts are cached for re-use (the split search builds a context per
  * attempt); this returns all of them to the driver. */

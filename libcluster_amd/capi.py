@@ -201,6 +201,7 @@ def lib() -> C.CDLL:
     L.lc_ctx_set_skip_zero.argtypes = [C.c_void_p, C.c_int]
     L.lc_ctx_set_speck_skip.argtypes = [C.c_void_p, C.c_int]
     L.lc_ctx_speck_passes.argtypes = [C.c_void_p, c_int64_p, c_int64_p]
+    L.lc_ctx_speck_list_passes.argtypes = [C.c_void_p, c_int64_p]
     L.lc_ctx_get_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p]
     L.lc_ctx_set_qz.argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_int, C.c_int64, C.c_int64]
     L.lc_ctx_get_qz.argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_int64, C.c_int64]
@@ -410,6 +411,12 @@ class Context:
         a, b = C.c_int64(), C.c_int64()
         check(lib().lc_ctx_speck_passes(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def speck_list_passes(self):
+        """-> how many of the skipping passes summed per-quad row lists (the list route)"""
+        a = C.c_int64()
+        check(lib().lc_ctx_speck_list_passes(self._h, C.byref(a)))
+        return a.value
 
     def set_sharding(self, whole_groups: bool):
         check(lib().lc_ctx_set_sharding(self._h, int(whole_groups)))

@@ -475,6 +475,14 @@ int lc_ctx_speck_passes(lc_ctx* ctx, int64_t* skipping, int64_t* dense) {
   });
 }
 
+int lc_ctx_speck_list_passes(lc_ctx* ctx, int64_t* lists) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    need(lists, "lists");
+    *lists = ctx->impl.speck_passes_lists();
+  });
+}
+
 int lc_ctx_get_rows(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* out) {
   return guarded([&] {
     need(ctx, "ctx");

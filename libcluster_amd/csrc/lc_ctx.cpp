@@ -1212,20 +1212,28 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
     const bool listed = a.mode == lck::SS_WORK_LIST;  // sparse work list instead of the dense (chunk, slice) grid
     const int nchunks = plan.nchunks, KR = plan.KR, extra = plan.extra;
     a.skip_listed = listed && skip_zero_;
+    bool lists = false;  // the pass runs over per-quad row lists
     if (speck_skip_ && plan.route == lck::SS_FEAT && NP_ >= lck::SPECK_PROBE_MIN_ROWS) {
       // the selector: skip only where the probe finds at least a quarter of the sampled pairs skippable
-      speck_active_.reserve(1);
-      int64_t pairs = 0;
-      int active = 0;
-      LC_HIP(lck::launch_speck_probe(a.qZ, a.ldq, K, NP_, speck_active_.p, &pairs, stream_));
-      LC_HIP(hipMemcpyAsync(&active, speck_active_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
+      speck_active_.reserve(2);
+      int64_t pairs = 0, rows = 0;
+      int counts2[2] = {0, 0};
+      LC_HIP(lck::launch_speck_probe(a.qZ, a.ldq, K, NP_, speck_active_.p, &pairs, stream_, &rows));
+      LC_HIP(hipMemcpyAsync(counts2, speck_active_.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream_));
       LC_HIP(hipStreamSynchronize(stream_));
+      const int active = counts2[0];
       // sorted batches (mode 2) where at most half of the sampled pairs are kept: with more, few batches can be sorted (a row
       // that keeps two quads leaves its batch in order) and the sort's barrier is paid for nothing -- and only below D = 128,
       // where two blocks share a compute unit: alone on its unit a block idles the matrix pipe at that barrier
       const bool sort_pays = 2 * (int64_t)active <= pairs && DP < 128;
       a.speck_skip = !lck::speck_probe_says_skip(active, pairs) ? 0 : sort_pays ? lck::speck_skip_mode() : 1;
       (a.speck_skip ? speck_skipping_ : speck_dense_) += 1;
+      // the list route: a pass that skips, at least 58 of 64 of whose sampled rows keep exactly ONE quad (measured:
+      // speck_probe_says_lists) -- each of those is touched once by one block; a soft row is summed once per quad it keeps
+      // (the D < 128 rule above belongs to the sort's barrier and does not apply)
+      lists = a.speck_skip != 0 && a.mode == lck::SS_DENSE && lck::speck_lists_enabled() && lck::suffstat_list_instance(DP, DC_) &&
+              lck::speck_probe_says_lists(counts2[1], rows);
+      if (lists) speck_lists_ += 1;
     }
     const int nrec = listed ? build_sparse_worklist(smask, K, plan, a) : nchunks * KR;
     sspart_reserve((size_t)std::max(nrec, 1) * SS);
@@ -1242,7 +1250,13 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
     a.partial = sspart_.p;
     a.nchunks = nchunks;
     a.chunk_rows = plan.chunk_rows;
-    timed(Timed::Suffstat, [&] { LC_HIP(lck::launch_suffstat(a, plan, stream_)); });
+    if (lists) {
+      const size_t lbytes = lck::ss_list_layout(nchunks, plan.chunk_rows, K).bytes;
+      sslists_.reserve(lbytes);
+      a.speck_skip = 0;  // (the flag belongs to launch_suffstat's instances)
+      timed(Timed::Suffstat, [&] { LC_HIP(lck::launch_suffstat_lists(a, plan, sslists_.p, lbytes, stream_)); });
+    } else
+      timed(Timed::Suffstat, [&] { LC_HIP(lck::launch_suffstat(a, plan, stream_)); });
     if (listed)
       LC_HIP(lck::launch_reduce_records(sspart_.p, SS, K, sskptr_, sskrec_, ssout_.p, stream_));
     else if (extra > 0) {

@@ -168,6 +168,8 @@ class Context {
   // statistics passes of this context that ran the skipping instance / that the probe sent to the dense one
   int64_t speck_passes_skipping() const { return speck_skipping_; }
   int64_t speck_passes_dense() const { return speck_dense_; }
+  // ... and how many of the skipping ones took the list route (per-quad row lists, lck::launch_suffstat_lists)
+  int64_t speck_passes_lists() const { return speck_lists_; }
   bool group_sharded() const { return group_sharded_ && distributed(); }
   // a context for a sub-problem of this one: same device, stream and all-reduce hook
   void inherit_comm(const Context& parent) {
@@ -387,8 +389,9 @@ class Context {
   bool group_sharded_ = false;
   bool skip_zero_ = false;
   bool speck_skip_ = true;
-  int64_t speck_skipping_ = 0, speck_dense_ = 0;
+  int64_t speck_skipping_ = 0, speck_dense_ = 0, speck_lists_ = 0;
   DevBuf<int> speck_active_;
+  DevBuf<unsigned char> sslists_;  // the row lists of a list pass (lck::ss_list_layout: about 2 bytes per row and cluster quad)
 
   int J_ = 0, D_ = 0, DP_ = 0;
   int DC_ = 0;  // active width of the Gauss-Wishart E-step / feature-GEMM statistics (lck::estep_active_width): DP_ - 8 or DP_

@@ -205,8 +205,41 @@ hipError_t launch_suffstat(const SuffstatLaunch& a, const SuffstatPlan& p, hipSt
 // nothing is 10 % slower than the dense instance).  Integer counts of a fixed sample: a deterministic function of qZ.
 constexpr int SPECK_PROBE_STEPS = 4096;
 constexpr int64_t SPECK_PROBE_MIN_ROWS = 4096;  // below: no probe, the dense instance
-hipError_t launch_speck_probe(const double* qZ, int64_t ldq, int K, int64_t NP, int* active, int64_t* pairs, hipStream_t stream);
+// active[1] (zeroed here too) counts the sampled ROWS that keep a value of exactly one quad -- the rows a list pass (below)
+// touches once; *rows (host, optional) = the rows looked at.  K > 256 (a step's quads no longer sit in one wave): not counted.
+hipError_t launch_speck_probe(const double* qZ, int64_t ldq, int K, int64_t NP, int* active, int64_t* pairs, hipStream_t stream,
+                              int64_t* rows = nullptr);
 inline bool speck_probe_says_skip(int64_t active, int64_t pairs) { return pairs > 0 && 4 * (pairs - active) >= pairs; }
+// Does a skipping pass take the list route (below)?  At least LC_FT_LIST_SHARE64 / 64 of the sampled rows have to keep exactly
+// one quad (decided in lc_kernels_suffstat.hip, a device source: tools/variants.py can build another share).
+bool speck_probe_says_lists(int64_t single, int64_t rows);
+
+// ---- the list route of a skipping pass (suffstat_list_kernel) -------------------------------------------
+// Every (row chunk, cluster quad) of the plan gets the ascending list of the chunk's rows that keep a value of the quad
+// ("not (q < SPECK_TAU)" in any of its clusters: a NaN is kept, pad rows are in no list, a soft row is in several), and one
+// block sums one list with the feature GEMM's arithmetic for a single quad.  Same partial records as launch_suffstat.
+// The buffer: [nchunks x nq] lengths (int), then [nchunks x nq] segments of chunk_rows chunk-local row offsets each -- a
+// segment can hold every row of its chunk, so no list overflows whatever qZ holds -- as 16-bit values while a chunk has at
+// most 65536 rows, 32-bit beyond.
+struct SsListLayout {
+  int nq;            // cluster quads of K
+  bool wide;         // 32-bit offsets
+  size_t ent_off;    // byte offset of the segments
+  size_t bytes;      // of the whole buffer
+};
+inline SsListLayout ss_list_layout(int nchunks, int64_t chunk_rows, int K) {
+  SsListLayout l{(K + 3) / 4, chunk_rows > 65536, 0, 0};
+  l.ent_off = ((size_t)nchunks * l.nq * sizeof(int) + 15) / 16 * 16;
+  l.bytes = l.ent_off + (size_t)nchunks * l.nq * (size_t)chunk_rows * (l.wide ? 4 : 2);
+  return l;
+}
+bool suffstat_list_instance(int DP, int DC);  // a suffstat_list_kernel exists for this width (DC = 0: DP)
+bool speck_lists_enabled();                   // false in a build with -DLC_FT_SPECK_LISTS=0 (tools/variants.py)
+// a (dense, SS_FEAT) launch as launch_suffstat takes it, with its plan; lists: ss_list_layout(...).bytes of device memory.
+// Both refuse (hipErrorInvalidValue, nothing launched) a launch that is not the plan's, a route other than the feature
+// GEMM's, a width without an instance and a buffer that is too small.  _build: the lists alone; the other: lists + sums.
+hipError_t launch_suffstat_list_build(const SuffstatLaunch& a, const SuffstatPlan& p, void* lists, size_t bytes, hipStream_t stream);
+hipError_t launch_suffstat_lists(const SuffstatLaunch& a, const SuffstatPlan& p, void* lists, size_t bytes, hipStream_t stream);
 // SuffstatLaunch::speck_skip of a pass that skips: 2 (sorted batches); 1 in a build with -DLC_FT_SPECK_SORT=0 (decided in
 // lc_kernels_suffstat.hip, a device source, so that tools/variants.py can build the unsorted rule for a same-visit A/B)
 int speck_skip_mode();
@@ -296,6 +329,16 @@ __host__ __device__ __attribute__((always_inline)) constexpr void ft_deal(int DP
     *t0 = t;
     *nt = tiles - t < tpw ? (tiles - t > 0 ? tiles - t : 0) : tpw;
   }
+}
+// The list kernel (one cluster quad per block): ALL tiles of the width in one 8-wave block, dealt per SIMD as above --
+// D = 64: 135 tiles = 34 34 34 33 per SIMD = waves of 17 + 17, the last 17 + 16.  ftl_tpw: tiles of the fuller waves; a
+// wave with one fewer runs an idle tile (1 * 1, not stored) on the one SIMD that has a slot to spare.
+__host__ __device__ constexpr int ftl_tpw(int DC) { return ((ft_tiles(DC) + 3) / 4 + 1) / 2; }
+__host__ __device__ __attribute__((always_inline)) constexpr void ft_deal_one(int DC, int wave, int* t0, int* nt) {
+  const int tiles = ft_tiles(DC), s = wave & 3, l = tiles / 4, r = tiles % 4;
+  const int load = l + (s < r ? 1 : 0), first = s * l + (s < r ? s : r);
+  *t0 = first + (wave < 4 ? 0 : (load + 1) / 2);
+  *nt = wave < 4 ? (load + 1) / 2 : load / 2;
 }
 // the smallest tile count of any wave (the 8-wave deal: ft_tpw or one fewer)
 __host__ __device__ constexpr int ft_nt_min(int DP, int DC, int NQ) {

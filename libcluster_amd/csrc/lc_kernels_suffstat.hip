@@ -1059,36 +1059,55 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
 }
 
 // launch_speck_probe: one thread per (sampled step, cluster quad), one atomic per wave
+// (a step's quads sit in nqp consecutive lanes, nqp = the power of two >= nq: lanes c >= nq idle.  The second count -- rows
+// that keep exactly one quad -- is a popcount over those lanes of the row's "kept" ballot; nqp > 64: not counted)
 __global__ void __launch_bounds__(256) speck_probe_kernel(const double* qZ, int64_t ldq, int K, int64_t stride, int nsteps, int nq,
-                                                           int* active) {
+                                                           int nqp, int* active) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  bool keep = false;
-  if (t < (int64_t)nsteps * nq) {
-    const int c = (int)(t % nq);
-    const int64_t row = 4 * stride * (t / nq);
+  const int c = (int)(t % nqp);
+  unsigned rk = 0;  // bit i: row i of the step keeps a value of quad c
+  if (t / nqp < nsteps && c < nq) {
+    const int64_t row = 4 * stride * (t / nqp);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int k = 4 * c + i;
       if (k < K) {
         const double2* qp = reinterpret_cast<const double2*>(qZ + (int64_t)k * ldq + row);
         const double2 v0 = qp[0], v1 = qp[1];
-        keep = keep || !(v0.x < SPECK_TAU) || !(v0.y < SPECK_TAU) || !(v1.x < SPECK_TAU) || !(v1.y < SPECK_TAU);
+        rk |= (!(v0.x < SPECK_TAU) ? 1u : 0u) | (!(v0.y < SPECK_TAU) ? 2u : 0u) | (!(v1.x < SPECK_TAU) ? 4u : 0u) |
+              (!(v1.y < SPECK_TAU) ? 8u : 0u);
       }
     }
   }
-  const unsigned long long b = __ballot(keep);
-  if ((threadIdx.x & 63) == 0 && b != 0) atomicAdd(active, __popcll(b));
+  const int lane = threadIdx.x & 63;
+  const unsigned long long b = __ballot(rk != 0);
+  if (lane == 0 && b != 0) atomicAdd(active, __popcll(b));
+  if (nqp <= 64) {
+    const unsigned long long grp = (nqp == 64 ? ~0ull : ((1ull << nqp) - 1ull)) << (lane & ~(nqp - 1));
+    int single = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned long long br = __ballot((rk >> i) & 1u);
+      single += __popcll(__ballot(c == 0 && __popcll(br & grp) == 1));
+    }
+    if (lane == 0 && single != 0) atomicAdd(active + 1, single);
+  }
 }
-hipError_t launch_speck_probe(const double* qZ, int64_t ldq, int K, int64_t NP, int* active, int64_t* pairs, hipStream_t stream) {
+hipError_t launch_speck_probe(const double* qZ, int64_t ldq, int K, int64_t NP, int* active, int64_t* pairs, hipStream_t stream,
+                              int64_t* rows) {
   const int64_t steps = NP / 4;
   *pairs = 0;
-  if (hipError_t e = hipMemsetAsync(active, 0, sizeof(int), stream); e != hipSuccess) return e;
+  if (rows) *rows = 0;
+  if (hipError_t e = hipMemsetAsync(active, 0, 2 * sizeof(int), stream); e != hipSuccess) return e;
   if (steps < 1 || K < 1) return hipSuccess;
   const int nsteps = (int)(steps < SPECK_PROBE_STEPS ? steps : SPECK_PROBE_STEPS), nq = (K + 3) / 4;
   const int64_t stride = steps / nsteps;  // (the last sampled step: stride * (nsteps - 1) < steps)
+  int nqp = 1;
+  while (nqp < nq) nqp *= 2;
   *pairs = (int64_t)nsteps * nq;
-  hipLaunchKernelGGL(speck_probe_kernel, dim3((unsigned)((*pairs + 255) / 256)), dim3(256), 0, stream, qZ, ldq, K, stride, nsteps, nq,
-                     active);
+  if (rows && nqp <= 64) *rows = 4 * (int64_t)nsteps;
+  hipLaunchKernelGGL(speck_probe_kernel, dim3((unsigned)(((int64_t)nsteps * nqp + 255) / 256)), dim3(256), 0, stream, qZ, ldq, K, stride,
+                     nsteps, nq, nqp, active);
   return hipGetLastError();
 }
 
@@ -1153,6 +1172,293 @@ static hipError_t launch_ss_feat(const SuffstatLaunch& a, hipStream_t stream) {
     case 128: return launch_ss_feat_w<128>(a, stream);
   }
   return hipErrorInvalidValue;
+}
+
+// ===========================================================================
+// The list route of a skipping pass: per-quad row lists, one block per list
+// ===========================================================================
+// suffstat_feat_kernel<..., SPECK> decides what to skip per (4-row step, quad) inside a walk over ALL rows with all eight
+// quads' accumulators live; once the rows are hard the work that matters is one (row, quad) pair per row.  Here a first
+// kernel writes, per (row chunk, quad), the ascending list of the rows that keep a value of the quad, and a second one
+// sums one list per block: the feature GEMM for NQ = 1 over gathered rows, all tiles of the width in one block (X staged
+// once), no masks and no tests in the loop.  A cluster's accumulator sees its kept rows in ascending order, four per MFMA
+// as ever -- the terms of the dense pass minus specks -- so the records equal those of the other skipping modes bit for bit
+// wherever those equal the dense ones.
+// -DLC_FT_SPECK_LISTS=0 (tools/variants.py): the context ignores the route
+#ifndef LC_FT_SPECK_LISTS
+#define LC_FT_SPECK_LISTS 1
+#endif
+#ifndef LC_FTL_BR
+#define LC_FTL_BR 48  // rows per staged batch of the list kernel (64: the second buffer leaves the 16-bit offset of a ds_read)
+#endif
+bool speck_lists_enabled() { return LC_FT_SPECK_LISTS != 0; }
+// Share of one-quad rows (in 64ths) from which a skipping pass takes the list route.  A row that keeps several quads is
+// gathered and multiplied once per quad; with the other rows soft in EVERY quad the list pass loses to the sorted instance
+// at 56 / 64 (11.19 against 10.61 ms at the north star) and wins at 58 / 64 (10.09 against 10.61): DESIGN 4.2b has the sweep.
+#ifndef LC_FT_LIST_SHARE64
+#define LC_FT_LIST_SHARE64 58
+#endif
+bool speck_probe_says_lists(int64_t single, int64_t rows) { return rows > 0 && 64 * single >= (int64_t)LC_FT_LIST_SHARE64 * rows; }
+bool suffstat_list_instance(int DP, int DC) { return DP == 64 && (DC == 0 || DC == 64 || DC == 56); }
+
+// One block per row chunk walks the chunk 256 rows at a time, quads in groups of 32 (128 columns of qZ, each read coalesced,
+// every column once).  Per tile and quad: a ballot of the rows that keep the quad; the four waves' counts meet in LDS, lane c
+// of every wave carries the running length of quad c's list, and a row's place is that base + the counts of the waves before
+// its own + its rank in the ballot: ascending row order, no atomics at all.  A segment holds chunk_rows entries.
+template <typename IT>
+__global__ void __launch_bounds__(256) ss_list_build_kernel(const double* __restrict__ qZ, int64_t ldq, int K, int64_t NP,
+                                                             int64_t chunk_rows, int nq, int* __restrict__ lens, IT* __restrict__ ent) {
+  __shared__ int wcnt[2][32][4];
+  const int chunk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t r0 = (int64_t)chunk * chunk_rows;
+  const int64_t r1 = (r0 + chunk_rows) < NP ? (r0 + chunk_rows) : NP;
+  if (r0 >= r1) {
+    for (int c = tid; c < nq; c += 256) lens[(int64_t)chunk * nq + c] = 0;
+    return;
+  }
+  for (int q0 = 0; q0 < nq; q0 += 32) {
+    const int nqg = nq - q0 < 32 ? nq - q0 : 32;
+    int base = 0, par = 0;
+    for (int64_t t0 = r0; t0 < r1; t0 += 256, par ^= 1) {
+      const int64_t row = t0 + tid;
+      const bool valid = row < r1;
+      const double* qr = qZ + (valid ? row : r1 - 1);  // (rows past the chunk: a valid address, the value is not used)
+      unsigned m = 0;
+      for (int c8 = 0; c8 < nqg; c8 += 8) {  // 32 loads in flight per thread
+        double v[32];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+          const int k = 4 * (q0 + c8) + i;
+          v[i] = qr[(int64_t)(k < K ? k : K - 1) * ldq];
+        }
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+          const int k = 4 * (q0 + c8) + i;
+          if (valid && k < K && !(v[i] < SPECK_TAU)) m |= 1u << (c8 + i / 4);
+        }
+      }
+      int mycnt = 0;
+      for (int c = 0; c < nqg; ++c) {
+        const unsigned long long bal = __ballot((m >> c) & 1u);
+        if (lane == c) mycnt = __popcll(bal);
+      }
+      if (lane < nqg) wcnt[par][lane][wave] = mycnt;
+      __syncthreads();  // (one barrier per tile: the counts alternate between two buffers)
+      int mybase = 0;
+      if (lane < nqg) {
+        int tot = 0, before = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          const int n = wcnt[par][lane][w];
+          before += w < wave ? n : 0;
+          tot += n;
+        }
+        mybase = base + before;
+        base += tot;
+      }
+      for (int c = 0; c < nqg; ++c) {
+        const unsigned long long bal = __ballot((m >> c) & 1u);
+        const int at = __shfl(mybase, c) + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+        if ((m >> c) & 1u) ent[((int64_t)chunk * nq + q0 + c) * chunk_rows + at] = (IT)(row - r0);
+      }
+    }
+    if (wave == 0 && lane < nqg) lens[(int64_t)chunk * nq + q0 + lane] = base;
+    __syncthreads();  // (the next group starts with the first count buffer again)
+  }
+}
+
+// One block = one (row chunk, cluster quad): 8 waves, all tiles of the width (ft_deal_one).  A staged batch is LC_FTL_BR rows
+// of the list: X rows gathered whole (row-major: one contiguous row each), the quad's four q values per row, zeros with
+// q = 0 past the list's end.  The row offsets of a batch are fetched TWO batches ahead (their loads would otherwise stand
+// in front of the gather's), the rows one batch ahead into registers.  Step loop: the step's products (fragments read a
+// whole step ahead, under the previous step's MFMAs), then its MFMAs -- one v_mul_f64 per MFMA, and nothing else.
+template <int DP, int DC, typename IT>
+__global__ void __launch_bounds__(512, 2) suffstat_list_kernel(SuffstatLaunch a, const int* __restrict__ lens, const IT* __restrict__ ent,
+                                                                int nq) {
+  static_assert(DC % 4 == 0 && DC <= DP && DC > DP - 16, "active width");
+  constexpr int NTHR = 512, BR = LC_FTL_BR, LD = lds_row_stride(DP), QLD = 4, XBUF = BR * LD, QBUF = BR * QLD;
+  constexpr int ONE = DP, NT = ftl_tpw(DC);
+  constexpr int TPR = DP / 2, RPP = NTHR / TPR, NPRE = BR / RPP;
+  static_assert(LD > DP && NTHR % TPR == 0 && BR % RPP == 0 && BR % 4 == 0 && 4 * BR <= NTHR, "staging");
+  static_assert((XBUF + (BR - 4) * LD + LD) * 8 <= 65536, "fragment reads: one address register per tile, the rest immediate");
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  double* xbuf = lds;             // [2][BR][LD]
+  double* qbuf = lds + 2 * XBUF;  // [2][BR][4]: q[row][cluster of the quad], clusters past K zero
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int hi = lane >> 4, blk = (lane >> 2) & 3, lo2 = lane & 3;
+  const int chunk = blockIdx.x / nq, quad = blockIdx.x % nq;
+  const int64_t r0 = (int64_t)chunk * a.chunk_rows;
+  const int len = lens[blockIdx.x];
+  const IT* li = ent + (int64_t)blockIdx.x * a.chunk_rows;
+  int T0 = 0, nt = 0;
+  ft_deal_one(DC, wave, &T0, &nt);
+  const double* pu[NT];
+  const double* pw[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const FtFeature f = t < nt ? ft_feature(DC, ONE, 16 * (T0 + t) + lo2 + 4 * blk) : FtFeature{ONE, ONE, FT_SPARE};
+    pu[t] = xbuf + hi * LD + f.u;
+    pw[t] = xbuf + hi * LD + f.w;
+  }
+  double acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = 0.0;
+
+  const int xr0 = tid / TPR, xc2 = tid % TPR, qrow = tid / 4, qcl = tid % 4;
+  const bool qthr = tid < 4 * BR;
+  const int kq = 4 * quad + qcl;
+  const double* qcol = a.qZ + (int64_t)(kq < a.K ? kq : a.K - 1) * a.ldq + r0;
+  int xi[NPRE], qi = -1;
+  double pre[NPRE][2], qpre = 0.0;
+  auto iload = [&](int p0) {  // list places p0 ... p0 + BR - 1 -> row offsets (-1 past the end)
+#pragma unroll
+    for (int i = 0; i < NPRE; ++i) {
+      const int p = p0 + xr0 + i * RPP;
+      xi[i] = p < len ? (int)li[p] : -1;
+    }
+    qi = qthr && p0 + qrow < len ? (int)li[p0 + qrow] : -1;
+  };
+  auto gload = [&]() {  // (every load is issued: a place past the end reads the chunk's first row and keeps zeros)
+#pragma unroll
+    for (int i = 0; i < NPRE; ++i) {
+      const double2 v = *reinterpret_cast<const double2*>(a.X + (r0 + (xi[i] < 0 ? 0 : xi[i])) * DP + 2 * xc2);
+      pre[i][0] = xi[i] < 0 ? 0.0 : v.x;
+      pre[i][1] = xi[i] < 0 ? 0.0 : v.y;
+    }
+    const double q = qcol[qi < 0 ? 0 : qi];
+    qpre = qi < 0 || kq >= a.K ? 0.0 : q;
+  };
+  auto lstore = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < NPRE; ++i)
+      *reinterpret_cast<double2*>(xbuf + buf * XBUF + (xr0 + i * RPP) * LD + 2 * xc2) = make_double2(pre[i][0], pre[i][1]);
+    if (qthr) qbuf[buf * QBUF + qrow * QLD + qcl] = qpre;
+  };
+  if (tid < 2 * BR) xbuf[(tid / BR) * XBUF + (tid % BR) * LD + ONE] = 1.0;
+  if (len > 0) {
+    iload(0);
+    gload();
+    iload(BR);
+    lstore(0);
+  }
+  __syncthreads();
+  const double* pq = qbuf + hi * QLD + lo2;
+  auto batch = [&](auto bsel) {
+    constexpr int B = decltype(bsel)::value, XO = B * XBUF, QO = B * QBUF;
+    double uf[NT], wf[NT], pp[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      uf[t] = pu[t][XO];
+      wf[t] = pw[t][XO];
+    }
+    double qa = pq[QO];
+#pragma unroll
+    for (int st = 0; st < BR / 4; ++st) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) pp[t] = uf[t] * wf[t];
+      const double qc = qa;
+      if (st + 1 < BR / 4) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          uf[t] = pu[t][XO + (st + 1) * 4 * LD];
+          wf[t] = pw[t][XO + (st + 1) * 4 * LD];
+        }
+        qa = pq[QO + (st + 1) * 4 * QLD];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) acc[t] = mfma4(qc, pp[t], acc[t]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  for (int p0 = 0; p0 < len; p0 += 2 * BR) {  // two batches per trip: the buffer index is a compile-time constant
+    const bool more1 = p0 + BR < len, more2 = p0 + 2 * BR < len;
+    if (more1) {
+      gload();
+      iload(p0 + 2 * BR);
+    }
+    batch(std::integral_constant<int, 0>{});
+    if (more1) lstore(1);
+    __syncthreads();
+    if (!more1) break;
+    if (more2) {
+      gload();
+      iload(p0 + 3 * BR);
+    }
+    batch(std::integral_constant<int, 1>{});
+    if (more2) lstore(0);
+    __syncthreads();
+  }
+
+  // ---- partial records, as suffstat_feat_kernel writes them (an empty list: exact zeros)
+  const int64_t SS = 1 + (int64_t)DP + (int64_t)DP * DP;
+  int wv = wave, T0e = 0, nte = 0;
+  asm volatile("" : "+v"(wv));  // (worked out again, not kept in registers across the step loop)
+  ft_deal_one(DC, wv, &T0e, &nte);
+  const int kk = 4 * quad + hi;
+  if (kk >= a.K) return;
+  double* out = a.partial + ((int64_t)chunk * a.KR + kk) * SS;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    if (t >= nte) continue;
+    const FtFeature f = ft_feature(DC, ONE, 16 * (T0e + t) + lo2 + 4 * blk);
+    if (f.kind == FT_SPARE) continue;
+    const double v = acc[t];
+    if (f.kind == FT_PRODUCT) {
+      double* S = out + 1 + DP;
+      S[(int64_t)f.u * DP + f.w] = v;
+      S[(int64_t)f.w * DP + f.u] = v;
+    } else if (f.kind == FT_LINEAR) {
+      out[1 + f.u] = v;
+    } else {
+      out[0] = v;
+    }
+  }
+}
+
+// the checks both launchers share; *lay: the buffer's layout
+static hipError_t ss_list_check(const SuffstatLaunch& a, const SuffstatPlan& p, const void* lists, size_t bytes, SsListLayout* lay) {
+  if (a.K <= 0 || p.nchunks <= 0 || !lists || !a.qZ || !a.X) return hipErrorInvalidValue;
+  if (p.route != SS_FEAT || a.mode != SS_DENSE || a.smask || a.items || p.extra != 0) return hipErrorInvalidValue;
+  if (a.nchunks != p.nchunks || a.chunk_rows != p.chunk_rows || a.KR != p.KR || a.KR != a.K) return hipErrorInvalidValue;
+  if (!suffstat_list_instance(a.DP, a.DC)) return hipErrorInvalidValue;
+  if (a.chunk_rows < 4 || a.chunk_rows % 4 || a.chunk_rows > (int64_t)1 << 30 || (int64_t)a.nchunks * a.chunk_rows < a.NP) return hipErrorInvalidValue;
+  *lay = ss_list_layout(a.nchunks, a.chunk_rows, a.K);
+  if ((int64_t)a.nchunks * lay->nq > (int64_t)1 << 30 || bytes < lay->bytes) return hipErrorInvalidValue;
+  return hipSuccess;
+}
+hipError_t launch_suffstat_list_build(const SuffstatLaunch& a, const SuffstatPlan& p, void* lists, size_t bytes, hipStream_t stream) {
+  SsListLayout lay;
+  if (hipError_t e = ss_list_check(a, p, lists, bytes, &lay); e != hipSuccess) return e;
+  int* lens = static_cast<int*>(lists);
+  void* ent = static_cast<char*>(lists) + lay.ent_off;
+  if (lay.wide)
+    hipLaunchKernelGGL(ss_list_build_kernel<unsigned>, dim3((unsigned)a.nchunks), dim3(256), 0, stream, a.qZ, a.ldq, a.K, a.NP,
+                       a.chunk_rows, lay.nq, lens, static_cast<unsigned*>(ent));
+  else
+    hipLaunchKernelGGL(ss_list_build_kernel<unsigned short>, dim3((unsigned)a.nchunks), dim3(256), 0, stream, a.qZ, a.ldq, a.K, a.NP,
+                       a.chunk_rows, lay.nq, lens, static_cast<unsigned short*>(ent));
+  return hipGetLastError();
+}
+template <int DP, int DC, typename IT>
+static hipError_t launch_ss_list_i(const SuffstatLaunch& a, const SsListLayout& lay, const void* lists, hipStream_t stream) {
+  constexpr int BR = LC_FTL_BR;
+  const size_t shmem = (size_t)(2 * BR * lds_row_stride(DP) + 2 * BR * 4) * sizeof(double);
+  auto kern = suffstat_list_kernel<DP, DC, IT>;
+  static LdsGrant grant;
+  if (hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(kern), shmem, grant); e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(a.nchunks * lay.nq)), dim3(512), shmem, stream, a, static_cast<const int*>(lists),
+                     reinterpret_cast<const IT*>(static_cast<const char*>(lists) + lay.ent_off), lay.nq);
+  return hipGetLastError();
+}
+hipError_t launch_suffstat_lists(const SuffstatLaunch& a, const SuffstatPlan& p, void* lists, size_t bytes, hipStream_t stream) {
+  SsListLayout lay;
+  if (hipError_t e = ss_list_check(a, p, lists, bytes, &lay); e != hipSuccess) return e;
+  if (hipError_t e = launch_suffstat_list_build(a, p, lists, bytes, stream); e != hipSuccess) return e;
+  const bool narrow = a.DC == 56;
+  if (lay.wide) return narrow ? launch_ss_list_i<64, 56, unsigned>(a, lay, lists, stream) : launch_ss_list_i<64, 64, unsigned>(a, lay, lists, stream);
+  return narrow ? launch_ss_list_i<64, 56, unsigned short>(a, lay, lists, stream)
+                : launch_ss_list_i<64, 64, unsigned short>(a, lay, lists, stream);
 }
 
 // ===========================================================================

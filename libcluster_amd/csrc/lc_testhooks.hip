@@ -851,6 +851,66 @@ LC_HOOK lcx_test_suffstat_speck(const double* X, int DP, int DC, i64 NP, const d
                        skip_listed, partial, npartial, fold, folded, nfolded, plan_out, speck_skip);
 }
 
+// lcx_test_suffstat_lists: the list route of a skipping pass on a dense launch (launch_suffstat_list_build alone with sums = 0,
+// launch_suffstat_lists otherwise; the launchers refuse what has no instance).  plan_out [7] as above.  The lists come back
+// as lens_out (io) [nlens >= nchunks * quads] and ent_out (io) [nent >= nchunks * quads * chunk_rows]: segment (chunk, quad)
+// starts at (chunk * quads + quad) * chunk_rows and only its first lens entries are written; -2: a length outside its segment.
+// partial (io), fold / folded (io) as in lc_test_suffstat.  (lcx_: bound by its own test file, like the hook above.)
+LC_HOOK lcx_test_suffstat_lists(const double* X, int DP, int DC, i64 NP, const double* qZ, int K, i64 ldq, int sums, double* partial,
+                                i64 npartial, int fold, double* folded, i64 nfolded, i64* plan_out, int* lens_out, i64 nlens, int* ent_out,
+                                i64 nent) {
+  if (!X || !qZ || !partial || !plan_out || !lens_out || !ent_out || K < 1 || K > 4096 || !gw_width_ok(DP, DC)) return -1;
+  if (NP < RG || NP % RG || NP > HOT_MAX_NRG * RG || ldq < NP || ldq % 2) return -1;
+  const i64 SS = lck::stat_stride(DP);
+  if (fold && (!sums || !folded || nfolded < (i64)K * SS)) return -1;
+  const lck::SuffstatPlan p = lck::suffstat_plan(DP, DC, NP, K, lck::SS_DENSE);
+  plan_out[0] = p.route, plan_out[1] = p.nchunks, plan_out[2] = p.chunk_rows, plan_out[3] = p.extra, plan_out[4] = p.klast0;
+  plan_out[5] = p.KR, plan_out[6] = p.clusters_per_block;
+  if (p.nchunks < 1 || p.chunk_rows < lck::SS_BR || p.chunk_rows % lck::SS_BR || (i64)p.nchunks * p.chunk_rows < NP) return -1;
+  const lck::SsListLayout lay = lck::ss_list_layout(p.nchunks, p.chunk_rows, K);
+  const i64 nseg = (i64)p.nchunks * lay.nq;
+  if (npartial < (i64)p.nchunks * p.KR * SS || nlens < nseg || nent < nseg * p.chunk_rows) return -1;
+  Scope s;
+  lck::SuffstatLaunch a{};
+  a.DP = DP;
+  a.DC = DC;
+  a.X = s.in(X, (size_t)NP * DP);
+  a.NP = NP;
+  a.qZ = s.in(qZ, (size_t)K * (size_t)ldq);
+  a.ldq = ldq;
+  a.K = K;
+  a.mode = lck::SS_DENSE;
+  a.rginfo = nullptr;
+  a.smask = nullptr;
+  a.partial = s.io(partial, (size_t)npartial);
+  a.nchunks = p.nchunks;
+  a.KR = p.KR;
+  a.chunk_rows = p.chunk_rows;
+  unsigned char* lists = s.scratch<unsigned char>(lay.bytes);
+  double* dfold = fold ? s.io(folded, (size_t)nfolded) : nullptr;
+  if (!s.ok()) return s.finish(hipSuccess);
+  hipError_t e = hipMemset(lists, 0xff, lay.bytes);
+  if (e == hipSuccess)
+    e = sums ? lck::launch_suffstat_lists(a, p, lists, lay.bytes, nullptr) : lck::launch_suffstat_list_build(a, p, lists, lay.bytes, nullptr);
+  if (e == hipSuccess && fold) e = lck::launch_reduce_partials(a.partial, p.nchunks, (i64)K * SS, dfold, nullptr);
+  const int rc = s.finish(e);
+  if (rc != 0) return rc;
+  std::vector<unsigned char> raw(lay.bytes);
+  if (hipMemcpy(raw.data(), lists, lay.bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  const int* lens = reinterpret_cast<const int*>(raw.data());
+  for (i64 g = 0; g < nseg; ++g)
+    if (lens[g] < 0 || lens[g] > p.chunk_rows) return -2;
+  for (i64 g = 0; g < nseg; ++g) {
+    lens_out[g] = lens[g];
+    for (int i = 0; i < lens[g]; ++i) {
+      const size_t at = (size_t)g * (size_t)p.chunk_rows + (size_t)i;
+      ent_out[at] = lay.wide ? (int)reinterpret_cast<const unsigned*>(raw.data() + lay.ent_off)[at]
+                             : (int)reinterpret_cast<const unsigned short*>(raw.data() + lay.ent_off)[at];
+    }
+  }
+  return 0;
+}
+
 // out [4] = fused_eligible, fused_plan's grid, compute units of the device, fused_record(DP, K)
 LC_HOOK lc_test_fused_plan(int DP, i64 nrg, int K, i64* out) {
   if (!out || K < 1 || K > 4096 || nrg < 0 || nrg > HOT_MAX_NRG || DP < 1 || DP > 1024) return -1;

@@ -160,7 +160,27 @@ def check(asm: str):
     return problems, seen
 
 
+def check_lists(asm: str):
+    """`--lists [file.s]`: every instance of the statistics pass's list route (suffstat_list_kernel, ss_list_build_kernel in
+    lc_kernels_suffstat.hip) is there and holds no scratch.  Not part of the default run: that file takes minutes to compile."""
+    scratch = dict(re.findall(r"\.amdhsa_kernel\s+(\S+)\s+\.amdhsa_group_segment_fixed_size\s+\d+\s+"
+                              r"\.amdhsa_private_segment_fixed_size\s+(\d+)", asm))
+    mine = {n: int(sz) for n, sz in scratch.items() if "suffstat_list_kernel" in n or "ss_list_build_kernel" in n}
+    problems = [f"{n}: {sz} bytes of scratch" for n, sz in mine.items() if sz]
+    for want in ("suffstat_list_kernelILi64ELi64E", "suffstat_list_kernelILi64ELi56E", "ss_list_build_kernel"):
+        if not any(want in n for n in mine):
+            problems.append(f"no instance {want} found")
+    return problems, len(mine)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--lists":
+        asm = Path(sys.argv[2]).read_text() if len(sys.argv) > 2 else device_asm("lc_kernels_suffstat.hip")
+        problems, n = check_lists(asm)
+        for q in problems:
+            print("ISA check:", q)
+        print(f"checked {n} list-route kernels: {'FAILED' if problems else 'ok'}")
+        sys.exit(1 if problems else 0)
     if len(sys.argv) > 2 and sys.argv[1] == "--mfma-asm":  # check 4 alone, on a given source file (or .s)
         p = Path(sys.argv[2])
         problems, nasm = check_mfma_into_asm(p.read_text() if p.suffix == ".s" else device_asm(src=p))
