@@ -263,23 +263,27 @@ struct FtFeature {
 };
 // (always inlined: behind the long unrolled step loops of the speck-skipping instances hipcc otherwise CALLS them from the
 //  epilogue, with ft_deal's two results in scratch)
+// the features behind the off-diagonal patches, g = 0 ...: diagonal products, linear features, N_k, spare slots
+__host__ __device__ __attribute__((always_inline)) constexpr FtFeature ft_feature_rest(int DC, int one, int g) {
+  const int ndiag = 10 * (DC / 4);
+  if (g < ndiag) {  // (i, j) of a diagonal block: (0,0) (0,1) (0,2) (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3)
+    const int b = 4 * (g / 10), e = g % 10;
+    const int i = e < 4 ? 0 : e < 7 ? 1 : e < 9 ? 2 : 3, i0 = e < 4 ? 0 : e < 7 ? 4 : e < 9 ? 7 : 9;
+    return {b + i, b + i + (e - i0), FT_PRODUCT};
+  }
+  g -= ndiag;
+  if (g < DC) return {g, one, FT_LINEAR};
+  return {one, one, g == DC ? FT_COUNT : FT_SPARE};
+}
 __host__ __device__ __attribute__((always_inline)) constexpr FtFeature ft_feature(int DC, int one, int f) {
-  const int noff = 16 * ft_offdiag(DC), ndiag = 10 * (DC / 4);
+  const int noff = 16 * ft_offdiag(DC);
   if (f < noff) {
     const int p = f / 16, r = f % 16;
     int ja = 1;
     while ((ja + 1) * ja / 2 <= p) ++ja;
     return {4 * (p - ja * (ja - 1) / 2) + (r & 3), 4 * ja + (r >> 2), FT_PRODUCT};
   }
-  f -= noff;
-  if (f < ndiag) {  // (i, j) of a diagonal block: (0,0) (0,1) (0,2) (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3)
-    const int b = 4 * (f / 10), e = f % 10;
-    const int i = e < 4 ? 0 : e < 7 ? 1 : e < 9 ? 2 : 3, i0 = e < 4 ? 0 : e < 7 ? 4 : e < 9 ? 7 : 9;
-    return {b + i, b + i + (e - i0), FT_PRODUCT};
-  }
-  f -= ndiag;
-  if (f < DC) return {f, one, FT_LINEAR};
-  return {one, one, f == DC ? FT_COUNT : FT_SPARE};
+  return ft_feature_rest(DC, one, f - noff);
 }
 // Waves per block.  The waves of a block share one staged batch, so 8 waves (one block per CU, longer batches) halve
 // the staging instructions and barriers per MFMA against 4 waves (two blocks per CU): D = 64, N = 10M, K = 32:
@@ -340,6 +344,55 @@ __host__ __device__ __attribute__((always_inline)) constexpr void ft_deal_one(in
   *t0 = first + (wave < 4 ? 0 : (load + 1) / 2);
   *nt = wave < 4 ? (load + 1) / 2 : load / 2;
 }
+// The list kernel's SHARED deal.  ft_deal_one hands a wave 17 consecutive tiles, and each reads both factors
+// of its product from LDS -- 35 fragment reads per 17 MFMAs, most of them the same `w` fragment again.  Here a wave's
+// off-diagonal tiles share a factor.  The DC / 4 = 16 column blocks are the vertices of K16 and the 120 off-diagonal 4 x 4
+// patches its edges, oriented as a circulant: block a owns {a, a + 1 ... a + 7 (mod 16)}, and the eight diameters {a, a + 8}
+// go to a < 8 -- blocks 0-7 own 8 edges, blocks 8-15 own 7, every edge once.  Wave v takes the stars of blocks v and v + 8:
+//   tiles 0 ... S - 1  (S = ftl_split = 8): patch (v, v + 1 + t),               the SHARED factor column 4 v + blk
+//   tiles S ... P - 1  (P = ftl_paired = 15): patch (v + 8, v + 8 + 1 + t - S), the shared factor column 4 (v + 8) + blk
+//   tiles P, P + 1: "free" tiles 2 v and 2 v + 1 of ft_feature_rest (diagonal products, linear features, N_k; both factors
+//     read as before); free tile 15 does not exist, so wave 7 runs the idle 1 * 1 tile there: 34 34 34 33 tiles per SIMD as
+//     in ft_deal_one.
+// A paired tile's other factor sits in the lo2 position (column 4 o + lo2): the two access patterns of ft_feature.  u * w
+// commutes, so which block of a patch is the shared one changes no bit.  22 fragment reads per 17 MFMAs.
+// -DLC_FTL_SHARED=0 (tools/variants.py) restores ft_deal_one's deal.  Widths other than 64 keep it: DC = 56 has 14 blocks,
+// whose 7 + 6 stars fill seven waves of 13 tiles and leave the eighth with 13 free ones -- a second batch body.
+#ifndef LC_FTL_SHARED
+#define LC_FTL_SHARED 1
+#endif
+__host__ __device__ constexpr bool ftl_shared(int DC) { return LC_FTL_SHARED != 0 && DC == 64; }
+__host__ __device__ constexpr int ftl_paired(int DC) { return ftl_shared(DC) ? DC / 4 - 1 : 0; }  // paired tiles of a wave
+__host__ __device__ constexpr int ftl_split(int DC) { return ftl_shared(DC) ? DC / 8 : 0; }       // ... of its first star
+struct FtlFeature {
+  int u, w, kind;  // as FtFeature; a paired tile: u = the tile's own column (lo2 position), w = the shared one (blk position)
+  int shared;      // which shared fragment of the wave the tile uses: 0, 1; -1: none (both factors read)
+};
+// lane (lo2, blk) = l16 of tile t of wave `wave`, either deal: THE map of the list kernel (addresses and epilogue)
+__host__ __device__ __attribute__((always_inline)) constexpr FtlFeature ftl_feature(int DC, int one, int wave, int t, int l16) {
+  if (!ftl_shared(DC)) {
+    int t0 = 0, nt = 0;
+    ft_deal_one(DC, wave, &t0, &nt);
+    if (t >= nt) return {one, one, FT_SPARE, -1};
+    const FtFeature f = ft_feature(DC, one, 16 * (t0 + t) + l16);
+    return {f.u, f.w, f.kind, -1};
+  }
+  const int nb = DC / 4, S = ftl_split(DC), P = ftl_paired(DC);
+  if (t < P) {
+    const int second = t >= S ? 1 : 0, a = wave + second * S, o = (a + 1 + t - second * S) % nb;
+    return {4 * o + (l16 & 3), 4 * a + (l16 >> 2), FT_PRODUCT, second};
+  }
+  const FtFeature f = ft_feature_rest(DC, one, 16 * (2 * wave + t - P) + l16);
+  return {f.u, f.w, f.kind, -1};
+}
+// the wave's factor registers: paired tiles use register `shared`, the others one of their own behind the two
+__host__ __device__ constexpr int ftl_nw(int DC) { return ftl_shared(DC) ? 2 + ftl_tpw(DC) - ftl_paired(DC) : ftl_tpw(DC); }
+__host__ __device__ constexpr int ftl_wi(int DC, int t) {
+  return !ftl_shared(DC) ? t : t < ftl_split(DC) ? 0 : t < ftl_paired(DC) ? 1 : 2 + t - ftl_paired(DC);
+}
+static_assert(!ftl_shared(64) || (ftl_tpw(64) == ftl_paired(64) + 2 && 16 * 2 * 8 >= ft_features(64) - 16 * ft_offdiag(64)),
+              "shared deal: 8 waves of two stars and two free tiles");
+
 // the smallest tile count of any wave (the 8-wave deal: ft_tpw or one fewer)
 __host__ __device__ constexpr int ft_nt_min(int DP, int DC, int NQ) {
   int m = ft_tpw(DP, DC, NQ);

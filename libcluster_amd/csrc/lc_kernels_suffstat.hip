@@ -1267,7 +1267,10 @@ __global__ void __launch_bounds__(256) ss_list_build_kernel(const double* __rest
   }
 }
 
-// One block = one (row chunk, cluster quad): 8 waves, all tiles of the width (ft_deal_one).  A staged batch is LC_FTL_BR rows
+// One block = one (row chunk, cluster quad): 8 waves, all tiles of the width (ftl_feature: at DC = 64 the shared deal, a
+// wave's off-diagonal tiles are two stars that read their common factor once a step -- 22 fragment reads per 17 MFMAs where
+// ft_deal_one's deal takes 35; the products, their order per accumulator and the records are the same bit for bit).
+// A staged batch is LC_FTL_BR rows
 // of the list: X rows gathered whole (row-major: one contiguous row each), the quad's four q values per row, zeros with
 // q = 0 past the list's end.  The row offsets of a batch are fetched TWO batches ahead (their loads would otherwise stand
 // in front of the gather's), the rows one batch ahead into registers.  Step loop: the step's products (fragments read a
@@ -1290,15 +1293,20 @@ __global__ void __launch_bounds__(512, 2) suffstat_list_kernel(SuffstatLaunch a,
   const int64_t r0 = (int64_t)chunk * a.chunk_rows;
   const int len = lens[blockIdx.x];
   const IT* li = ent + (int64_t)blockIdx.x * a.chunk_rows;
-  int T0 = 0, nt = 0;
-  ft_deal_one(DC, wave, &T0, &nt);
+  // the wave's tiles (ftl_feature): tile t multiplies fragment t of `u` by fragment ftl_wi(t) of `w` -- one per tile in
+  // ft_deal_one's deal; in the shared deal one per star, read once a step, and one per free tile
+  constexpr int NW = ftl_nw(DC);
   const double* pu[NT];
-  const double* pw[NT];
+  const double* pw[NW];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    const FtFeature f = t < nt ? ft_feature(DC, ONE, 16 * (T0 + t) + lo2 + 4 * blk) : FtFeature{ONE, ONE, FT_SPARE};
+    const FtlFeature f = ftl_feature(DC, ONE, wave, t, lo2 + 4 * blk);
     pu[t] = xbuf + hi * LD + f.u;
-    pw[t] = xbuf + hi * LD + f.w;
+    int ow = hi * LD + f.w;
+    // (the shared deal: the two stars' fragments lie 32 columns apart and hipcc joins their reads into one ds_read2_b64,
+    //  which takes 8 cycles of the LDS array where two ds_read_b64 take 4 -- the offset is hidden from it)
+    if constexpr (ftl_shared(DC)) asm volatile("" : "+v"(ow));
+    pw[ftl_wi(DC, t)] = xbuf + ow;
   }
   double acc[NT];
 #pragma unroll
@@ -1345,24 +1353,25 @@ __global__ void __launch_bounds__(512, 2) suffstat_list_kernel(SuffstatLaunch a,
   const double* pq = qbuf + hi * QLD + lo2;
   auto batch = [&](auto bsel) {
     constexpr int B = decltype(bsel)::value, XO = B * XBUF, QO = B * QBUF;
-    double uf[NT], wf[NT], pp[NT];
+    double uf[NT], wf[NW], pp[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      uf[t] = pu[t][XO];
-      wf[t] = pw[t][XO];
-    }
+    for (int t = 0; t < NT; ++t) uf[t] = pu[t][XO];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) wf[i] = pw[i][XO];
     double qa = pq[QO];
+    // (the shared deal: without the fence hipcc joins every fragment's reads of steps 0 and 1 into a ds_read2st64_b64 --
+    //  8 LDS cycles where two ds_read_b64 take 4, once per fragment and batch)
+    if constexpr (ftl_shared(DC)) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int st = 0; st < BR / 4; ++st) {
 #pragma unroll
-      for (int t = 0; t < NT; ++t) pp[t] = uf[t] * wf[t];
+      for (int t = 0; t < NT; ++t) pp[t] = uf[t] * wf[ftl_wi(DC, t)];
       const double qc = qa;
       if (st + 1 < BR / 4) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          uf[t] = pu[t][XO + (st + 1) * 4 * LD];
-          wf[t] = pw[t][XO + (st + 1) * 4 * LD];
-        }
+        for (int t = 0; t < NT; ++t) uf[t] = pu[t][XO + (st + 1) * 4 * LD];
+#pragma unroll
+        for (int i = 0; i < NW; ++i) wf[i] = pw[i][XO + (st + 1) * 4 * LD];
         qa = pq[QO + (st + 1) * 4 * QLD];
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -1392,16 +1401,14 @@ __global__ void __launch_bounds__(512, 2) suffstat_list_kernel(SuffstatLaunch a,
 
   // ---- partial records, as suffstat_feat_kernel writes them (an empty list: exact zeros)
   const int64_t SS = 1 + (int64_t)DP + (int64_t)DP * DP;
-  int wv = wave, T0e = 0, nte = 0;
-  asm volatile("" : "+v"(wv));  // (worked out again, not kept in registers across the step loop)
-  ft_deal_one(DC, wv, &T0e, &nte);
+  int wv = wave;
+  asm volatile("" : "+v"(wv));  // (the map is worked out again, not kept in registers across the step loop)
   const int kk = 4 * quad + hi;
   if (kk >= a.K) return;
   double* out = a.partial + ((int64_t)chunk * a.KR + kk) * SS;
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    if (t >= nte) continue;
-    const FtFeature f = ft_feature(DC, ONE, 16 * (T0e + t) + lo2 + 4 * blk);
+    const FtlFeature f = ftl_feature(DC, ONE, wv, t, lo2 + 4 * blk);
     if (f.kind == FT_SPARE) continue;
     const double v = acc[t];
     if (f.kind == FT_PRODUCT) {

@@ -911,6 +911,26 @@ LC_HOOK lcx_test_suffstat_lists(const double* X, int DP, int DC, i64 NP, const d
   return 0;
 }
 
+// lcx_test_suffstat_list_deal: the list kernel's tile map (lck::ftl_feature) evaluated on the host, no device involved.
+// info [6] = shared deal at this width (0 / 1), waves, tiles per wave, ftl_paired, ftl_split, the ones-column; feat (io)
+// [nfeat >= waves * tiles * 16 * 4]: u, w, kind (FtKind), shared of lane l16 of tile t of wave v at ((v * tiles + t) * 16 + l16) * 4.
+// -1: a width without a list instance.  (lcx_: bound by its own test file.)
+LC_HOOK lcx_test_suffstat_list_deal(int DP, int DC, i64* info, int* feat, i64 nfeat) {
+  if (!info || !feat || !gw_width_ok(DP, DC) || !lck::suffstat_list_instance(DP, DC)) return -1;
+  const int dc = DC ? DC : DP, waves = 8, tiles = lck::ftl_tpw(dc);
+  if (nfeat < (i64)waves * tiles * 16 * 4) return -1;
+  info[0] = lck::ftl_shared(dc) ? 1 : 0, info[1] = waves, info[2] = tiles, info[3] = lck::ftl_paired(dc), info[4] = lck::ftl_split(dc);
+  info[5] = DP;
+  for (int v = 0; v < waves; ++v)
+    for (int t = 0; t < tiles; ++t)
+      for (int l = 0; l < 16; ++l) {
+        const lck::FtlFeature f = lck::ftl_feature(dc, DP, v, t, l);
+        int* o = feat + ((size_t)(v * tiles + t) * 16 + l) * 4;
+        o[0] = f.u, o[1] = f.w, o[2] = f.kind, o[3] = f.shared;
+      }
+  return 0;
+}
+
 // out [4] = fused_eligible, fused_plan's grid, compute units of the device, fused_record(DP, K)
 LC_HOOK lc_test_fused_plan(int DP, i64 nrg, int K, i64* out) {
   if (!out || K < 1 || K > 4096 || nrg < 0 || nrg > HOT_MAX_NRG || DP < 1 || DP > 1024) return -1;
