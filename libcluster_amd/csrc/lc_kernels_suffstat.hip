@@ -1191,6 +1191,27 @@ static hipError_t launch_ss_feat(const SuffstatLaunch& a, hipStream_t stream) {
 #ifndef LC_FTL_BR
 #define LC_FTL_BR 48  // rows per staged batch of the list kernel (64: the second buffer leaves the 16-bit offset of a ds_read)
 #endif
+// The list kernel's step reads the NEXT step's fragments while its MFMAs run.  LC_FTL_SPREAD = G > 0: the reads go out in
+// G near-equal portions, one behind each of the step's first G MFMAs, in the order the next step's multiplies take them
+// (ftl_read), so that a wave that pushes reads into the LDS queue keeps issuing MFMAs and the last MFMAs cover the last
+// read's latency.  -DLC_FTL_SPREAD=0 (tools/variants.py): all of them in one burst ahead of the MFMAs, as before.
+#ifndef LC_FTL_SPREAD
+#define LC_FTL_SPREAD 12
+#endif
+// the r-th LDS read of a step: t >= 0: the `u` fragment of tile t; -1 - i: `w` fragment i (ahead of the first tile that
+// multiplies by it); ftl_tpw: the step's q value, which the MFMAs need and no multiply does
+__host__ __device__ constexpr int ftl_read(int DC, int r) {
+  int n = 0;
+  for (int t = 0; t < ftl_tpw(DC); ++t) {
+    if (t == 0 || ftl_wi(DC, t) != ftl_wi(DC, t - 1)) {
+      if (n == r) return -1 - ftl_wi(DC, t);
+      ++n;
+    }
+    if (n == r) return t;
+    ++n;
+  }
+  return ftl_tpw(DC);
+}
 bool speck_lists_enabled() { return LC_FT_SPECK_LISTS != 0; }
 // Share of one-quad rows (in 64ths) from which a skipping pass takes the list route.  A row that keeps several quads is
 // gathered and multiplied once per quad; with the other rows soft in EVERY quad the list pass loses to the sorted instance
@@ -1273,8 +1294,9 @@ __global__ void __launch_bounds__(256) ss_list_build_kernel(const double* __rest
 // A staged batch is LC_FTL_BR rows
 // of the list: X rows gathered whole (row-major: one contiguous row each), the quad's four q values per row, zeros with
 // q = 0 past the list's end.  The row offsets of a batch are fetched TWO batches ahead (their loads would otherwise stand
-// in front of the gather's), the rows one batch ahead into registers.  Step loop: the step's products (fragments read a
-// whole step ahead, under the previous step's MFMAs), then its MFMAs -- one v_mul_f64 per MFMA, and nothing else.
+// in front of the gather's), the rows one batch ahead into registers.  Step loop: the step's products in one group (their
+// fragments were read a whole step ahead), then its MFMAs with the next step's reads spread behind the first
+// LC_FTL_SPREAD of them (ftl_read) -- one v_mul_f64 and one or two ds_read_b64 per MFMA, and nothing else.
 template <int DP, int DC, typename IT>
 __global__ void __launch_bounds__(512, 2) suffstat_list_kernel(SuffstatLaunch a, const int* __restrict__ lens, const IT* __restrict__ ent,
                                                                 int nq) {
@@ -1296,6 +1318,7 @@ __global__ void __launch_bounds__(512, 2) suffstat_list_kernel(SuffstatLaunch a,
   // the wave's tiles (ftl_feature): tile t multiplies fragment t of `u` by fragment ftl_wi(t) of `w` -- one per tile in
   // ft_deal_one's deal; in the shared deal one per star, read once a step, and one per free tile
   constexpr int NW = ftl_nw(DC);
+  constexpr int NRD = NT + NW + 1, SPREAD = LC_FTL_SPREAD < 0 ? 0 : LC_FTL_SPREAD < NT ? LC_FTL_SPREAD : NT;  // (ftl_read)
   const double* pu[NT];
   const double* pw[NW];
 #pragma unroll
@@ -1318,6 +1341,11 @@ __global__ void __launch_bounds__(512, 2) suffstat_list_kernel(SuffstatLaunch a,
   const double* qcol = a.qZ + (int64_t)(kq < a.K ? kq : a.K - 1) * a.ldq + r0;
   int xi[NPRE], qi = -1;
   double pre[NPRE][2], qpre = 0.0;
+  // What a place past the list's end loaded becomes zero where the batch is STORED, a whole batch after its loads went
+  // out: a select next to the load waits for the load, and the fences of the step loop keep that wait in front of the
+  // batch's first MFMA -- the gather's whole latency, once per batch (LC_FTL_SPREAD = 0 selects there, as before).
+  constexpr bool LATE = SPREAD != 0;
+  bool xok[NPRE], qok = false;
   auto iload = [&](int p0) {  // list places p0 ... p0 + BR - 1 -> row offsets (-1 past the end)
 #pragma unroll
     for (int i = 0; i < NPRE; ++i) {
@@ -1330,17 +1358,20 @@ __global__ void __launch_bounds__(512, 2) suffstat_list_kernel(SuffstatLaunch a,
 #pragma unroll
     for (int i = 0; i < NPRE; ++i) {
       const double2 v = *reinterpret_cast<const double2*>(a.X + (r0 + (xi[i] < 0 ? 0 : xi[i])) * DP + 2 * xc2);
-      pre[i][0] = xi[i] < 0 ? 0.0 : v.x;
-      pre[i][1] = xi[i] < 0 ? 0.0 : v.y;
+      xok[i] = xi[i] >= 0;
+      pre[i][0] = LATE || xok[i] ? v.x : 0.0;
+      pre[i][1] = LATE || xok[i] ? v.y : 0.0;
     }
     const double q = qcol[qi < 0 ? 0 : qi];
-    qpre = qi < 0 || kq >= a.K ? 0.0 : q;
+    qok = qi >= 0 && kq < a.K;
+    qpre = LATE || qok ? q : 0.0;
   };
   auto lstore = [&](int buf) {
 #pragma unroll
     for (int i = 0; i < NPRE; ++i)
-      *reinterpret_cast<double2*>(xbuf + buf * XBUF + (xr0 + i * RPP) * LD + 2 * xc2) = make_double2(pre[i][0], pre[i][1]);
-    if (qthr) qbuf[buf * QBUF + qrow * QLD + qcl] = qpre;
+      *reinterpret_cast<double2*>(xbuf + buf * XBUF + (xr0 + i * RPP) * LD + 2 * xc2) =
+          make_double2(!LATE || xok[i] ? pre[i][0] : 0.0, !LATE || xok[i] ? pre[i][1] : 0.0);
+    if (qthr) qbuf[buf * QBUF + qrow * QLD + qcl] = !LATE || qok ? qpre : 0.0;
   };
   if (tid < 2 * BR) xbuf[(tid / BR) * XBUF + (tid % BR) * LD + ONE] = 1.0;
   if (len > 0) {
@@ -1367,36 +1398,78 @@ __global__ void __launch_bounds__(512, 2) suffstat_list_kernel(SuffstatLaunch a,
 #pragma unroll
       for (int t = 0; t < NT; ++t) pp[t] = uf[t] * wf[ftl_wi(DC, t)];
       const double qc = qa;
-      if (st + 1 < BR / 4) {
+      if constexpr (SPREAD == 0) {
+        if (st + 1 < BR / 4) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) uf[t] = pu[t][XO + (st + 1) * 4 * LD];
+          for (int t = 0; t < NT; ++t) uf[t] = pu[t][XO + (st + 1) * 4 * LD];
 #pragma unroll
-        for (int i = 0; i < NW; ++i) wf[i] = pw[i][XO + (st + 1) * 4 * LD];
-        qa = pq[QO + (st + 1) * 4 * QLD];
+          for (int i = 0; i < NW; ++i) wf[i] = pw[i][XO + (st + 1) * 4 * LD];
+          qa = pq[QO + (st + 1) * 4 * QLD];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t] = mfma4(qc, pp[t], acc[t]);
+        __builtin_amdgcn_sched_barrier(0);
+      } else {
+        // (uf and wf are dead once the products exist: the next step's fragments land in the same registers.  A fence
+        //  per MFMA: the scheduler would otherwise gather the reads into one burst again)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          acc[t] = mfma4(qc, pp[t], acc[t]);
+          if (st + 1 < BR / 4 && t < SPREAD) {
+#pragma unroll
+            for (int r = t * NRD / SPREAD; r < (t + 1) * NRD / SPREAD; ++r) {
+              const int what = ftl_read(DC, r);
+              if (what == NT)
+                qa = pq[QO + (st + 1) * 4 * QLD];
+              else if (what >= 0)
+                uf[what] = pu[what][XO + (st + 1) * 4 * LD];
+              else
+                wf[-1 - what] = pw[-1 - what][XO + (st + 1) * 4 * LD];
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = mfma4(qc, pp[t], acc[t]);
-      __builtin_amdgcn_sched_barrier(0);
     }
   };
-  for (int p0 = 0; p0 < len; p0 += 2 * BR) {  // two batches per trip: the buffer index is a compile-time constant
-    const bool more1 = p0 + BR < len, more2 = p0 + 2 * BR < len;
-    if (more1) {
+  if constexpr (LATE) {
+    // The next batch is fetched and stored whether it exists or not (past the list's end: the chunk's first row, stored as
+    // zeros into a buffer nobody reads again).  Under a condition the offsets and rows in flight meet their old values
+    // in register copies at the join, and a copy of a loaded register waits for every load in front of the batch.
+    for (int p0 = 0; p0 < len; p0 += 2 * BR) {  // two batches per trip: the buffer index is a compile-time constant
       gload();
       iload(p0 + 2 * BR);
-    }
-    batch(std::integral_constant<int, 0>{});
-    if (more1) lstore(1);
-    __syncthreads();
-    if (!more1) break;
-    if (more2) {
+      batch(std::integral_constant<int, 0>{});
+      lstore(1);
+      __syncthreads();
+      if (p0 + BR >= len) break;
       gload();
       iload(p0 + 3 * BR);
+      batch(std::integral_constant<int, 1>{});
+      lstore(0);
+      __syncthreads();
     }
-    batch(std::integral_constant<int, 1>{});
-    if (more2) lstore(0);
-    __syncthreads();
+  } else {
+    for (int p0 = 0; p0 < len; p0 += 2 * BR) {
+      const bool more1 = p0 + BR < len, more2 = p0 + 2 * BR < len;
+      if (more1) {
+        gload();
+        iload(p0 + 2 * BR);
+      }
+      batch(std::integral_constant<int, 0>{});
+      if (more1) lstore(1);
+      __syncthreads();
+      if (!more1) break;
+      if (more2) {
+        gload();
+        iload(p0 + 3 * BR);
+      }
+      batch(std::integral_constant<int, 1>{});
+      if (more2) lstore(0);
+      __syncthreads();
+    }
   }
 
   // ---- partial records, as suffstat_feat_kernel writes them (an empty list: exact zeros)
