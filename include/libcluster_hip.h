@@ -347,6 +347,25 @@ int lc_model_predict_conditional(lc_model* m, lc_ctx* ctx, const int* groups /* 
  * between rows (>= ntarget), logp n values; either may be NULL.  LC_EINVAL: no conditional prediction on ctx, a row
  * range out of bounds. */
 int lc_ctx_get_conditional(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* mean, int64_t row_stride, double* logp);
+/* ---- predictive variance of the conditional prediction (nothing in the reference corresponds).  Everything
+ * lc_model_predict_conditional does, and per row the diagonal of the mixture's predictive covariance of the target columns.
+ * The conditional of cluster k's predictive Student-t has nu' + ngiven degrees of freedom, location M_k(x_a) and, with
+ * d^2 = nu (x_a - m_a)^T iW_aa^-1 (x_a - m_a) and s = beta / ((1 + beta) nu), the covariance
+ *   Cov_k(x_a) = g_k (1 + s d^2) S_k,  S_k = iW_bb - iW_ba iW_aa^-1 iW_ab,  g_k = (1 + beta) / (beta (nu' + ngiven - 2))
+ *   var_t     = sum_k r_k (Cov_k(x_a)_tt + (M_k,t - mean_t)^2): within the experts plus between them, centred on mean
+ * in the order of target; the prior component of StickBreak weights takes part as in mean.  mean and logp are those of
+ * lc_model_predict_conditional, bit for bit.  LC_EINVAL: the cases of lc_model_predict_conditional.  LC_EDOMAIN, before
+ * anything runs on the device: a component with positive weight has nu' + ngiven <= 2, so that its covariance does not
+ * exist (every StickBreak model with ngiven = 1: the prior component has nu' = 1); the message names the component, no
+ * prediction is left on ctx, and lc_model_predict_conditional still works.  A learned cluster that ended up empty has a
+ * huge but finite variance, which is returned as it is. */
+int lc_model_predict_conditional_var(lc_model* m, lc_ctx* ctx, const int* groups /* [J of ctx] or NULL */, const int* given,
+                                     int ngiven, const int* target /* or NULL */, int ntarget);
+/* rows [row0, row0+n) of block j of the variance of the last lc_model_predict_conditional_var on ctx: var is n x ntarget
+ * with row_stride doubles between rows (>= ntarget); it may be NULL (the checks only).  mean and logp of the same call:
+ * lc_ctx_get_conditional.  LC_EINVAL: no conditional prediction on ctx, one without variance
+ * (lc_model_predict_conditional), a row range out of bounds, row_stride < ntarget. */
+int lc_ctx_get_conditional_var(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* var, int64_t row_stride);
 /* ---- rows whose unknown columns differ from row to row (nothing in the reference corresponds).  Gauss-Wishart
  * models only.  ctx holds the rows at the model's FULL width D; a NaN marks an unknown value ("hole"), +-inf is data.  A row
  * may have up to LC_HOLES_MAX holes and needs at least one known column; every row has its own set.  Block b of ctx is mixed
@@ -490,6 +509,13 @@ int lc_gw_mstep(double clustwidth, int D, double Ns, const double* xs, const dou
 int lc_gw_conditional(int D, double nu, double beta, const double* m, const double* iW, const int* given, int ngiven,
                       const int* target, int ntarget, double* A, double* ma, double* B, double* mb, double* G, double* s,
                       double* e);
+/* The tables of lc_model_predict_conditional_var from the same posterior and split (checked as in lc_gw_conditional):
+ *   S [ntarget] = the diagonal of iW_bb - iW_ba iW_aa^-1 iW_ab, in the order of target (one triangular solve per target
+ *   with the Cholesky factor of iW_aa; no inverse is formed),  g = (1 + beta) / (beta (nu + 1 - D + ngiven - 2))
+ * so that cluster k's conditional covariance has the diagonal g (1 + s ||A (x_a - m_a)||^2) S.  Either output may be NULL.
+ * LC_EINVAL: the cases of lc_gw_conditional.  LC_EDOMAIN: nu + 1 - D + ngiven <= 2 (the covariance does not exist). */
+int lc_gw_conditional_var(int D, double nu, double beta, const double* iW, const int* given, int ngiven, const int* target,
+                          int ntarget, double* S, double* g);
 /* The host table of lc_model_predict_incomplete from one Gauss-Wishart posterior (nu, beta, m [D], iW [D x D]); with
  * nu' = nu + 1 - D and, for nb = 0 ... LC_HOLES_MAX holes, Da = D - nb known columns:
  *   P [D x D] row-major = nu iW^-1 (symmetric; the square A^T A of the E-step whitener of lc_gw_mstep)

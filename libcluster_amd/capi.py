@@ -40,9 +40,22 @@ class Prediction(NamedTuple):
 
 class Conditional(NamedTuple):
     """Per-row outputs of Model.predict_conditional (lc_model_predict_conditional): mean (N, ntarget) =
-    E[x_target | x_given, training data], logp (N,) = log p(x_given | training data)."""
+    E[x_target | x_given, training data], logp (N,) = log p(x_given | training data).  var is None: a call with
+    variance=True returns a ConditionalVar, which holds it."""
     mean: np.ndarray
     logp: np.ndarray
+
+    @property
+    def var(self):
+        return None
+
+
+class ConditionalVar(NamedTuple):
+    """Conditional with the predictive variance (lc_model_predict_conditional_var): var (N, ntarget) = the diagonal of the
+    mixture's predictive covariance of the target columns, in their order."""
+    mean: np.ndarray
+    logp: np.ndarray
+    var: np.ndarray
 
 
 class Completion(NamedTuple):
@@ -282,6 +295,10 @@ def lib() -> C.CDLL:
     L.lc_model_exemplars.argtypes = [C.c_void_p, C.c_void_p, c_int_p, C.c_int, c_int32_p, c_int32_p, c_int64_p, c_double_p]
     L.lc_model_predict_conditional.argtypes = [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, c_int_p, C.c_int]
     L.lc_ctx_get_conditional.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, C.c_int64, c_double_p]
+    L.lc_model_predict_conditional_var.argtypes = [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, c_int_p, C.c_int]
+    L.lc_ctx_get_conditional_var.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, C.c_int64]
+    L.lc_gw_conditional_var.argtypes = [C.c_int, C.c_double, C.c_double, c_double_p, c_int_p, C.c_int, c_int_p, C.c_int,
+                                        c_double_p, c_double_p]
     L.lc_gw_conditional.argtypes = [C.c_int, C.c_double, C.c_double, c_double_p, c_double_p, c_int_p, C.c_int, c_int_p,
                                     C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                     c_double_p]
@@ -633,12 +650,18 @@ class Context:
                                                dptr(logZ), dptr(lp)))
         return label, logZ, lp
 
-    def get_conditional(self, j, row0, n, ntarget):
+    def get_conditional(self, j, row0, n, ntarget, variance=False):
         """Rows [row0, row0+n) of block j of the last Model.predict_conditional_context on this context ->
-        Conditional(mean (n, ntarget), logp (n,)); ntarget is the number of target columns of that call."""
+        Conditional(mean (n, ntarget), logp (n,)); ntarget is the number of target columns of that call.  variance:
+        ConditionalVar, with var (n, ntarget) (lc_ctx_get_conditional_var; ValueError when that call was made without
+        variance=True)."""
         mean, logp = np.zeros((n, ntarget)), np.zeros(n)
         check(lib().lc_ctx_get_conditional(self._h, j, row0, n, dptr(mean), ntarget, dptr(logp)))
-        return Conditional(mean, logp)
+        if not variance:
+            return Conditional(mean, logp)
+        var = np.zeros((n, ntarget))
+        check(lib().lc_ctx_get_conditional_var(self._h, j, row0, n, dptr(var), ntarget))
+        return ConditionalVar(mean, logp, var)
 
     def get_completed(self, j, row0, n):
         """Rows [row0, row0+n) of block j after the last Model.predict_incomplete_context on this context ->
@@ -826,9 +849,11 @@ class Model:
         gs = set(int(g) for g in given)
         return [c for c in range(self.dims()[2]) if c not in gs]
 
-    def predict_conditional_context(self, ctx, given, target=None, groups=None):
+    def predict_conditional_context(self, ctx, given, target=None, groups=None, variance=False):
         """E[x_target | x_given] and log p(x_given) of the rows resident in ctx, whose column i is model column
         given[i] (lc_model_predict_conditional).  target None: every model column that is not given, ascending.
+        variance: also the predictive variance of every target column (lc_model_predict_conditional_var; DomainError
+        where it does not exist: a component with weight and nu + 1 - D + len(given) <= 2).
         Nothing is downloaded: read the rows with ctx.get_conditional.  Returns the number of target columns."""
         g = None
         if groups is not None:
@@ -838,37 +863,43 @@ class Model:
             g = garr.ctypes.data_as(c_int_p)
         gv = np.ascontiguousarray(given, dtype=np.int32).reshape(-1)
         tv = None if target is None else np.ascontiguousarray(target, dtype=np.int32).reshape(-1)
-        check(lib().lc_model_predict_conditional(self._h, ctx._h, g, gv.ctypes.data_as(c_int_p), gv.size,
-                                                 None if tv is None else tv.ctypes.data_as(c_int_p),
-                                                 0 if tv is None else tv.size))
+        call = lib().lc_model_predict_conditional_var if variance else lib().lc_model_predict_conditional
+        check(call(self._h, ctx._h, g, gv.ctypes.data_as(c_int_p), gv.size,
+                   None if tv is None else tv.ctypes.data_as(c_int_p), 0 if tv is None else tv.size))
         return len(self._targets(gv, tv))
 
-    def predict_conditional(self, Xa, given, target=None, groups=None, device=0):
+    def predict_conditional(self, Xa, given, target=None, groups=None, device=0, variance=False):
         """Conditional(mean, logp) for the host rows Xa ((N, len(given)) array: the known columns, in the order of
-        given), or a list of them for a list of blocks (block b mixed with learned group groups[b], default 0)."""
+        given), or a list of them for a list of blocks (block b mixed with learned group groups[b], default 0).
+        variance: ConditionalVar(mean, logp, var) with the predictive variance of every target column."""
         blocks = isinstance(Xa, (list, tuple))
         Xs = list(Xa) if blocks else [Xa]
         Da = len(given)
         Xs = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, max(Da, 1))) for x in Xs]
         with Context(device) as ctx:
             ctx.set_data(Xs)
-            nt = self.predict_conditional_context(ctx, given, target, groups)
-            out = [ctx.get_conditional(j, 0, x.shape[0], nt) for j, x in enumerate(Xs)]
+            nt = self.predict_conditional_context(ctx, given, target, groups, variance)
+            out = [ctx.get_conditional(j, 0, x.shape[0], nt, variance) for j, x in enumerate(Xs)]
         return out if blocks else out[0]
 
-    def impute(self, X, missing, groups=None, device=0):
+    def impute(self, X, missing, groups=None, device=0, return_var=False):
         """A copy of the full-width rows X ((N, D) array or a list of blocks) with the columns `missing` replaced by
         their conditional mean given the other columns (predict_conditional).  What X holds in the missing columns is
-        not looked at (NaN is fine).  Rows whose missing columns differ from row to row: predict_incomplete."""
+        not looked at (NaN is fine).  Rows whose missing columns differ from row to row: predict_incomplete.
+        return_var: (filled, var) with var (N, len(missing)) the predictive variance of the values filled in, in the
+        order of `missing` (lists of each for a list of blocks)."""
         blocks = isinstance(X, (list, tuple))
         D = self.dims()[2]
         Xs = [np.array(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (X if blocks else [X])]
         miss = [int(c) for c in missing]
         given = [c for c in range(D) if c not in set(miss)]
-        res = self.predict_conditional([x[:, given] for x in Xs], given, miss, groups, device)
+        res = self.predict_conditional([x[:, given] for x in Xs], given, miss, groups, device, variance=return_var)
         for x, r in zip(Xs, res):
             x[:, miss] = r.mean
-        return Xs if blocks else Xs[0]
+        if not return_var:
+            return Xs if blocks else Xs[0]
+        var = [r.var for r in res]
+        return (Xs, var) if blocks else (Xs[0], var[0])
 
     # -- rows with holes (DESIGN 4.15) -------------------------------------------------------------------------------
     def predict_incomplete_context(self, ctx, groups=None):
@@ -1001,6 +1032,22 @@ def gw_conditional(nu, beta, m, iW, given, target=None):
                                   None if tv is None else tv.ctypes.data_as(c_int_p), 0 if tv is None else tv.size,
                                   dptr(A), dptr(ma), dptr(B), dptr(mb), C.byref(G), C.byref(s), C.byref(e)))
     return {"A": A, "ma": ma, "B": B, "mb": mb, "G": G.value, "s": s.value, "e": e.value, "target": tg}
+
+
+def gw_conditional_var(nu, beta, iW, given, target=None):
+    """The tables of the conditional variance (lc_gw_conditional_var) from one Gauss-Wishart posterior -> (S, g): S the
+    diagonal of iW_bb - iW_ba iW_aa^-1 iW_ab in the order of target (None: the columns not given, ascending), g =
+    (1 + beta) / (beta (nu + 1 - D + len(given) - 2)).  DomainError where the variance does not exist."""
+    iW = np.ascontiguousarray(iW, dtype=np.float64)
+    D = iW.shape[0]
+    gv = np.ascontiguousarray(given, dtype=np.int32).reshape(-1)
+    tv = None if target is None else np.ascontiguousarray(target, dtype=np.int32).reshape(-1)
+    Db = tv.size if tv is not None else len([c for c in range(D) if c not in set(int(g) for g in gv)])
+    S, g = np.zeros(Db), C.c_double()
+    check(lib().lc_gw_conditional_var(D, nu, beta, dptr(iW), gv.ctypes.data_as(c_int_p), gv.size,
+                                      None if tv is None else tv.ctypes.data_as(c_int_p), 0 if tv is None else tv.size,
+                                      dptr(S), C.byref(g)))
+    return S, g.value
 
 
 def gw_precision(nu, beta, m, iW):

@@ -1155,6 +1155,25 @@ int lc_ctx_get_conditional(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* 
   });
 }
 
+// ---- predictive variance of the conditional prediction ---------------
+int lc_model_predict_conditional_var(lc_model* m, lc_ctx* ctx, const int* groups, const int* given, int ngiven,
+                                     const int* target, int ntarget) {
+  return guarded([&] {
+    need(m, "model");
+    need(ctx, "ctx");
+    ctx->impl.predict_clear();  // (a failure leaves no prediction behind)
+    if (!model_alive(m)) throw std::invalid_argument("the model was freed");
+    lcp::predict_conditional(ctx->impl, m->model, groups, given, ngiven, target, ntarget, /*want_var=*/true);
+  });
+}
+
+int lc_ctx_get_conditional_var(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* var, int64_t row_stride) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.get_conditional_var(j, row0, n, var, row_stride);
+  });
+}
+
 // ---- rows with holes -------------------------------------------------
 static_assert(LC_HOLES_MAX == lck::HOLES_MAX, "the header and the kernels agree on the holes a row may have");
 int lc_model_predict_incomplete(lc_model* m, lc_ctx* ctx, const int* groups) {
@@ -1285,6 +1304,16 @@ int lc_gw_conditional(int D, double nu, double beta, const double* m, const doub
     if (D < 1) throw std::invalid_argument("D must be >= 1!");
     const std::vector<int> tg = lcp::conditional_split(D, given, ngiven, target, ntarget);
     lcp::gw_conditional(D, nu, beta, m, iW, std::vector<int>(given, given + ngiven), tg, A, ma, B, mb, G, s, e);
+  });
+}
+
+int lc_gw_conditional_var(int D, double nu, double beta, const double* iW, const int* given, int ngiven, const int* target,
+                          int ntarget, double* S, double* g) {
+  return guarded([&] {
+    need(iW, "iW");
+    if (D < 1) throw std::invalid_argument("D must be >= 1!");
+    const std::vector<int> tg = lcp::conditional_split(D, given, ngiven, target, ntarget);
+    lcp::gw_conditional_var(D, nu, beta, iW, std::vector<int>(given, given + ngiven), tg, S, g);
   });
 }
 

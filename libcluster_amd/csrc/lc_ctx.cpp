@@ -264,6 +264,7 @@ void Context::build_layout(int J, const int64_t* Nj, int D) {
   qz_[0].cap = qz_[1].cap = 0;
   pred_vb_ = pred_logp_ = false;  // (the per-row prediction outputs belong to the old rows)
   pred_cond_ = 0;
+  pred_cond_var_ = false;
   pred_holes_ = false;
   pred_docs_T_ = 0;               // (... and the per-document ones to the old documents)
   LC_HIP(hipSetDevice(device_));

@@ -14,6 +14,10 @@
 #include "lc_comm.hpp"
 #include "lc_kernels.h"
 
+namespace lck {
+struct PredictCondLaunch;  // (lc_predict.hpp)
+}
+
 namespace lcc {
 
 struct HipFailure : std::runtime_error {
@@ -278,6 +282,7 @@ class Context {
     pred_vb_ = pred_logp_ = false;
     pred_docs_T_ = 0;
     pred_cond_ = 0;
+    pred_cond_var_ = false;
     pred_holes_ = false;
   }
   // Conditional prediction: after a raw E-step with zero constants over the context's (given) columns left
@@ -289,6 +294,12 @@ class Context {
   // rows [row0, row0+n) of group j of the last conditional prediction (either output may be null)
   void get_conditional(int j, int64_t row0, int64_t n, double* mean, int64_t row_stride, double* logp) const;
   int conditional_width() const { return pred_cond_; }  // target columns of the conditional prediction held (0: none)
+  // Predictive variance, right after predict_cond with the same Kp and Db, on the columns, logp and mean it
+  // left: per row the diagonal of the mixture's covariance of the target columns (lck::PredictCondVarLaunch for the tables:
+  // S Kp x Db, g Kp, host arrays).
+  void predict_cond_var(int Kp, int Db, const double* S, const double* g);
+  // rows [row0, row0+n) of group j of that variance (var may be null); throws when the prediction held has none
+  void get_conditional_var(int j, int64_t row0, int64_t n, double* var, int64_t row_stride) const;
   // Rows with holes (a NaN in X is an unknown value).  holes_scan: one read of X leaves the per-row hole
   // records on the device and returns the number of rows with holes, the largest count and the first row (in block, row
   // order) that has more than lck::HOLES_MAX holes or no known column (*bad_block = -1: none), with its count.
@@ -475,6 +486,10 @@ class Context {
   // ... of the last conditional prediction: mean [NP x pred_cond_] and log p(x_given) [NP]; pred_cond_ = 0: none
   DevBuf<double> pcmean_, pclogp_;
   int pred_cond_ = 0;
+  // ... and, when pred_cond_var_, its variance [NP x pred_cond_] with the tables of that pass [g Kp | S Kp x Dbp]
+  DevBuf<double> pcvar_, pvtab_;
+  bool pred_cond_var_ = false;
+  lck::PredictCondLaunch predict_cond_args(int Kp, int Db) const;  // over the tables predict_cond left in ptab_
   // ... of the last prediction of rows with holes: count [NP], cols [NP x HOLES_MAX], log p(x_known) [NP], the scan's
   // three integers; pred_holes_: X holds the completed rows of such a prediction
   DevBuf<int> hcount_, hcols_;

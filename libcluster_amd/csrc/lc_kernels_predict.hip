@@ -257,6 +257,135 @@ __global__ __launch_bounds__(PC_THREADS) void predict_cond_kernel(PredictCondLau
   }
 }
 
+// Predictive variance, after predict_cond_kernel and in its lane layout.  Lane l owns row l of the wave in
+// the first part of a cluster's step (r_k and h_k from the t_k and logp that kernel left); the lanes that hold row hi of
+// block blk in the D operand fetch them with one __shfl per row group each.  The tile M_k of a cluster is complete -- all
+// chunks of given columns contracted -- before it is squared: the loop order is panel, cluster, chunk, and x stays in
+// registers across the clusters only when one chunk holds all given columns (Dae <= PC_CHUNK: RES); otherwise it is re-read
+// per cluster from the cache.  With the 16-wide panel (80 resident doubles per lane) both instances fit the 256 registers
+// of two waves per SIMD without scratch; the 32-wide panel (128 doubles) runs at one wave.
+template <bool RES>  // RES: one chunk holds all given columns, x is loaded once
+__global__ __launch_bounds__(PC_THREADS, PCV_PANEL == 16 ? 2 : 1) void predict_cond_var_kernel(PredictCondVarLaunch v) {
+  __shared__ double etab[64];
+  fill_exp_table(etab, threadIdx.x, PC_THREADS);
+  __syncthreads();  // (the only barrier)
+  const PredictCondLaunch& a = v.c;
+  // (x that is re-read per cluster anyway is held half a chunk at a time: 32 registers less)
+  constexpr int CH = RES ? PC_CHUNK : PC_CHUNK / 2;
+  constexpr int NG = PC_WAVE_ROWS / RG, NS = CH / 4, NQ = PCV_PANEL / 4;
+  static_assert(RG == 16 && NG == 4, "one MFMA block per quad of rows, one shuffle source per row group");
+  const int lane = threadIdx.x & 63, lo2 = lane & 3, blk = (lane >> 2) & 3, hi = lane >> 4;
+  const int64_t NP = a.nrg * RG;
+  const int64_t wrow0 = ((int64_t)blockIdx.x * (PC_THREADS / 64) + (threadIdx.x >> 6)) * PC_WAVE_ROWS;
+  if (wrow0 >= NP) return;
+  // rows past the end and pad rows: clamped for reading, scored with r = h = 0, never written
+  const int64_t row = wrow0 + lane, rrow = row < NP ? row : NP - 1;
+  int j = 0;
+  const bool valid = row_valid(rrow, a.rginfo, a.nrows, j) && row < NP;
+  if (!valid) j = 0;
+  const double* __restrict__ col = a.col + rrow;
+  const double* __restrict__ tt = a.ttab + (size_t)j * a.Kp;
+  const double logp = valid ? a.logp[rrow] : 0.0;
+  int64_t xrow[NG];
+  bool ovalid[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int64_t ra = wrow0 + g * RG + 4 * blk + lo2, ro = wrow0 + g * RG + 4 * blk + hi;
+    xrow[g] = ra < NP ? ra : NP - 1;
+    int jo;
+    ovalid[g] = ro < NP && row_valid(ro < NP ? ro : NP - 1, a.rginfo, a.nrows, jo);
+  }
+  const unsigned toff = (unsigned)(hi * a.Dbp + lo2);  // of (given column hi, target lo2) inside a k-step's piece of T
+  constexpr bool resident = RES;
+  double x[NG][NS];
+  auto load_x = [&](int c0) {
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const int c = c0 + 4 * s + hi;
+        x[g][s] = c < a.Da ? a.X[(size_t)xrow[g] * a.DP + c] : c == a.Da ? 1.0 : 0.0;  // (the ones column carries m_b)
+      }
+  };
+  if (resident) load_x(0);
+  for (int t0 = 0; t0 < a.Db; t0 += PCV_PANEL) {  // accumulators, mean and tile of one panel of targets are resident
+    const int nq = (a.Dbp - t0) / 4 < NQ ? (a.Dbp - t0) / 4 : NQ;
+    double acc[NG][NQ], mu[NG][NQ];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const int64_t ro = wrow0 + g * RG + 4 * blk + hi, orow = ro < NP ? ro : NP - 1;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const int tcol = t0 + 4 * q + lo2;
+        acc[g][q] = 0.0;
+        mu[g][q] = tcol < a.Db ? a.mean[(size_t)orow * a.Db + tcol] : 0.0;
+      }
+    }
+    for (int k = 0; k < a.Kp; ++k) {
+      const double t = col[(size_t)k * a.ldq];
+      const double r = valid ? exp_nonpos(t - logp, etab) : 0.0;
+      // 1 + s_k d_k^2 back from t_k = ttab_jk - e_k log1p(s_k d_k^2); a component without weight (t = -inf) adds nothing
+      // (as the reciprocal of the table exponential of the negated argument: half the instructions and registers of exp())
+      const double h = r > 0.0 ? v.g[k] * rcp_pos(exp_nonpos((t - tt[k]) / a.pexp[k], etab)) : 0.0;
+      double tile[NG][NQ];
+#pragma unroll
+      for (int g = 0; g < NG; ++g)
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) tile[g][q] = 0.0;
+      for (int c0 = 0; c0 < a.Dae; c0 += CH) {
+        if (!resident) load_x(c0);
+        const int ns = (a.Dae - c0) / 4 < NS ? (a.Dae - c0) / 4 : NS;
+        // wave-uniform bases and one 32-bit lane offset: the addresses stay in scalar registers
+        const double* __restrict__ mk = a.mext + (size_t)k * a.Dae + c0;
+        const double* __restrict__ Tk = a.T + ((size_t)k * a.Dae + c0) * a.Dbp + t0;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          if (s < ns) {
+            const double mv = (mk + 4 * s)[(unsigned)hi];
+            double av[NG], bv[NQ];
+#pragma unroll
+            for (int g = 0; g < NG; ++g) av[g] = x[g][s] - mv;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) bv[q] = q < nq ? (Tk + (size_t)(4 * s) * a.Dbp + 4 * q)[toff] : 0.0;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+              if (q < nq) {
+#pragma unroll
+                for (int g = 0; g < NG; ++g) tile[g][q] = mfma4(av[g], bv[q], tile[g][q]);
+              }
+            }
+          }
+        }
+      }
+      // the cluster's update in one group after its run of MFMAs; r_k and h_k cross to the D layout here,
+      // not before the run, where they would be eight more doubles live under it.  Quads past the panel's end are skipped.
+      double sv[NQ];
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) sv[q] = q < nq ? (v.S + (size_t)k * a.Dbp + t0 + 4 * q)[(unsigned)lo2] : 0.0;
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const double rD = __shfl(r, g * RG + 4 * blk + hi), hD = __shfl(h, g * RG + 4 * blk + hi);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+          if (q < nq) {
+            const double d = tile[g][q] - mu[g][q];
+            acc[g][q] = fma(rD, fma(d, d, hD * sv[q]), acc[g][q]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const int64_t ro = wrow0 + g * RG + 4 * blk + hi;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const int tcol = t0 + 4 * q + lo2;
+        if (ovalid[g] && tcol < a.Db) v.var[(size_t)ro * a.Db + tcol] = acc[g][q];
+      }
+    }
+  }
+}
+
 template <int MODE>
 hipError_t launch_diag_mode(const PredictDiagLaunch& a, dim3 grid, hipStream_t stream) {
   switch (a.DP) {
@@ -293,6 +422,22 @@ hipError_t launch_predict_cond(const PredictCondLaunch& a, hipStream_t stream) {
     return hipErrorInvalidValue;
   const int64_t per = (int64_t)(PC_THREADS / 64) * PC_WAVE_ROWS;
   hipLaunchKernelGGL(predict_cond_kernel, dim3((unsigned)((rows + per - 1) / per)), dim3(PC_THREADS), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_predict_cond_var(const PredictCondVarLaunch& v, hipStream_t stream) {
+  const PredictCondLaunch& a = v.c;
+  const int64_t rows = a.nrg * RG;
+  if (rows == 0) return hipSuccess;
+  if (a.Kp < 1 || a.Da < 1 || a.Db < 1 || a.DP < a.Da || a.Dae < a.Da + 1 || a.Dae % 4 != 0 || a.Dbp < a.Db ||
+      a.Dbp % 4 != 0 || !v.S || !v.g || !v.var)
+    return hipErrorInvalidValue;
+  const int64_t per = (int64_t)(PC_THREADS / 64) * PC_WAVE_ROWS;
+  const dim3 grid((unsigned)((rows + per - 1) / per));
+  if (a.Dae <= PC_CHUNK)
+    hipLaunchKernelGGL(predict_cond_var_kernel<true>, grid, dim3(PC_THREADS), 0, stream, v);
+  else
+    hipLaunchKernelGGL(predict_cond_var_kernel<false>, grid, dim3(PC_THREADS), 0, stream, v);
   return hipGetLastError();
 }
 

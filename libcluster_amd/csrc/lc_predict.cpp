@@ -158,6 +158,16 @@ void Context::predict_cond(int Kp, int Db, const double* tt, const double* ps, c
   }
   ptab_.reserve(hpack_.size());
   LC_HIP(hipMemcpyAsync(ptab_.p, hpack_.data(), hpack_.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+  LC_HIP(lck::launch_predict_cond(predict_cond_args(Kp, Db), stream_));
+  LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ is free again; ptab_ keeps the tables for predict_cond_var)
+  qz_[cur_].K = Kp;
+  qz_[cur_].hash_ok = false;
+  pred_cond_ = Db;
+}
+
+lck::PredictCondLaunch Context::predict_cond_args(int Kp, int Db) const {
+  const int Da = D_, Dae = (Da + 1 + 3) / 4 * 4, Dbp = (Db + 3) / 4 * 4;
+  const size_t nt = (size_t)J_ * Kp, nm = (size_t)Kp * Dae;  // (the layout predict_cond packs into ptab_)
   lck::PredictCondLaunch a;
   a.X = X_.p;
   a.DP = DP_;
@@ -178,11 +188,48 @@ void Context::predict_cond(int Kp, int Db, const double* tt, const double* ps, c
   a.T = a.mext + nm;
   a.mean = pcmean_.p;
   a.logp = pclogp_.p;
-  LC_HIP(lck::launch_predict_cond(a, stream_));
-  LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ and ptab_ are free again)
-  qz_[cur_].K = Kp;
-  qz_[cur_].hash_ok = false;
-  pred_cond_ = Db;
+  return a;
+}
+
+void Context::predict_cond_var(int Kp, int Db, const double* S, const double* g) {
+  use_device();
+  pred_cond_var_ = false;
+  if (pred_cond_ != Db || Kp < 1) throw std::logic_error("predict_cond_var: no conditional prediction of this width");
+  if (NP_ == 0) {
+    pred_cond_var_ = true;
+    return;
+  }
+  if (qz_[cur_].K != Kp) throw std::logic_error("predict_cond_var: the columns of predict_cond are gone");
+  const int Dbp = (Db + 3) / 4 * 4;
+  pcvar_.reserve((size_t)NP_ * Db);
+  // tables: [g Kp | S Kp x Dbp], the pads zero
+  hpack_.assign((size_t)Kp + (size_t)Kp * Dbp, 0.0);
+  std::copy(g, g + Kp, hpack_.data());
+  for (int k = 0; k < Kp; ++k) std::copy(S + (size_t)k * Db, S + (size_t)(k + 1) * Db, hpack_.data() + Kp + (size_t)k * Dbp);
+  pvtab_.reserve(hpack_.size());
+  LC_HIP(hipMemcpyAsync(pvtab_.p, hpack_.data(), hpack_.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+  lck::PredictCondVarLaunch v;
+  v.c = predict_cond_args(Kp, Db);
+  v.g = pvtab_.p;
+  v.S = pvtab_.p + Kp;
+  v.var = pcvar_.p;
+  LC_HIP(lck::launch_predict_cond_var(v, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ is free again)
+  pred_cond_var_ = true;
+}
+
+void Context::get_conditional_var(int j, int64_t row0, int64_t n, double* var, int64_t row_stride) const {
+  use_device();
+  if (pred_cond_ < 1) throw std::invalid_argument("the context holds no conditional prediction (lc_model_predict_conditional_var)");
+  if (!pred_cond_var_)
+    throw std::invalid_argument("the context's conditional prediction has no variance (lc_model_predict_conditional_var)");
+  if (j < 0 || j >= J_ || row0 < 0 || n < 0 || row0 + n > Nj_[j]) throw std::invalid_argument("row range out of bounds");
+  if (var && row_stride < pred_cond_) throw std::invalid_argument("row_stride is smaller than the number of target columns");
+  if (n == 0 || !var) return;
+  const size_t at = (size_t)(goff_[j] + row0), w = (size_t)pred_cond_ * sizeof(double);
+  LC_HIP(hipMemcpy2DAsync(var, (size_t)row_stride * sizeof(double), pcvar_.p + at * pred_cond_, w, w, (size_t)n,
+                          hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
 }
 
 void Context::get_conditional(int j, int64_t row0, int64_t n, double* mean, int64_t row_stride, double* logp) const {
@@ -589,12 +636,18 @@ std::vector<int> conditional_split(int D, const int* given, int ngiven, const in
   return tg;
 }
 
-void gw_conditional(int D, double nu, double beta, const double* m, const double* iW, const std::vector<int>& given,
-                    const std::vector<int>& target, double* A, double* ma, double* B, double* mb, double* G, double* s,
-                    double* e) {
+namespace {
+// gw_conditional and gw_conditional_var on ONE Cholesky factor of iW_aa; S and gv (the variance tables) may be null, and
+// the existence of the variance is looked at only when one of them is asked for
+void conditional_tables(int D, double nu, double beta, const double* m, const double* iW, const std::vector<int>& given,
+                        const std::vector<int>& target, double* A, double* ma, double* B, double* mb, double* G, double* s,
+                        double* e, double* S, double* gv) {
   const int Da = (int)given.size(), Db = (int)target.size();
   const double nup = nu + 1 - D;  // Student-t degrees of freedom: of the FULL model's width (the marginal keeps them)
   if (!(nup > 0.0) || !(beta > 0.0)) throw std::invalid_argument("nu must exceed D - 1 and beta must be positive");
+  if ((S || gv) && !(nup + Da > 2.0))  // the conditional Student-t has nu' + Da degrees of freedom
+    throw std::domain_error("the conditional variance does not exist: nu + 1 - D + ngiven = " + std::to_string(nup + Da) +
+                            " is not above 2");
   std::vector<double> L((size_t)Da * Da);
   for (int i = 0; i < Da; ++i)
     for (int c = 0; c < Da; ++c) L[(size_t)i * Da + c] = iW[(size_t)given[(size_t)i] * D + given[(size_t)c]];
@@ -611,14 +664,21 @@ void gw_conditional(int D, double nu, double beta, const double* m, const double
     for (int i = 0; i < Da; ++i) ma[i] = m[given[(size_t)i]];
   if (mb)
     for (int t = 0; t < Db; ++t) mb[t] = m[target[(size_t)t]];
-  if (B) {  // row t of B solves iW_aa b = iW_a,t: L y = iW_a,t, then L^T b = y
+  if (B || S) {  // row t of B solves iW_aa b = iW_a,t: L y = iW_a,t, then L^T b = y; the Schur complement's diagonal needs y only
     std::vector<double> y((size_t)Da);
     for (int t = 0; t < Db; ++t) {
+      const int ct = target[(size_t)t];
       for (int i = 0; i < Da; ++i) {
-        double v = iW[(size_t)target[(size_t)t] * D + given[(size_t)i]];
+        double v = iW[(size_t)ct * D + given[(size_t)i]];
         for (int c = 0; c < i; ++c) v -= L[(size_t)i * Da + c] * y[(size_t)c];
         y[(size_t)i] = v / L[(size_t)i * Da + i];
       }
+      if (S) {  // iW_tt - iW_ta iW_aa^-1 iW_at = iW_tt - ||y||^2
+        double v = iW[(size_t)ct * D + ct];
+        for (int i = 0; i < Da; ++i) v -= y[(size_t)i] * y[(size_t)i];
+        S[t] = v;
+      }
+      if (!B) continue;
       double* b = B + (size_t)t * Da;
       for (int i = Da - 1; i >= 0; --i) {
         double v = y[(size_t)i];
@@ -632,10 +692,25 @@ void gw_conditional(int D, double nu, double beta, const double* m, const double
          0.5 * (Da * std::log(nup * beta / (1 + beta)) - logdet);
   if (s) *s = beta / ((1 + beta) * nu);
   if (e) *e = (nup + Da) / 2;
+  if (gv) *gv = (1 + beta) / (beta * (nup + Da - 2.0));
+}
+}  // namespace
+
+void gw_conditional(int D, double nu, double beta, const double* m, const double* iW, const std::vector<int>& given,
+                    const std::vector<int>& target, double* A, double* ma, double* B, double* mb, double* G, double* s,
+                    double* e) {
+  conditional_tables(D, nu, beta, m, iW, given, target, A, ma, B, mb, G, s, e, nullptr, nullptr);
+}
+
+void gw_conditional_var(int D, double nu, double beta, const double* iW, const std::vector<int>& given,
+                        const std::vector<int>& target, double* S, double* g) {
+  double gdummy;  // (the existence check runs even when neither output is wanted)
+  conditional_tables(D, nu, beta, nullptr, iW, given, target, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, S,
+                     g ? g : &gdummy);
 }
 
 void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* groups, const int* given, int ngiven,
-                         const int* target, int ntarget) {
+                         const int* target, int ntarget, bool want_var) {
   ctx.predict_clear();  // (whatever an earlier prediction left must not outlive a failure of this one)
   const int K = (int)model.clusters.size(), J = (int)model.weights.size(), Jc = ctx.J();
   if (K < 1) throw std::invalid_argument("the model has no clusters");
@@ -662,12 +737,29 @@ void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* 
   const int Kp = K + (rest ? 1 : 0);
   const lch::ClusterAny prior(model.ckind, model.clusters[0].prior(), D);  // clearobs state: a cluster that saw no data
   std::vector<double> A((size_t)Kp * Da * Da), ma((size_t)Kp * Da), B((size_t)Kp * Db * Da), mb((size_t)Kp * Db),
-      G((size_t)Kp), ps((size_t)Kp), pe((size_t)Kp);
+      G((size_t)Kp), ps((size_t)Kp), pe((size_t)Kp), S(want_var ? (size_t)Kp * Db : 0, 0.0), gvar(want_var ? (size_t)Kp : 0, 0.0);
   for (int k = 0; k < Kp; ++k) {
     const lch::GaussWishState& g = k < K ? model.clusters[(size_t)k].gw : prior.gw;
-    gw_conditional(D, g.nu, g.beta, g.m.data(), g.iW.data(), gv, tg, A.data() + (size_t)k * Da * Da,
-                   ma.data() + (size_t)k * Da, B.data() + (size_t)k * Db * Da, mb.data() + (size_t)k * Db, &G[(size_t)k],
-                   &ps[(size_t)k], &pe[(size_t)k]);
+    bool var_k = want_var;
+    if (want_var && !(g.nu + 1 - D + Da > 2.0)) {
+      // the variance of this component does not exist: an error when a row can give it weight, nothing when none can
+      // (its g and S stay 0, and the kernel skips a component whose responsibility is 0)
+      bool weighted = false;
+      for (int b = 0; b < Jc; ++b) {
+        const int j = groups ? groups[b] : 0;
+        weighted = weighted || (k < K ? Epi[(size_t)j * K + k] : Erest[(size_t)j]) > 0.0;
+      }
+      if (weighted)
+        throw std::domain_error("the conditional variance does not exist: " +
+                                (k < K ? "cluster " + std::to_string(k) : std::string("the prior component")) +
+                                " has nu + 1 - D + ngiven = " + std::to_string(g.nu + 1 - D + Da) +
+                                ", which is not above 2 (the mean and logp of lc_model_predict_conditional do exist)");
+      var_k = false;
+    }
+    conditional_tables(D, g.nu, g.beta, g.m.data(), g.iW.data(), gv, tg, A.data() + (size_t)k * Da * Da,
+                       ma.data() + (size_t)k * Da, B.data() + (size_t)k * Db * Da, mb.data() + (size_t)k * Db, &G[(size_t)k],
+                       &ps[(size_t)k], &pe[(size_t)k], var_k ? S.data() + (size_t)k * Db : nullptr,
+                       var_k ? &gvar[(size_t)k] : nullptr);
   }
   std::vector<double> tt((size_t)Jc * Kp), zero((size_t)Jc * Kp, 0.0);
   for (int b = 0; b < Jc; ++b) {
@@ -678,6 +770,7 @@ void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* 
   // one raw E-step over the given columns with the marginal whiteners: -d^2 / 2 per column
   ctx.estep(Kp, A.data(), ma.data(), zero.data(), nullptr, nullptr, /*raw=*/true);
   ctx.predict_cond(Kp, Db, tt.data(), ps.data(), pe.data(), ma.data(), B.data(), mb.data());
+  if (want_var) ctx.predict_cond_var(Kp, Db, S.data(), gvar.data());
 }
 
 void gw_precision(int D, double nu, double beta, const double* iW, double* P, double* G, double* s, double* e) {

@@ -94,6 +94,27 @@ struct PredictCondLaunch {
 };
 hipError_t launch_predict_cond(const PredictCondLaunch& a, hipStream_t stream);
 
+// predict_cond_var_kernel: the predictive variance of the target columns, the diagonal of the mixture's
+// covariance centred on the mean predict_cond_kernel left.  It runs after that kernel on the same launch arguments and
+// reads what it wrote: t_k in the Kp columns, logp and mean.  Per valid row, with r_k = exp(t_k - logp),
+//   h_k = g_k (1 + s_k d_k^2) = g_k exp((ttab_jk - t_k) / e_k)        (the raw column is gone: t_k holds the same d_k^2)
+//   var[row, t] = sum_k r_k ((M_k,t - mean_t)^2 + h_k S_k,t),  M_k = [x_a - m_a,k, 1] T_k
+// M_k is a tile on the matrix pipe from zeroed accumulators per cluster (the operand is NOT scaled by r_k: the tile gets
+// squared), the update one group of VALU instructions after the cluster's MFMAs.  One wave owns 64 rows: no atomics, the
+// same bits on every call.  PCV_PANEL target columns are resident per pass (accumulators, mean and tile).
+#ifndef LC_PCV_PANEL
+#define LC_PCV_PANEL 16
+#endif
+constexpr int PCV_PANEL = LC_PCV_PANEL;
+static_assert(PCV_PANEL == 16 || PCV_PANEL == 32, "a panel is 4 or 8 quads of target columns");
+struct PredictCondVarLaunch {
+  PredictCondLaunch c;        // as launched before (col, mean and logp are read here)
+  const double* S = nullptr;  // [Kp x Dbp] diagonal of iW_bb - iW_ba iW_aa^-1 iW_ab, pads zero
+  const double* g = nullptr;  // [Kp] (1 + beta) / (beta (nu' + Da - 2)); 0 for a component without weight
+  double* var = nullptr;      // [NP x Db]
+};
+hipError_t launch_predict_cond_var(const PredictCondVarLaunch& a, hipStream_t stream);
+
 // ---- rows whose unknown columns differ from row to row (lc_kernels_holes.hip) ---------------------------------
 // A NaN in X marks an unknown value ("hole"); a row may hold up to HOLES_MAX of them (LC_HOLES_MAX of the C header).
 constexpr int HOLES_MAX = 8;
@@ -182,11 +203,22 @@ std::vector<int> conditional_split(int D, const int* given, int ngiven, const in
 void gw_conditional(int D, double nu, double beta, const double* m, const double* iW, const std::vector<int>& given,
                     const std::vector<int>& target, double* A, double* ma, double* B, double* mb, double* G, double* s,
                     double* e);
+// The tables of the conditional variance from the same posterior and split: the conditional of the
+// cluster's predictive Student-t has nu' + Da degrees of freedom and the covariance g (1 + s d^2) (iW_bb - iW_ba iW_aa^-1 iW_ab);
+//   S [Db] = the diagonal of that Schur complement: iW_tt - ||L^-1 iW_a,t||^2 with the Cholesky factor L of iW_aa that
+//            gw_conditional uses (one triangular solve per target, no inverse)
+//   g = (1 + beta) / (beta (nu' + Da - 2))
+// Either output may be null.  Throws std::domain_error for nu' + Da <= 2 (the covariance does not exist), and
+// std::invalid_argument as gw_conditional does.
+void gw_conditional_var(int D, double nu, double beta, const double* iW, const std::vector<int>& given,
+                        const std::vector<int>& target, double* S, double* g);
 // E[x_target | x_given, training data] and log p(x_given | training data) of the rows in ctx (its columns are the given
 // columns, in the order of `given`): into the context's conditional outputs (Context::get_conditional).  Gauss-Wishart
 // models only; all K clusters take part (and the prior component of StickBreak weights), as in predict()'s logp.
+// want_var: also the diagonal of the mixture's predictive covariance of the target columns (Context::get_conditional_var).
+// Throws std::domain_error, before anything is launched, when a component with weight has nu' + Da <= 2.
 void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* groups, const int* given, int ngiven,
-                         const int* target, int ntarget);
+                         const int* target, int ntarget, bool want_var = false);
 // The host table of one Gauss-Wishart posterior for rows with holes, NH = lck::HOLES_MAX + 1:
 //   P [D x D] = nu iW^-1 = A^T A with the whitener A (symmetric)
 //   G [NH]: G[nb] = lgam(e[nb]) - lgam(nu'/2) - (Da/2) log(nu' pi) + (Da log(nu' beta / (1 + beta)) - log|iW| + nb log nu) / 2

@@ -11,9 +11,13 @@ timed with the context's events, so (b) minus the E-step kernel of the same call
 derived from that difference are therefore lower bounds of the kernel's.  At --host-rows rows the host route is timed
 once: rows downloaded, then per cluster a triangular solve, the Student-t term and a GEMM in numpy.  One JSON line.
 
-    python tools/conditional_bench.py [--configs northstar,d32,wide256] [--reps 5] [--host-rows 1000000]
+    python tools/conditional_bench.py [--configs northstar,d32,wide256] [--reps 5] [--host-rows 1000000] [--variance]
 Kernel times: rocprofv3 --kernel-trace --stats -- python tools/conditional_bench.py --reps 3 --host-rows 0 (a run of its
-own)."""
+own).
+
+--variance adds, per shape, the whole call with the predictive variance (lc_model_predict_conditional_var)
+as a third alternating step, and at --host-rows rows the host route extended by the variance in numpy, timed once.  Without
+the flag the output is what it was."""
 import argparse
 import json
 import sys
@@ -52,10 +56,11 @@ def _raw_marginal_estep(ctx, cl, given):
                                                      capi.dptr(iW), capi.dptr(logdW)))
 
 
-def _host_route(Xa, cl, Epi, D, given, target):
-    """what a user did before: per cluster the marginal Student-t term and the linear expert in numpy"""
+def _host_route(Xa, cl, Epi, D, given, target, variance=False):
+    """what a user did before: per cluster the marginal Student-t term and the linear expert in numpy (variance: and the
+    conditional covariance's diagonal, then the mixture's variance centred on the mean)"""
     Da = len(given)
-    T, M = [], []
+    T, M, H = [], [], []
     for k, c in enumerate(cl):
         nu, beta, m, iW = c["nu"], c["beta"], c["mean"], c["iW"]
         nup = nu + 1 - D
@@ -67,15 +72,25 @@ def _host_route(Xa, cl, Epi, D, given, target):
         T.append(np.log(Epi[k]) + G - 0.5 * (nup + Da) * np.log1p(beta / ((1 + beta) * nu) * d2))
         Bk = solve_triangular(Lc.T, solve_triangular(Lc, iW[np.ix_(given, target)], lower=True), lower=False)
         M.append(m[target] + (Xa - m[given]) @ Bk)
+        if variance:
+            Sab = iW[np.ix_(given, target)]
+            schur = np.diag(iW)[target] - np.einsum("ab,ab->b", Sab, Bk)
+            g = (1 + beta) / (beta * (nup + Da - 2))
+            H.append((g * (1 + beta / ((1 + beta) * nu) * d2), schur))
     T = np.stack(T, axis=1)
     logp = logsumexp(T, axis=1)
     mean = np.zeros_like(M[0])
     for k in range(len(cl)):
         mean += np.exp(T[:, k] - logp)[:, None] * M[k]
-    return mean, logp
+    if not variance:
+        return mean, logp
+    var = np.zeros_like(mean)
+    for k in range(len(cl)):
+        var += np.exp(T[:, k] - logp)[:, None] * ((M[k] - mean) ** 2 + H[k][0][:, None] * H[k][1][None, :])
+    return mean, logp, var
 
 
-def run(name, reps, host_rows):
+def run(name, reps, host_rows, variance=False):
     cfg = bench.CONFIGS[name]
     N, D, K, seed = cfg["N"], cfg["D"], cfg["K"], cfg["seed"]
     Da = SPLITS[name]
@@ -95,6 +110,8 @@ def run(name, reps, host_rows):
         _marginal_rows(ctx, N, K, mu, L, given, seed)
         steps = {"raw_estep": _raw_marginal_estep(ctx, cl, given),
                  "conditional": lambda: m.predict_conditional_context(ctx, given, target)}
+        if variance:
+            steps["conditional_var"] = lambda: m.predict_conditional_context(ctx, given, target, variance=True)
         ctx.timing_enable(True)
         for f in steps.values():  # warm-up (allocations, code objects)
             f()
@@ -111,8 +128,8 @@ def run(name, reps, host_rows):
                 t[k].append((time.perf_counter() - t0) * 1e3)
                 te[k].append(ctx.timing_get()["estep_ms"])
         ctx.timing_enable(False)
-        got = ctx.get_conditional(0, 0, min(N, 4096), Db)
-        ref = _host_route(ctx.get_rows(0, 0, min(N, 4096)), cl, Epi, D, given, target)
+        got = ctx.get_conditional(0, 0, min(N, 4096), Db, variance)  # (of the last step: with the variance when asked for)
+        ref = _host_route(ctx.get_rows(0, 0, min(N, 4096)), cl, Epi, D, given, target, variance)
     over = float(np.median(np.array(t["conditional"]) - np.array(te["conditional"])))
     estep_ms = float(np.median(te["conditional"]))
     flops = 2.0 * N * K * (Da + 1) * Db
@@ -135,6 +152,16 @@ def run(name, reps, host_rows):
         "check": {"finite": bool(np.isfinite(got.mean).all() and np.isfinite(got.logp).all()),
                   "max_abs_mean_diff_vs_numpy": float(np.max(np.abs(got.mean - ref[0]))),
                   "max_rel_logp_diff_vs_numpy": float(np.max(np.abs(got.logp - ref[1]) / np.abs(ref[1])))}})
+    if variance:
+        tv, tc = np.array(t["conditional_var"]), np.array(t["conditional"])
+        out["variance"] = {
+            "conditional_var_ms": round(float(np.median(tv)), 4),
+            # the same round's mean-only call subtracted: tables, upload, predict_cond_var_kernel and its synchronisation
+            "var_pass_ms": round(float(np.median(tv - tc)), 4),
+            "var_pass_over_cond_pass": round(float(np.median(tv - tc)) / over, 3),
+            "var_pass_tflops_lower_bound": round(flops / (float(np.median(tv - tc)) * 1e-3) / 1e12, 3),
+            "check": {"finite": bool(np.isfinite(got.var).all()),
+                      "max_rel_var_diff_vs_numpy": float(np.max(np.abs(got.var - ref[2]) / ref[2]))}}
     if host_rows > 0:
         n1 = min(N, host_rows)
         with capi.Context(0) as c1:
@@ -152,9 +179,26 @@ def run(name, reps, host_rows):
             t1 = time.perf_counter()
             _host_route(Xa, cl, Epi, D, given, target)
             t2 = time.perf_counter()
+            if variance:
+                m.predict_conditional_context(c1, given, target, variance=True)  # warm-up
+                devv = []
+                for _ in range(reps):
+                    c1.synchronize()
+                    t3 = time.perf_counter()
+                    m.predict_conditional_context(c1, given, target, variance=True)
+                    c1.synchronize()
+                    devv.append((time.perf_counter() - t3) * 1e3)
+                t3 = time.perf_counter()
+                _host_route(Xa, cl, Epi, D, given, target, variance=True)
+                t4 = time.perf_counter()
         out["host_route"] = {"rows": n1, "device_call_ms": round(float(np.median(dev)), 4),
                              "download_ms": round((t1 - t0) * 1e3, 2), "numpy_ms": round((t2 - t1) * 1e3, 2),
                              "speedup": round((t2 - t0) * 1e3 / float(np.median(dev)), 1)}
+        if variance:
+            out["variance"]["host_route"] = {
+                "rows": n1, "device_call_ms": round(float(np.median(devv)), 4), "download_ms": round((t1 - t0) * 1e3, 2),
+                "numpy_ms": round((t4 - t3) * 1e3, 2),
+                "speedup": round(((t1 - t0) + (t4 - t3)) * 1e3 / float(np.median(devv)), 1)}
     m.close()
     return out
 
@@ -164,8 +208,9 @@ def main():
     ap.add_argument("--configs", default="northstar,d32,wide256")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-rows", type=int, default=1_000_000)
+    ap.add_argument("--variance", action="store_true", help="also time the call with the predictive variance")
     a = ap.parse_args()
-    res = {name: run(name, a.reps, a.host_rows) for name in a.configs.split(",")}
+    res = {name: run(name, a.reps, a.host_rows, a.variance) for name in a.configs.split(",")}
     print(json.dumps({"tool": "conditional_bench", "device": _device_name(), "results": res}))
 
 
