@@ -391,6 +391,28 @@ int lc_model_predict_incomplete(lc_model* m, lc_ctx* ctx, const int* groups /* [
  * bounds, row_stride < D. */
 int lc_ctx_get_completed(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* rows, int64_t row_stride, double* logp,
                          int32_t* count, int32_t* cols);
+/* ---- predictive variance of the filled values (nothing in the reference corresponds).  Everything
+ * lc_model_predict_incomplete does, and per row the diagonal of the mixture's predictive covariance of its holes.  With
+ * a, b, nb as above, Da = D - nb, H = (P_k)_bb, d_a^2 the distance of the known columns and s = beta / ((1 + beta) nu), the
+ * conditional of cluster k's predictive Student-t has nu' + Da degrees of freedom, location M_k(x_a) and the covariance
+ *   Cov_k(x_a) = g_k(nb) (1 + s d_a^2) S_k,  S_k = iW_bb - iW_ba iW_aa^-1 iW_ab = nu H^-1,  g_k(nb) = (1 + beta) / (beta (nu - 1 - nb))
+ *   var_i     = sum_k r_k (Cov_k(x_a)_ii + (M_k,i - mean_i)^2): within the experts plus between them, centred on mean
+ * for hole i of the row, in the order of cols (ascending); the prior component of StickBreak weights takes part as in the
+ * completed rows.  Completed rows, logp, count and cols are those of lc_model_predict_incomplete, bit for bit.
+ * LC_EINVAL: the cases of lc_model_predict_incomplete.  LC_EDOMAIN, after the scan and before anything is written to the
+ * observations: a component with positive weight in some block has nu - 1 - cmax <= 0, where cmax is the largest hole
+ * count of the WHOLE context -- conservative (the row with cmax holes may give that component next to no weight, and may
+ * sit in another block) and strict, as in lc_model_predict_conditional_var.  In practice: a row with a single known
+ * column scored against the prior component of StickBreak weights (nu = D) or a cluster that ended up empty.  The
+ * message names the component and the count; the NaNs stay, no prediction is left on ctx, and
+ * lc_model_predict_incomplete on the same context still works.  A context without holes never fails this check. */
+int lc_model_predict_incomplete_var(lc_model* m, lc_ctx* ctx, const int* groups /* [J of ctx] or NULL */);
+/* rows [row0, row0+n) of block j of the variance of the last lc_model_predict_incomplete_var on ctx: var is n x LC_HOLES_MAX
+ * with row_stride doubles between rows (>= LC_HOLES_MAX); slot i belongs to cols[i] of lc_ctx_get_completed, the slots
+ * i >= count are exactly 0.0, and so is every slot of a row without holes.  var may be NULL (the checks only).  LC_EINVAL:
+ * no incomplete prediction on ctx, one without variance (lc_model_predict_incomplete), a row range out of bounds,
+ * row_stride < LC_HOLES_MAX. */
+int lc_ctx_get_completed_var(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* var, int64_t row_stride);
 /* ---- ranking on the device (nothing in the reference corresponds): the m best rows of each of C device-resident
  * columns, 1 <= m <= 64, without bringing the columns to the host.  Entry a is better than entry b when its score is larger
  * (largest != 0; smaller otherwise), or the scores compare equal (+0.0 and -0.0 do) and a comes first in the context (lower
@@ -527,6 +549,12 @@ int lc_gw_conditional_var(int D, double nu, double beta, const double* iW, const
  * entries.  Any output may be NULL.  LC_EINVAL: nu <= D - 1, beta <= 0, iW not positive definite. */
 int lc_gw_precision(int D, double nu, double beta, const double* m, const double* iW, double* P, double* G, double* s,
                     double* e);
+/* The table of lc_model_predict_incomplete_var from the same posterior: for nb = 0 ... LC_HOLES_MAX holes
+ *   g[nb] = (1 + beta) / (beta (nu' + Da - 2)) = (1 + beta) / (beta (nu - 1 - nb))
+ * so that the conditional covariance of the holes b is g[nb] (1 + s d_a^2) nu (P_bb)^-1; NaN where nb >= D (no known
+ * column) or nu - 1 - nb <= 0 (the covariance does not exist).  g[0] is the g of lc_gw_conditional_var with every column
+ * given.  g has LC_HOLES_MAX + 1 entries.  LC_EINVAL: D < 1, nu <= D - 1, beta <= 0, g NULL. */
+int lc_gw_precision_var(int D, double nu, double beta, double* g);
 /* NormGamma: addobs sums -> update() (distributions.cpp:441-464), fenergy (:508-517), Eloglike constant (:486-488).
  * xs, xxs: D values each (sum q x, sum q x.^2). */
 int lc_ng_mstep(double clustwidth, int D, double Ns, const double* xs, const double* xxs, double* nu, double* beta,

@@ -67,6 +67,20 @@ class Completion(NamedTuple):
     count: np.ndarray
     cols: np.ndarray
 
+    @property
+    def var(self):
+        return None
+
+
+class CompletionVar(NamedTuple):
+    """Completion with the predictive variance of the filled values (lc_model_predict_incomplete_var): var (N, HOLES_MAX),
+    slot i belongs to cols[:, i]; 0 beyond count and in rows without holes."""
+    rows: np.ndarray
+    logp: np.ndarray
+    count: np.ndarray
+    cols: np.ndarray
+    var: np.ndarray
+
 
 HOLES_MAX = 8  # LC_HOLES_MAX: the NaNs one row may hold
 
@@ -307,6 +321,9 @@ def lib() -> C.CDLL:
                                        c_int32_p, c_int32_p]
     L.lc_gw_precision.argtypes = [C.c_int, C.c_double, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p,
                                   c_double_p, c_double_p]
+    L.lc_model_predict_incomplete_var.argtypes = [C.c_void_p, C.c_void_p, c_int_p]
+    L.lc_ctx_get_completed_var.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, C.c_int64]
+    L.lc_gw_precision_var.argtypes = [C.c_int, C.c_double, C.c_double, c_double_p]
     _lib = L
     return L
 
@@ -663,16 +680,21 @@ class Context:
         check(lib().lc_ctx_get_conditional_var(self._h, j, row0, n, dptr(var), ntarget))
         return ConditionalVar(mean, logp, var)
 
-    def get_completed(self, j, row0, n):
+    def get_completed(self, j, row0, n, variance=False):
         """Rows [row0, row0+n) of block j after the last Model.predict_incomplete_context on this context ->
-        Completion(rows (n, D), logp (n,), count (n,), cols (n, HOLES_MAX))."""
+        Completion(rows (n, D), logp (n,), count (n,), cols (n, HOLES_MAX)).  variance: CompletionVar, with var
+        (n, HOLES_MAX) (lc_ctx_get_completed_var; ValueError when that call was made without variance=True)."""
         D = self.dims()[1]
         rows, logp = np.zeros((n, D)), np.zeros(n)
         count, cols = np.zeros(n, dtype=np.int32), np.full((n, HOLES_MAX), -1, dtype=np.int32)
         c_int32_p = C.POINTER(C.c_int32)
         check(lib().lc_ctx_get_completed(self._h, j, row0, n, dptr(rows), D, dptr(logp), count.ctypes.data_as(c_int32_p),
                                          cols.ctypes.data_as(c_int32_p)))
-        return Completion(rows, logp, count, cols)
+        if not variance:
+            return Completion(rows, logp, count, cols)
+        var = np.zeros((n, HOLES_MAX))
+        check(lib().lc_ctx_get_completed_var(self._h, j, row0, n, dptr(var), HOLES_MAX))
+        return CompletionVar(rows, logp, count, cols, var)
 
     def top_rows(self, m, by="qz", largest=True, ncols=None, by_label=False):
         """TopRows of the m best rows (1 ... 64) of each column, ranked on the device (lc_ctx_top_rows): by="qz" the first
@@ -902,29 +924,33 @@ class Model:
         return (Xs, var) if blocks else (Xs[0], var[0])
 
     # -- rows with holes -------------------------------------------------------------------------------
-    def predict_incomplete_context(self, ctx, groups=None):
+    def predict_incomplete_context(self, ctx, groups=None, variance=False):
         """Complete the full-width rows resident in ctx in place: every NaN (up to HOLES_MAX per row, every row its own
         set) becomes E[x_unknown | x_known, training data] (lc_model_predict_incomplete).  Nothing is downloaded: read
-        the rows with ctx.get_completed.  A second call on the same context finds no NaN any more."""
+        the rows with ctx.get_completed.  A second call on the same context finds no NaN any more.
+        variance: also the predictive variance of every filled value (lc_model_predict_incomplete_var; DomainError, with
+        the NaNs left in place, where it does not exist); read it with ctx.get_completed(..., variance=True)."""
         g = None
         if groups is not None:
             garr = np.ascontiguousarray(groups, dtype=np.int32)
             if garr.shape != (ctx.dims()[0],):
                 raise ValueError("groups needs one learned group index per block of the context")
             g = garr.ctypes.data_as(c_int_p)
-        check(lib().lc_model_predict_incomplete(self._h, ctx._h, g))
+        fn = lib().lc_model_predict_incomplete_var if variance else lib().lc_model_predict_incomplete
+        check(fn(self._h, ctx._h, g))
 
-    def predict_incomplete(self, X, groups=None, device=0):
+    def predict_incomplete(self, X, groups=None, device=0, variance=False):
         """Completion(rows, logp, count, cols) for the host rows X ((N, D) array, NaN = unknown), or a list of them for a
-        list of blocks (block b mixed with learned group groups[b], default 0).  rows is a filled copy: X keeps its NaNs."""
+        list of blocks (block b mixed with learned group groups[b], default 0).  rows is a filled copy: X keeps its NaNs.
+        variance: CompletionVar, with var (N, HOLES_MAX) the predictive variance of the filled values."""
         blocks = isinstance(X, (list, tuple))
         Xs = self._blocks(X)
         if not Xs:
             return []
         with Context(device) as ctx:
             ctx.set_data(Xs)
-            self.predict_incomplete_context(ctx, groups)
-            out = [ctx.get_completed(j, 0, x.shape[0]) for j, x in enumerate(Xs)]
+            self.predict_incomplete_context(ctx, groups, variance)
+            out = [ctx.get_completed(j, 0, x.shape[0], variance) for j, x in enumerate(Xs)]
         return out if blocks else out[0]
 
     # -- ranking (DESIGN 4.13) -------------------------------------------------------------------------------------
@@ -1059,6 +1085,14 @@ def gw_precision(nu, beta, m, iW):
     P, G, e, s = np.zeros((D, D)), np.zeros(HOLES_MAX + 1), np.zeros(HOLES_MAX + 1), C.c_double()
     check(lib().lc_gw_precision(D, nu, beta, dptr(m), dptr(iW), dptr(P), dptr(G), C.byref(s), dptr(e)))
     return {"P": P, "G": G, "s": s.value, "e": e}
+
+
+def gw_precision_var(nu, beta, D):
+    """The table of the variance of filled values (lc_gw_precision_var): g (HOLES_MAX + 1 values, one per hole count) =
+    (1 + beta) / (beta (nu - 1 - nb)); NaN where nb >= D or the variance does not exist."""
+    g = np.zeros(HOLES_MAX + 1)
+    check(lib().lc_gw_precision_var(D, nu, beta, dptr(g)))
+    return g
 
 
 def ng_mstep(clustwidth, Ns, xs, xxs):

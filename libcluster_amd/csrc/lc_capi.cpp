@@ -1194,6 +1194,24 @@ int lc_ctx_get_completed(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* ro
   });
 }
 
+// ---- predictive variance of the filled values --------------------------
+int lc_model_predict_incomplete_var(lc_model* m, lc_ctx* ctx, const int* groups) {
+  return guarded([&] {
+    need(m, "model");
+    need(ctx, "ctx");
+    ctx->impl.predict_clear();  // (a failure leaves no prediction behind)
+    if (!model_alive(m)) throw std::invalid_argument("the model was freed");
+    lcp::predict_incomplete(ctx->impl, m->model, groups, /*want_var=*/true);
+  });
+}
+
+int lc_ctx_get_completed_var(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* var, int64_t row_stride) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.get_completed_var(j, row0, n, var, row_stride);
+  });
+}
+
 // ---- ranking -----------------------------------------------------
 int lc_ctx_top_rows(lc_ctx* ctx, int what, int ncols, int m, int largest, int by_label, int32_t* count, int32_t* group,
                     int64_t* row, double* score) {
@@ -1324,6 +1342,14 @@ int lc_gw_precision(int D, double nu, double beta, const double* m, const double
     need(iW, "iW");
     if (D < 1) throw std::invalid_argument("D must be >= 1!");
     lcp::gw_precision(D, nu, beta, iW, P, G, s, e);
+  });
+}
+
+int lc_gw_precision_var(int D, double nu, double beta, double* g) {
+  return guarded([&] {
+    need(g, "g");
+    if (D < 1) throw std::invalid_argument("D must be >= 1!");
+    lcp::gw_precision_var(D, nu, beta, g);
   });
 }
 

@@ -9,6 +9,7 @@
 
 #include <cmath>
 #include <limits>
+#include <type_traits>
 
 #include "lc_device.hpp"
 #include "lc_predict.hpp"
@@ -98,7 +99,41 @@ __global__ __launch_bounds__(HS_THREADS) void holes_fill_kernel(HolesFillLaunch 
   }
 }
 
-__global__ __launch_bounds__(PH_THREADS) void predict_holes_kernel(PredictHolesLaunch a) {
+// The fold of predict_holes_kernel's u loop (described there) for the variance sums: eight sums over the wave in ten
+// exchanges, a fixed tree.  Lane l ends with the sum of acc[i], i = bit5 + 2 bit4 + 4 bit3 of l.  (The u loop keeps its
+// own copy of these lines: with a call to this function there the mean-only instance takes 236 registers, not 222.)
+static_assert(HOLES_MAX == 8, "the fold below halves eight values three times");
+__device__ __forceinline__ double fold8(const double (&acc)[HOLES_MAX], int lane) {
+  const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8;
+  double v4[4], v2[2];
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+    v4[p] = (b5 ? acc[2 * p + 1] : acc[2 * p]) + __shfl_xor(b5 ? acc[2 * p] : acc[2 * p + 1], 32);
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+    v2[p] = (b4 ? v4[2 * p + 1] : v4[2 * p]) + __shfl_xor(b4 ? v4[2 * p] : v4[2 * p + 1], 16);
+  double v1 = (b3 ? v2[1] : v2[0]) + __shfl_xor(b3 ? v2[0] : v2[1], 8);
+  v1 += __shfl_xor(v1, 4);
+  v1 += __shfl_xor(v1, 2);
+  v1 += __shfl_xor(v1, 1);
+  return v1;
+}
+
+// predict_holes_kernel<false> is the kernel of DESIGN 4.15 as it was (222 registers, two waves per SIMD, no scratch):
+// every addition sits behind if constexpr.  <true> also forms the variance of the filled values; it is
+// held to two waves per SIMD, which it reaches without scratch (248 registers) with the fill values in scalar registers.
+__device__ __forceinline__ const PredictHolesLaunch& holes_args(const PredictHolesLaunch& x) { return x; }
+__device__ __forceinline__ const PredictHolesLaunch& holes_args(const PredictHolesVarLaunch& x) { return x.h; }
+template <bool VAR>
+__global__ __launch_bounds__(PH_THREADS, VAR ? 2 : 0) void predict_holes_kernel(
+    std::conditional_t<VAR, PredictHolesVarLaunch, PredictHolesLaunch> aa) {
+  const PredictHolesLaunch& a = holes_args(aa);
+  [[maybe_unused]] const double* __restrict__ gnu = nullptr;
+  [[maybe_unused]] double* __restrict__ var = nullptr;
+  if constexpr (VAR) {
+    gnu = aa.gnu;
+    var = aa.var;
+  }
   __shared__ double etab[64];
   __shared__ LogEntry ltab[128];
   __shared__ double uslab[PH_THREADS / 64][64][HOLES_MAX];  // per wave: u of up to 64 clusters (16 KB in all)
@@ -132,6 +167,10 @@ __global__ __launch_bounds__(PH_THREADS) void predict_holes_kernel(PredictHolesL
       }
     }
     a.logp[row] = mp + log(sp);
+    if constexpr (VAR) {
+#pragma unroll
+      for (int i = 0; i < HOLES_MAX; ++i) var[(size_t)row * HOLES_MAX + i] = 0.0;
+    }
   }
 
   // The rows with holes of this wave, one after the other.  Everything a row decides -- its position, nb, the hole
@@ -150,6 +189,9 @@ __global__ __launch_bounds__(PH_THREADS) void predict_holes_kernel(PredictHolesL
     for (int i = 0; i < HOLES_MAX; ++i) {
       c[i] = i < nb ? __builtin_amdgcn_readfirstlane(a.cols[(size_t)hr * HOLES_MAX + i]) : 0;
       xb[i] = i < nb ? xr[c[i]] : 0.0;
+      if constexpr (VAR)  // (the same value in every lane: into scalar registers, the vector ones are the tight spot)
+        xb[i] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(xb[i])),
+                                 __builtin_amdgcn_readfirstlane(__double2loint(xb[i])));
     }
     const double* __restrict__ tt = a.ttab + ((size_t)jh * NH + nb) * Kp;
     const double* __restrict__ pe = a.pexp + (size_t)nb * Kp;
@@ -157,6 +199,9 @@ __global__ __launch_bounds__(PH_THREADS) void predict_holes_kernel(PredictHolesL
     double mrun = NINF, ssum = 0.0, esum[HOLES_MAX];
 #pragma unroll
     for (int i = 0; i < HOLES_MAX; ++i) esum[i] = 0.0;
+    // VAR: lane l carries ONE more running sum, that of the hole fold8 leaves in l: sum_k e_k (Cov_k,ii + w_k,i^2)
+    [[maybe_unused]] double vsum = 0.0;
+    [[maybe_unused]] const double* __restrict__ gv = VAR ? gnu + (size_t)nb * Kp : nullptr;
     for (int k0 = 0; k0 < Kp; k0 += 64) {
       const int kc = Kp - k0 < 64 ? Kp - k0 : 64;
       // u = (P_k y)_b: the lanes own the columns of row b_i of P_k (a coalesced read), a sum over the wave per (i, k); the
@@ -173,10 +218,6 @@ __global__ __launch_bounds__(PH_THREADS) void predict_holes_kernel(PredictHolesL
           for (int i = 0; i < HOLES_MAX; ++i)
             if (i < nb) acc[i] = fma(Pk[(size_t)c[i] * DP + d], y, acc[i]);
         }
-        // The eight sums over the wave in ten exchanges instead of 48: three steps halve the number of values a lane
-        // carries (the lanes with bit 5 / 4 / 3 set keep the odd member of each pair and hand over the even one), three
-        // more sum the eight lanes that are left with the same value.  Lane l ends with u_i, i = bit5 + 2 bit4 + 4 bit3.
-        static_assert(HOLES_MAX == 8, "the fold below halves eight values three times");
         const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8;
         double v4[4], v2[2];
 #pragma unroll
@@ -243,6 +284,31 @@ __global__ __launch_bounds__(PH_THREADS) void predict_holes_kernel(PredictHolesL
         for (int q = i + 1; q < HOLES_MAX; ++q) v = fma(-L[q][i], u[q], v);
         u[i] = v * inv[i];
       }
+      // VAR: (H^-1)_ii = ||L^-1 e_i||^2, one forward solve per hole on eight temporaries (L's last use); the identity
+      // padding adds nothing, so the rows j >= nb are skipped
+      [[maybe_unused]] double hd[HOLES_MAX];
+      if constexpr (VAR) {
+#pragma unroll
+        for (int i = 0; i < HOLES_MAX; ++i) {
+          hd[i] = 0.0;
+          if (i < nb) {
+            double x[HOLES_MAX];
+            x[i] = inv[i];
+            double s2 = x[i] * x[i];
+#pragma unroll
+            for (int r = i + 1; r < HOLES_MAX; ++r) {
+              if (r < nb) {
+                double v = 0.0;
+#pragma unroll
+                for (int q = i; q < r; ++q) v = fma(-L[r][q], x[q], v);
+                x[r] = v * inv[r];
+                s2 = fma(x[r], x[r], s2);
+              }
+            }
+            hd[i] = s2;
+          }
+        }
+      }
       const double d2full = -2.0 * a.col[(size_t)k * a.ldq + hr];
       const double d2a = fmax(d2full - quad, 0.0);
       const double t = on ? tt[k] - log(prod) - pe[k] * log1p_nonneg(a.pscale[k] * d2a, ltab) : NINF;
@@ -250,10 +316,41 @@ __global__ __launch_bounds__(PH_THREADS) void predict_holes_kernel(PredictHolesL
       const double mnew = fmax(mrun, wave_max(t));
       const double f = exp_nonpos(mrun - mnew, etab), e = exp_nonpos(t - mnew, etab);
       ssum = fma(ssum, f, wave_sum(e));
+      // VAR: Cov_k,ii = g_k(nb) nu_k (1 + s_k d_a^2) (H^-1)_ii, and the second moment of the expert about the fill value;
+      // d_a^2 is multiplied, never exponentiated: a far row stays finite
+      [[maybe_unused]] double hk = 0.0, vacc[HOLES_MAX];
+      if constexpr (VAR) hk = gv[k] * fma(a.pscale[k], d2a, 1.0);
 #pragma unroll
-      for (int i = 0; i < HOLES_MAX; ++i)
-        if (i < nb) esum[i] = fma(esum[i], f, wave_sum(e * (xb[i] - u[i])));
+      for (int i = 0; i < HOLES_MAX; ++i) {
+        if constexpr (VAR) vacc[i] = 0.0;
+        if (i < nb) {
+          const double ex = xb[i] - u[i];  // the expert
+          esum[i] = fma(esum[i], f, wave_sum(e * ex));
+          // w_i is taken back out of the expert, the ONE value both instances form: u keeps the uses it has in the
+          // mean-only instance, the compiler contracts the subtraction above alike in both, and X gets the same bits
+          if constexpr (VAR) {
+            const double wd = xb[i] - ex;
+            vacc[i] = e * fma(hk, hd[i], wd * wd);
+          }
+        }
+      }
+      if constexpr (VAR) vsum = fma(vsum, f, fold8(vacc, lane));
       mrun = mnew;
+    }
+    if constexpr (VAR) {
+      // lane 0 collects the eight sums from the lanes that hold them (lane 32 holds hole 1, 16 hole 2, 48 hole 3, 8 hole 4, ...)
+      double vs[HOLES_MAX];
+#pragma unroll
+      for (int i = 0; i < HOLES_MAX; ++i) vs[i] = __shfl(vsum, ((i & 1) << 5) | ((i & 2) << 3) | ((i & 4) << 1));
+      if (lane == 0) {
+        // var_i = sum_k r_k (Cov_k,ii + w_k,i^2) - (sum_k r_k w_k,i)^2 with sum_k r_k w_k,i = fill_i - mean_i: centred
+        // on the mean through deviations from the fill value, which lies among the data
+#pragma unroll
+        for (int i = 0; i < HOLES_MAX; ++i) {
+          const double dw = xb[i] - esum[i] / ssum;
+          var[(size_t)hr * HOLES_MAX + i] = i < nb ? fma(-dw, dw, vs[i] / ssum) : 0.0;
+        }
+      }
     }
     if (lane == 0) {
       a.logp[hr] = mrun + log(ssum);
@@ -296,7 +393,15 @@ hipError_t launch_predict_holes(const PredictHolesLaunch& a, hipStream_t stream)
   const int64_t rows = a.nrg * RG;
   if (rows == 0) return hipSuccess;
   if (a.Kp < 1 || a.DP < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(predict_holes_kernel, dim3((unsigned)((rows + PH_THREADS - 1) / PH_THREADS)), dim3(PH_THREADS), 0, stream, a);
+  hipLaunchKernelGGL(predict_holes_kernel<false>, dim3((unsigned)((rows + PH_THREADS - 1) / PH_THREADS)), dim3(PH_THREADS), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_predict_holes_var(const PredictHolesVarLaunch& a, hipStream_t stream) {
+  const int64_t rows = a.h.nrg * RG;
+  if (rows == 0) return hipSuccess;
+  if (a.h.Kp < 1 || a.h.DP < 1 || !a.gnu || !a.var) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(predict_holes_kernel<true>, dim3((unsigned)((rows + PH_THREADS - 1) / PH_THREADS)), dim3(PH_THREADS), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -311,12 +311,14 @@ void Context::holes_fill(const double* fill) {
 }
 
 void Context::predict_holes(int Kp, const double* tt, const double* ps, const double* pe, const double* mean,
-                            const double* P) {
+                            const double* P, const double* gnu) {
   use_device();
   if (Kp < 1) throw std::invalid_argument("K must be >= 1");
   pred_holes_ = false;
+  pred_holes_var_ = false;
   if (NP_ == 0) {
     pred_holes_ = true;
+    pred_holes_var_ = gnu != nullptr;
     return;
   }
   if (qz_[cur_].cap < Kp || !qz_[cur_].buf.p) throw std::logic_error("predict_holes: no raw E-step columns");
@@ -324,10 +326,12 @@ void Context::predict_holes(int Kp, const double* tt, const double* ps, const do
   constexpr int NH = lck::HOLES_MAX + 1;
   const int D = D_, DP = DP_;
   hlogp_.reserve((size_t)NP_);
-  // tables: [tt J x NH x Kp | ps Kp | pe NH x Kp | mean Kp x DP | P Kp x DP x DP], the pads zero
+  if (gnu) hvar_.reserve((size_t)NP_ * lck::HOLES_MAX);
+  // tables: [tt J x NH x Kp | ps Kp | pe NH x Kp | mean Kp x DP | P Kp x DP x DP], the pads zero; with gnu: [... | gnu NH x Kp]
   const size_t nt = (size_t)J_ * NH * Kp, ne = (size_t)NH * Kp, nm = (size_t)Kp * DP, nP = nm * DP;
-  hpack_.assign(nt + (size_t)Kp + ne + nm + nP, 0.0);
+  hpack_.assign(nt + (size_t)Kp + ne + nm + nP + (gnu ? ne : 0), 0.0);
   double* h = hpack_.data();
+  if (gnu) std::copy(gnu, gnu + ne, h + nt + Kp + ne + nm + nP);
   std::copy(tt, tt + nt, h);
   std::copy(ps, ps + Kp, h + nt);
   std::copy(pe, pe + ne, h + nt + Kp);
@@ -357,12 +361,35 @@ void Context::predict_holes(int Kp, const double* tt, const double* ps, const do
   a.mean = ptab_.p + nt + Kp + ne;
   a.P = a.mean + nm;
   a.logp = hlogp_.p;
-  LC_HIP(lck::launch_predict_holes(a, stream_));
+  if (gnu) {
+    lck::PredictHolesVarLaunch v;
+    v.h = a;
+    v.gnu = a.P + nP;
+    v.var = hvar_.p;
+    LC_HIP(lck::launch_predict_holes_var(v, stream_));
+  } else {
+    LC_HIP(lck::launch_predict_holes(a, stream_));
+  }
   LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ and ptab_ are free again)
   qz_[cur_].K = Kp;
   qz_[cur_].hash_ok = false;
   dcache_invalidate();  // (the observations changed)
   pred_holes_ = true;
+  pred_holes_var_ = gnu != nullptr;
+}
+
+void Context::get_completed_var(int j, int64_t row0, int64_t n, double* var, int64_t row_stride) const {
+  use_device();
+  if (!pred_holes_) throw std::invalid_argument("the context holds no completed rows (lc_model_predict_incomplete_var)");
+  if (!pred_holes_var_)
+    throw std::invalid_argument("the context's completed rows have no variance (lc_model_predict_incomplete_var)");
+  if (j < 0 || j >= J_ || row0 < 0 || n < 0 || row0 + n > Nj_[j]) throw std::invalid_argument("row range out of bounds");
+  if (row_stride < lck::HOLES_MAX) throw std::invalid_argument("row_stride is smaller than LC_HOLES_MAX");
+  if (n == 0 || !var) return;
+  const size_t at = (size_t)(goff_[j] + row0), w = (size_t)lck::HOLES_MAX * sizeof(double);
+  LC_HIP(hipMemcpy2DAsync(var, (size_t)row_stride * sizeof(double), hvar_.p + at * lck::HOLES_MAX, w, w, (size_t)n,
+                          hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
 }
 
 void Context::get_completed(int j, int64_t row0, int64_t n, double* rows, int64_t row_stride, double* logp, int32_t* count,
@@ -802,7 +829,17 @@ void gw_precision(int D, double nu, double beta, const double* iW, double* P, do
   if (s) *s = beta / ((1 + beta) * nu);
 }
 
-void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* groups) {
+void gw_precision_var(int D, double nu, double beta, double* g) {
+  constexpr int NH = lck::HOLES_MAX + 1;
+  const double nup = nu + 1 - D;  // (the checks of gw_precision)
+  if (!(nup > 0.0) || !(beta > 0.0)) throw std::invalid_argument("nu must exceed D - 1 and beta must be positive");
+  for (int nb = 0; nb < NH; ++nb) {
+    const double dof2 = nu - 1 - nb;  // nu' + Da - 2 with Da = D - nb
+    g[nb] = nb >= D || !(dof2 > 0.0) ? std::numeric_limits<double>::quiet_NaN() : (1 + beta) / (beta * dof2);
+  }
+}
+
+void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* groups, bool want_var) {
   ctx.predict_clear();  // (whatever an earlier prediction left must not outlive a failure of this one)
   constexpr int NH = lck::HOLES_MAX + 1;
   const int K = (int)model.clusters.size(), J = (int)model.weights.size(), Jc = ctx.J();
@@ -870,10 +907,36 @@ void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* g
                                 " columns: at most " + std::to_string(lck::HOLES_MAX) +
                                 " per row, and at least one known column (lc_model_predict_conditional takes a pattern "
                                 "shared by all rows, of any size)");
+  // the variance's table g_k(nb) nu_k, 0 where the variance does not exist: an error when a row can meet such an entry
+  // (a component with weight in some block, at the largest hole count of the context), never read otherwise
+  std::vector<double> gnu;
+  if (want_var) {
+    gnu.assign((size_t)NH * Kp, 0.0);
+    for (int k = 0; k < Kp; ++k) {
+      const lch::GaussWishState& g = k < K ? model.clusters[(size_t)k].gw : prior.gw;
+      if (holed > 0 && !(g.nu - 1 - max_count > 0.0)) {
+        bool weighted = false;
+        for (int b = 0; b < Jc; ++b) {
+          const int j = groups ? groups[b] : 0;
+          weighted = weighted || (k < K ? Epi[(size_t)j * K + k] : Erest[(size_t)j]) > 0.0;
+        }
+        if (weighted)  // (nothing was written to X so far)
+          throw std::domain_error("the variance of the filled values does not exist: " +
+                                  (k < K ? "cluster " + std::to_string(k) : std::string("the prior component")) + " has nu - 1 - " +
+                                  std::to_string(max_count) + " = " + std::to_string(g.nu - 1 - max_count) +
+                                  ", which is not above 0, and a row of the context has " + std::to_string(max_count) +
+                                  " unknown values (the completed rows and logp of lc_model_predict_incomplete do exist)");
+      }
+      double gk[NH];
+      gw_precision_var(D, g.nu, g.beta, gk);
+      for (int nb = 0; nb < NH; ++nb)
+        if (gk[nb] == gk[nb]) gnu[(size_t)nb * Kp + k] = gk[nb] * g.nu;
+    }
+  }
   if (holed > 0) ctx.holes_fill(fill.data());
   // one raw E-step at full width over the K clusters (+ the prior's whitener): -d_full^2 / 2 per column
   ctx.estep(Kp, A.data(), m.data(), zero.data(), nullptr, nullptr, /*raw=*/true);
-  ctx.predict_holes(Kp, tt.data(), ps.data(), pe.data(), m.data(), P.data());
+  ctx.predict_holes(Kp, tt.data(), ps.data(), pe.data(), m.data(), P.data(), want_var ? gnu.data() : nullptr);
 }
 
 void exemplars(lcc::Context& ctx, const lce::Model& model, bool sparse, const int* groups, int mtop, int32_t* count,

@@ -177,6 +177,20 @@ struct PredictHolesLaunch {
 };
 hipError_t launch_predict_holes(const PredictHolesLaunch& a, hipStream_t stream);
 
+// predict_holes_var_kernel: everything predict_holes_kernel does, with the same bits in X and logp, and per
+// row the predictive variance of every filled value.  With w = H^-1 u and S_k = nu_k H^-1 the Schur complement of iW_k:
+//   Cov_k,ii = gnu[nb][k] (1 + s_k d_a^2) (H^-1)_ii,  (H^-1)_ii = ||L^-1 e_i||^2 (one forward solve per hole)
+//   var_i    = sum_k r_k (Cov_k,ii + w_k,i^2) - (sum_k r_k w_k,i)^2   (M_k,i - fill_i = -w_k,i: centred on the mean)
+// var[row][i] belongs to cols[row][i]; the slots i >= count and all eight slots of a row without holes are 0.  Every valid
+// row's eight slots are written.  One more running sum per lane (the fold of u leaves hole i's sum in the lanes that
+// own it), no atomics, a fixed tree: the same bits on every call and wherever the row sits in its block.
+struct PredictHolesVarLaunch {
+  PredictHolesLaunch h;         // as launched without variance
+  const double* gnu = nullptr;  // [(HOLES_MAX + 1) x Kp] g_k(nb) nu_k; 0 where the variance does not exist
+  double* var = nullptr;        // [NP x HOLES_MAX]
+};
+hipError_t launch_predict_holes_var(const PredictHolesVarLaunch& a, hipStream_t stream);
+
 }  // namespace lck
 
 namespace lch {
@@ -230,7 +244,14 @@ void gw_precision(int D, double nu, double beta, const double* iW, double* P, do
 // per row and the hole records in the context (Context::get_completed).  Gauss-Wishart models only; all K clusters take
 // part (and the prior component of StickBreak weights).  Throws std::invalid_argument, with the observations untouched,
 // for a row with more than lck::HOLES_MAX holes or without a known column.
-void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* groups);
+// want_var: also the predictive variance of every filled value (Context::get_completed_var).  Throws
+// std::domain_error, after the scan and before anything is written to the observations, when a component with weight in
+// some block has nu - 1 - cmax <= 0 with cmax the largest hole count of the WHOLE context (conservative and strict).
+void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* groups, bool want_var = false);
+// The table of that variance: g[nb] = (1 + beta) / (beta (nu' + Da - 2)) = (1 + beta) / (beta (nu - 1 - nb)) for nb = 0 ...
+// lck::HOLES_MAX holes, so that cluster k's conditional covariance is g[nb] (1 + s d_a^2) nu (P_bb)^-1; NaN where nb >= D or
+// nu - 1 - nb <= 0.  Throws std::invalid_argument for nu <= D - 1, beta <= 0.
+void gw_precision_var(int D, double nu, double beta, double* g);
 // E[pi_k] (K values) and the mass beyond the truncation E[pi_rest] of a weight distribution in its updated state:
 //   Dirichlet:  alpha_k / sum(alpha), no rest
 //   StickBreak: E[v_k] prod_{i before k} E[1 - v_i] in ordvec order (distributions.cpp:139-165), rest prod_i E[1 - v_i]

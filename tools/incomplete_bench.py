@@ -12,7 +12,13 @@ Kernel times come from a run of their own per (shape, share): this tool starts i
 `rocprofv3 --kernel-trace` (--child) and sums, per kernel, the dispatches of the one timed call -- from the last
 holes_scan_kernel dispatch on -- and of the lc_model_predict that follows it.  One JSON line.
 
-    python tools/incomplete_bench.py [--configs northstar,d32] [--shares 0,1,10,100] [--reps 2] [--no-kernels]"""
+    python tools/incomplete_bench.py [--configs northstar,d32] [--shares 0,1,10,100] [--reps 2] [--no-kernels]
+
+--variance: per shape and share also the whole call with variance (lc_model_predict_incomplete_var), timed
+in turns with the mean-only call of the same run, and its kernels from a profiled run of its own.  The variance of the
+first rows with holes (up to --check-rows) is held against numpy (tests/incomplete_var_ref.py, direct_var) relative to var
+itself, and the time numpy took for them -- the host route: rows on the host, one factorisation per row and cluster --
+is recorded beside, per row with holes.  Such a line is kept in profiles/incomplete_var_bench_line.json."""
 import argparse
 import csv
 import json
@@ -28,6 +34,7 @@ import numpy as np
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tools"))
+sys.path.insert(0, str(ROOT / "tests"))  # (--variance: the numpy reference of the tests)
 import bench  # noqa: E402
 from libcluster_amd import capi  # noqa: E402
 from predict_bench import _data, _device_name  # noqa: E402
@@ -79,22 +86,56 @@ def _timed(ctx, f):
     return (time.perf_counter() - t0) * 1e3
 
 
-def _wall(m, X, share, reps, seed):
+def _check_var(m, Xh, got, check_rows):
+    """var of the first rows with holes against numpy, relative to var itself, and what numpy took per such row"""
+    import incomplete_var_ref as vref
+
+    J, K, D = m.dims()
+    cls = []
+    for k in range(K):
+        p = m.cluster(k)
+        cls.append((p["nu"], p["beta"], p["mean"], p["iW"]))
+    Epi, rest = capi.weights_predictive(m.kinds()[0], m.weights(0)[1])
+    head = Xh[: got.rows.shape[0]]
+    pick = np.flatnonzero(np.isnan(head).any(axis=1))[:check_rows]
+    if not pick.size:
+        return {"rows": 0}
+    t0 = time.perf_counter()
+    var, Vn, _, _ = vref.direct_var(head[pick], cls, (float(D), 1.0, np.zeros(D), D * np.eye(D)), Epi, rest)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    used = var > 0
+    return {"rows": int(pick.size), "max_rel_to_var": float(np.max(np.abs(got.var[pick] - var)[used] / var[used])),
+            "max_rel_to_Vn": float(np.max(np.abs(got.var[pick] - var) / Vn[:, None])),
+            "zeros_ok": bool(not got.var[pick][~used].any() and not got.var[~np.isnan(head).any(axis=1)].any()),
+            "host_route_us_per_hole_row": round(host_ms * 1e3 / pick.size, 2)}
+
+
+def _wall(m, X, share, reps, seed, variance=False, check_rows=2048):
     Xh, nrows, nholes = _punch(X, share, seed)
-    t, tp = [], []
+    t, tp, tv = [], [], []
     with capi.Context(0) as ctx:
         for _ in range(reps):
             ctx.set_data(Xh)
             t.append(_timed(ctx, lambda: m.predict_incomplete_context(ctx)))
-        got = ctx.get_completed(0, 0, min(X.shape[0], 4096))
+            if variance:  # (in turns: both calls see the same state of the box)
+                ctx.set_data(Xh)
+                tv.append(_timed(ctx, lambda: m.predict_incomplete_context(ctx, variance=True)))
+        got = ctx.get_completed(0, 0, min(X.shape[0], 4096), variance=variance)
         ctx.set_data(X)
         for _ in range(reps):
             tp.append(_timed(ctx, lambda: m.predict_context(ctx)))
     head = Xh[: got.rows.shape[0]]
     ok = bool(np.isfinite(got.rows).all() and np.isfinite(got.logp).all()
               and np.array_equal(got.count, np.isnan(head).sum(axis=1)) and np.array_equal(got.rows[~np.isnan(head)], head[~np.isnan(head)]))
-    return {"hole_rows": nrows, "holes": nholes, "incomplete_ms": round(float(np.median(t)), 3),
-            "predict_ms": round(float(np.median(tp)), 3), "check_ok": ok}
+    out = {"hole_rows": nrows, "holes": nholes, "incomplete_ms": round(float(np.median(t)), 3),
+           "predict_ms": round(float(np.median(tp)), 3), "check_ok": ok}
+    if variance:
+        out["incomplete_runs_ms"] = [round(x, 3) for x in t]
+        out["incomplete_var_runs_ms"] = [round(x, 3) for x in tv]
+        out["incomplete_var_ms"] = round(float(np.median(tv)), 3)
+        out["var_minus_mean_ms"] = round(out["incomplete_var_ms"] - out["incomplete_ms"], 3)
+        out["var_check"] = _check_var(m, Xh, got, check_rows)
+    return out
 
 
 def _short(name):
@@ -104,16 +145,17 @@ def _short(name):
     return None
 
 
-def _kernel_times(name, share):
+def _kernel_times(name, share, variance=False):
     """this tool under rocprofv3 --kernel-trace: the kernels of one timed call and of the lc_model_predict after it"""
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "kt", "--", sys.executable,
-               str(Path(__file__).resolve()), "--child", name, str(share)]
+               str(Path(__file__).resolve()), "--child", name, str(share)] + (["--variance"] if variance else [])
         r = subprocess.run(cmd, capture_output=True, text=True)
         traces = sorted(Path(d).rglob("*kernel_trace.csv"))
         if r.returncode != 0 or not traces:
             return {"error": (r.stderr or r.stdout)[-400:]}
         rows = sorted(csv.DictReader(open(traces[-1])), key=lambda x: int(x["Start_Timestamp"]))
+    print(f"incomplete_bench: profiled {name} at {share} %{' with variance' if variance else ''}", file=sys.stderr, flush=True)
     names = [_short(x["Kernel_Name"]) for x in rows]
     scans = [i for i, n in enumerate(names) if n == "holes_scan_kernel"]
     if not scans:
@@ -129,12 +171,12 @@ def _kernel_times(name, share):
     return {"incomplete": call, "predict": after}
 
 
-def _child(name, share):
+def _child(name, share, variance=False):
     m, X, _ = _model(name)
     Xh, _, _ = _punch(X, share / 100.0, 7)
     with capi.Context(0) as ctx:
         ctx.set_data(Xh)
-        m.predict_incomplete_context(ctx)
+        m.predict_incomplete_context(ctx, variance=variance)
         ctx.set_data(X)
         m.predict_context(ctx)
         ctx.synchronize()
@@ -147,28 +189,35 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--no-kernels", action="store_true")
     ap.add_argument("--child", nargs=2, metavar=("CONFIG", "SHARE"))
+    ap.add_argument("--variance", action="store_true", help="also the call with variance, beside the mean-only call")
+    ap.add_argument("--check-rows", type=int, default=2048, help="--variance: rows with holes held against numpy")
     a = ap.parse_args()
     if a.child:
-        _child(a.child[0], float(a.child[1]))
+        _child(a.child[0], float(a.child[1]), a.variance)
         return
-    res, kernels = {}, {}
+    res, kernels, kernels_var = {}, {}, {}
     if not a.no_kernels:  # (first: the profiled runs are processes of their own, started before this one opens the device)
         for name in a.configs.split(","):
             kernels[name] = {s: _kernel_times(name, float(s)) for s in a.shares.split(",")}
+            if a.variance:
+                kernels_var[name] = {s: _kernel_times(name, float(s), True) for s in a.shares.split(",")}
     for name in a.configs.split(","):
         m, X, (N, D, K) = _model(name)
         out = {"N": N, "D": D, "K": K, "reps": a.reps, "shares": {}}
         for s in a.shares.split(","):
-            e = _wall(m, X, float(s) / 100.0, a.reps, 7)
+            e = _wall(m, X, float(s) / 100.0, a.reps, 7, a.variance, a.check_rows)
             if e["hole_rows"]:
                 e["us_per_hole_row_over_predict"] = round((e["incomplete_ms"] - e["predict_ms"]) * 1e3 / e["hole_rows"], 4)
             out["shares"][s] = e
+            print(f"incomplete_bench: timed {name} at {s} %", file=sys.stderr, flush=True)
             if name in kernels:
                 e["kernels_ms"] = kernels[name][s]
+            if name in kernels_var:
+                e["kernels_var_ms"] = kernels_var[name][s]
         m.close()
         del X
         res[name] = out
-    print(json.dumps({"tool": "incomplete_bench", "device": _device_name(), "results": res}))
+    print(json.dumps({"tool": "incomplete_bench", "variance": a.variance, "device": _device_name(), "results": res}))
 
 
 if __name__ == "__main__":
