@@ -17,6 +17,24 @@
  * both Eigen storage orders (column-major default, row-major when the
  * reference is built with -DEIGEN_DEFAULT_TO_ROW_MAJOR, CMakeLists.txt:59-61)
  * are accepted without a copy on the caller's side.
+ *
+ * Random numbers (lc_ctx_synth, lc_model_sample, lc_model_predict_conditional_draws): Philox-4x32-10.  The key
+ * is the 64-bit seed (k0 = low word, k1 = high word).  (c0, c1) are the low and high word of
+ *   g = (block << 40) + row_offset + row inside its block      (row_offset = 0 for conditional draws)
+ * c3 = tag | (sub << 8); o[0..3] are the output words, u01(a, b) = ((a << 32 | b) >> 11 + 0.5) / 2^53, and a Box-Muller
+ * pair is sqrt(-2 log u01(o[0], o[1])) (cos, sin)(2 pi u01(o[2], o[3])).
+ *   tag   c2            sub        stream
+ *   0x01  pair p        0          lc_ctx_synth: the normals of columns 2p, 2p + 1
+ *   0x02  0             0          lc_ctx_synth: the label
+ *   0x10  draw i        0          component choice: u = u01(o[0], o[1]); the first k, in the order 0 ... K-1 then the prior
+ *                                  component, whose running sum of weights exceeds u (the sum short: the last with weight)
+ *   0x11  draw i        pair p     the normals z[2p], z[2p + 1] of the draw (cos, sin)
+ *   0x12  draw or slot  attempt t  gamma draw (Marsaglia-Tsang): the normal of attempt t (the cos value)
+ *   0x13  draw or slot  attempt t  gamma draw: the uniform u01(o[0], o[1]) of attempt t
+ *   0x14  draw or slot  0          gamma draw of a shape < 1: the U of Gamma(shape + 1) U^(1 / shape)
+ *   0x15  pair p        0          ExpGamma: the Lomax uniforms of columns 2p (o[0], o[1]) and 2p + 1 (o[2], o[3])
+ * lc_model_sample draws one row per counter: i = 0, and the slot of a gamma draw is 0 (Gauss-Wishart: one per row) or the
+ * column (NormGamma: one per entry).  lc_model_predict_conditional_draws: i = the draw, one gamma draw per draw.
  */
 #ifndef LIBCLUSTER_HIP_H
 #define LIBCLUSTER_HIP_H
@@ -366,6 +384,43 @@ int lc_model_predict_conditional_var(lc_model* m, lc_ctx* ctx, const int* groups
  * lc_ctx_get_conditional.  LC_EINVAL: no conditional prediction on ctx, one without variance
  * (lc_model_predict_conditional), a row range out of bounds, row_stride < ntarget. */
 int lc_ctx_get_conditional_var(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* var, int64_t row_stride);
+/* ---- draws of the conditional (nothing in the reference corresponds).  Everything lc_model_predict_conditional
+ * does, mean and logp bit for bit, and per row ndraws draws of the target columns from p(x_b | x_a, training data): draw i
+ * chooses component k with the responsibilities r_k (the prior component takes part as in mean) and draws cluster k's
+ * conditional Student-t with eta = nu' + ngiven degrees of freedom,
+ *   x_b = M_k(x_a) + sqrt(c_k (1 + s d^2)) L_k z sqrt(eta / chi^2_eta),  c_k = (1 + beta) / (beta eta),  L_k = chol(S_k)
+ * with S_k, s and d^2 as in lc_model_predict_conditional_var.  m completed copies of a table, each from one draw per row, are
+ * a multiple imputation.  A draw depends on (seed, block, row, i) and the row's values only: not on the number of rows, on
+ * ndraws or on other rows; the same call gives the same bits.  Random numbers: the table at the top of this header.
+ * LC_EINVAL: the cases of lc_model_predict_conditional, ndraws outside [1, LC_DRAWS_MAX].  LC_EDOMAIN, before anything runs
+ * on the device: an S_k that is not numerically positive definite.  No moment has to exist. */
+#define LC_DRAWS_MAX 64
+int lc_model_predict_conditional_draws(lc_model* m, lc_ctx* ctx, const int* groups /* [J of ctx] or NULL */, const int* given,
+                                       int ngiven, const int* target /* or NULL */, int ntarget, int ndraws, uint64_t seed);
+/* rows [row0, row0+n) of block j of the draws of the last lc_model_predict_conditional_draws on ctx: draws is n x ndraws x
+ * ntarget, label n x ndraws (the component of every draw; K = the prior component); either may be NULL.  mean and logp of
+ * the same call: lc_ctx_get_conditional.  LC_EINVAL: no such prediction on ctx, a row range out of bounds. */
+int lc_ctx_get_conditional_draws(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* draws, int32_t* label);
+/* the shape of those draws: ndraws and ntarget of the last lc_model_predict_conditional_draws on ctx, both 0 when ctx holds
+ * no such prediction (never an error for that): what a caller sizes the buffers of lc_ctx_get_conditional_draws with.
+ * Either pointer may be NULL. */
+int lc_ctx_conditional_draws(lc_ctx* ctx, int* ndraws, int* ntarget);
+/* ---- new rows from a learned model (nothing in the reference corresponds).  Fills ctx with J blocks of Nj[b]
+ * rows at the model's width D: afterwards ctx is as after lc_ctx_set_data with those rows (lc_ctx_get_rows and every
+ * lc_model_predict* call work on it; the data, qZ and predictions it held are gone).  Every row is one draw from the density
+ * whose logarithm lc_model_predict returns as logp: the component is chosen with E[pi_jk] of learned group groups[b] (NULL:
+ * group 0), the prior component with E[pi_rest] (StickBreak); all K clusters take part, also for sparse models.  Then
+ *   Gauss-Wishart  x = m + sqrt((1 + beta) / (beta nu')) chol(iW) z sqrt(nu' / chi^2_nu'),  nu' = nu + 1 - D
+ *   NormGamma      per column a Student-t with 2 nu degrees of freedom, location m_d, scale^2 (1 + beta) L_d / (beta nu)
+ *   ExpGamma       per column a Lomax with shape a and scale 1 / ib_d, by inverse CDF (every value >= 0)
+ * No moment has to exist.  Rows [a, b) of a call with row_offset = 0 are the rows of a call for b - a rows with row_offset =
+ * a, bit for bit, and block b's rows do not depend on J.  LC_EINVAL: a freed model, no clusters, J < 1, a negative Nj, a
+ * group index outside [0, J of the model), Gauss-Wishart with D > 1024; ctx is untouched then. */
+int lc_model_sample(lc_model* m, lc_ctx* ctx, int J, const int64_t* Nj, const int* groups /* [J] or NULL: group 0 */,
+                    uint64_t seed, int64_t row_offset);
+/* the components of rows [row0, row0+n) of block j of a context filled by lc_model_sample (K = the prior component).
+ * LC_EINVAL: the context's rows do not come from lc_model_sample, a row range out of bounds. */
+int lc_ctx_get_sample_labels(lc_ctx* ctx, int j, int64_t row0, int64_t n, int32_t* label);
 /* ---- rows whose unknown columns differ from row to row (nothing in the reference corresponds).  Gauss-Wishart
  * models only.  ctx holds the rows at the model's FULL width D; a NaN marks an unknown value ("hole"), +-inf is data.  A row
  * may have up to LC_HOLES_MAX holes and needs at least one known column; every row has its own set.  Block b of ctx is mixed
@@ -538,6 +593,13 @@ int lc_gw_conditional(int D, double nu, double beta, const double* m, const doub
  * LC_EINVAL: the cases of lc_gw_conditional.  LC_EDOMAIN: nu + 1 - D + ngiven <= 2 (the covariance does not exist). */
 int lc_gw_conditional_var(int D, double nu, double beta, const double* iW, const int* given, int ngiven, const int* target,
                           int ntarget, double* S, double* g);
+/* The scale matrix of the conditional Student-t of lc_model_predict_conditional_draws from the same posterior and split
+ * (checked as in lc_gw_conditional): S [ntarget x ntarget] = iW_bb - iW_ba iW_aa^-1 iW_ab, formed as iW_bb - Y^T Y with
+ * Y = L_aa^-1 iW_ab on the Cholesky factor of iW_aa that lc_gw_conditional uses (no inverse), and L its lower Cholesky factor
+ * (row-major, the upper part zero).  Either may be NULL.  LC_EDOMAIN: S is not numerically positive definite (checked
+ * whichever output is asked for). */
+int lc_gw_conditional_cov(int D, double nu, double beta, const double* iW, const int* given, int ngiven, const int* target,
+                          int ntarget, double* S, double* L);
 /* The host table of lc_model_predict_incomplete from one Gauss-Wishart posterior (nu, beta, m [D], iW [D x D]); with
  * nu' = nu + 1 - D and, for nb = 0 ... LC_HOLES_MAX holes, Da = D - nb known columns:
  *   P [D x D] row-major = nu iW^-1 (symmetric; the square A^T A of the E-step whitener of lc_gw_mstep)

@@ -9,5 +9,6 @@ learnGMC with the reference Python binding's return shape) and `dist`
 a CPU implementation of the data path.
 """
 from . import capi  # noqa: F401
+from .capi import ConditionalDraws, Sample  # noqa: F401  (what Model.predict_conditional(draws=) and Model.sample return)
 from .api import (learnBEMM, learnBGMM, learnDGMC, learnDGMM, learnEGMC, learnGMC, learnMCM,  # noqa: F401
                   learnSCM, learnSGMC, learnVDP)

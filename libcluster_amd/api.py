@@ -11,7 +11,9 @@ Additive keyword-only extras: ``return_info=True`` appends a dict (rounds with e
 posteriors, E[log weights]), ``device`` picks the GPU, ``concentration`` / ``alpha`` set the weight prior the C++ API
 takes through its ``weights`` argument, ``qY0`` gives learnSCM / learnMCM a reproducible start, ``nthreads`` is an
 alias of ``threads``, ``return_model=True`` (the eight flat and grouped learners) appends the open ``capi.Model`` as
-the last element, whose ``predict(Xnew)`` scores new observations (labels, responsibilities, log density).
+the last element, whose ``predict(Xnew)`` scores new observations (labels, responsibilities, log density),
+``sample(n, seed)`` draws new rows from the learned density, and ``predict_conditional(..., draws=m, seed=s)`` /
+``impute(X, missing, draws=m)`` draw the unknown columns of rows (multiple imputation).
 learnDGMM / learnBEMM / learnDGMC / learnEGMC are not in the reference's Python module (they are in its C++ API,
 include/libcluster.h:262-315, 462-523) and follow the same conventions."""
 from __future__ import annotations

@@ -58,6 +58,30 @@ class ConditionalVar(NamedTuple):
     var: np.ndarray
 
 
+class ConditionalDraws(NamedTuple):
+    """Conditional with draws (lc_model_predict_conditional_draws): draws (N, m, ntarget) = m draws per row of the target
+    columns from p(x_target | x_given, training data), label (N, m) int32 = the component of every draw (K = the prior
+    component).  mean and logp are those of the call without draws, bit for bit."""
+    mean: np.ndarray
+    logp: np.ndarray
+    draws: np.ndarray
+    label: np.ndarray
+
+    @property
+    def var(self):
+        return None
+
+
+class Sample(NamedTuple):
+    """New rows from a model (Model.sample, lc_model_sample): rows (n, D), label (n,) int32 = the component every row was
+    drawn from (K = the prior component of StickBreak weights)."""
+    rows: np.ndarray
+    label: np.ndarray
+
+
+DRAWS_MAX = 64  # LC_DRAWS_MAX: the draws one row of a conditional prediction may have
+
+
 class Completion(NamedTuple):
     """Per-row outputs of Model.predict_incomplete (lc_model_predict_incomplete): rows (N, D) = the rows with every NaN
     replaced by E[x_unknown | x_known, training data], logp (N,) = log p(x_known | training data), count (N,) int32 = the
@@ -324,6 +348,14 @@ def lib() -> C.CDLL:
     L.lc_model_predict_incomplete_var.argtypes = [C.c_void_p, C.c_void_p, c_int_p]
     L.lc_ctx_get_completed_var.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, C.c_int64]
     L.lc_gw_precision_var.argtypes = [C.c_int, C.c_double, C.c_double, c_double_p]
+    L.lc_model_predict_conditional_draws.argtypes = [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, c_int_p, C.c_int,
+                                                     C.c_int, C.c_uint64]
+    L.lc_ctx_get_conditional_draws.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, c_int32_p]
+    L.lc_ctx_conditional_draws.argtypes = [C.c_void_p, c_int_p, c_int_p]
+    L.lc_model_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, c_int64_p, c_int_p, C.c_uint64, C.c_int64]
+    L.lc_ctx_get_sample_labels.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_int32_p]
+    L.lc_gw_conditional_cov.argtypes = [C.c_int, C.c_double, C.c_double, c_double_p, c_int_p, C.c_int, c_int_p, C.c_int,
+                                        c_double_p, c_double_p]
     _lib = L
     return L
 
@@ -667,18 +699,46 @@ class Context:
                                                dptr(logZ), dptr(lp)))
         return label, logZ, lp
 
-    def get_conditional(self, j, row0, n, ntarget, variance=False):
+    def get_conditional(self, j, row0, n, ntarget, variance=False, draws=False):
         """Rows [row0, row0+n) of block j of the last Model.predict_conditional_context on this context ->
         Conditional(mean (n, ntarget), logp (n,)); ntarget is the number of target columns of that call.  variance:
         ConditionalVar, with var (n, ntarget) (lc_ctx_get_conditional_var; ValueError when that call was made without
-        variance=True)."""
+        variance=True).  draws: True, or the number of draws per row of that call -> ConditionalDraws, with draws
+        (n, m, ntarget) and label (n, m) (lc_ctx_get_conditional_draws; ValueError when that call was made without
+        draws)."""
+        if variance and draws:
+            raise ValueError("a conditional prediction holds its variance or draws, not both")
         mean, logp = np.zeros((n, ntarget)), np.zeros(n)
         check(lib().lc_ctx_get_conditional(self._h, j, row0, n, dptr(mean), ntarget, dptr(logp)))
+        if draws:
+            m, nt = self.conditional_draws()  # (the library's own counts size the buffers)
+            if m < 1:
+                raise ValueError("the context holds no draws of a conditional prediction (lc_model_predict_conditional_draws)")
+            if draws is not True and int(draws) != m:
+                raise ValueError(f"the context's conditional prediction has {m} draws per row, not {int(draws)}")
+            if nt != ntarget:
+                raise ValueError(f"the context's conditional prediction has {nt} target columns, not {ntarget}")
+            dr, lab = np.zeros((n, m, ntarget)), np.zeros((n, m), dtype=np.int32)
+            check(lib().lc_ctx_get_conditional_draws(self._h, j, row0, n, dptr(dr), lab.ctypes.data_as(C.POINTER(C.c_int32))))
+            return ConditionalDraws(mean, logp, dr, lab)
         if not variance:
             return Conditional(mean, logp)
         var = np.zeros((n, ntarget))
         check(lib().lc_ctx_get_conditional_var(self._h, j, row0, n, dptr(var), ntarget))
         return ConditionalVar(mean, logp, var)
+
+    def conditional_draws(self):
+        """(ndraws, ntarget) of the draws the context holds (lc_ctx_conditional_draws); (0, 0): none."""
+        nd, nt = C.c_int(), C.c_int()
+        check(lib().lc_ctx_conditional_draws(self._h, C.byref(nd), C.byref(nt)))
+        return nd.value, nt.value
+
+    def get_sample_labels(self, j, row0, n):
+        """The components of rows [row0, row0+n) of block j of a context filled by Model.sample_context -> (n,) int32, K =
+        the prior component (lc_ctx_get_sample_labels; ValueError when the rows come from anywhere else)."""
+        lab = np.zeros(n, dtype=np.int32)
+        check(lib().lc_ctx_get_sample_labels(self._h, j, row0, n, lab.ctypes.data_as(C.POINTER(C.c_int32))))
+        return lab
 
     def get_completed(self, j, row0, n, variance=False):
         """Rows [row0, row0+n) of block j after the last Model.predict_incomplete_context on this context ->
@@ -871,12 +931,16 @@ class Model:
         gs = set(int(g) for g in given)
         return [c for c in range(self.dims()[2]) if c not in gs]
 
-    def predict_conditional_context(self, ctx, given, target=None, groups=None, variance=False):
+    def predict_conditional_context(self, ctx, given, target=None, groups=None, variance=False, draws=None, seed=0):
         """E[x_target | x_given] and log p(x_given) of the rows resident in ctx, whose column i is model column
         given[i] (lc_model_predict_conditional).  target None: every model column that is not given, ascending.
         variance: also the predictive variance of every target column (lc_model_predict_conditional_var; DomainError
         where it does not exist: a component with weight and nu + 1 - D + len(given) <= 2).
+        draws = m (1 ... DRAWS_MAX): also m draws per row of the target columns from p(x_target | x_given, training data)
+        (lc_model_predict_conditional_draws; a draw depends on seed, block, row, its index and the row's values only).
         Nothing is downloaded: read the rows with ctx.get_conditional.  Returns the number of target columns."""
+        if draws is not None and variance:
+            raise ValueError("draws and variance are separate calls: ask for one of them")
         g = None
         if groups is not None:
             garr = np.ascontiguousarray(groups, dtype=np.int32)
@@ -885,36 +949,63 @@ class Model:
             g = garr.ctypes.data_as(c_int_p)
         gv = np.ascontiguousarray(given, dtype=np.int32).reshape(-1)
         tv = None if target is None else np.ascontiguousarray(target, dtype=np.int32).reshape(-1)
-        call = lib().lc_model_predict_conditional_var if variance else lib().lc_model_predict_conditional
-        check(call(self._h, ctx._h, g, gv.ctypes.data_as(c_int_p), gv.size,
-                   None if tv is None else tv.ctypes.data_as(c_int_p), 0 if tv is None else tv.size))
+        args = (self._h, ctx._h, g, gv.ctypes.data_as(c_int_p), gv.size,
+                None if tv is None else tv.ctypes.data_as(c_int_p), 0 if tv is None else tv.size)
+        if draws is not None:
+            m = int(draws)
+            if m < 1 or m > DRAWS_MAX:
+                raise ValueError(f"draws must be in 1 ... {DRAWS_MAX}")
+            check(lib().lc_model_predict_conditional_draws(*args, m, int(seed)))
+        else:
+            call = lib().lc_model_predict_conditional_var if variance else lib().lc_model_predict_conditional
+            check(call(*args))
         return len(self._targets(gv, tv))
 
-    def predict_conditional(self, Xa, given, target=None, groups=None, device=0, variance=False):
+    def predict_conditional(self, Xa, given, target=None, groups=None, device=0, variance=False, draws=None, seed=0):
         """Conditional(mean, logp) for the host rows Xa ((N, len(given)) array: the known columns, in the order of
         given), or a list of them for a list of blocks (block b mixed with learned group groups[b], default 0).
-        variance: ConditionalVar(mean, logp, var) with the predictive variance of every target column."""
+        variance: ConditionalVar(mean, logp, var) with the predictive variance of every target column.
+        draws = m: ConditionalDraws(mean, logp, draws (N, m, ntarget), label (N, m)): m draws per row from
+        p(x_target | x_given, training data), the same bits for the same seed."""
+        if draws is not None and variance:
+            raise ValueError("draws and variance are separate calls: ask for one of them")
         blocks = isinstance(Xa, (list, tuple))
         Xs = list(Xa) if blocks else [Xa]
         Da = len(given)
         Xs = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, max(Da, 1))) for x in Xs]
         with Context(device) as ctx:
             ctx.set_data(Xs)
-            nt = self.predict_conditional_context(ctx, given, target, groups, variance)
-            out = [ctx.get_conditional(j, 0, x.shape[0], nt, variance) for j, x in enumerate(Xs)]
+            nt = self.predict_conditional_context(ctx, given, target, groups, variance, draws, seed)
+            out = [ctx.get_conditional(j, 0, x.shape[0], nt, variance, draws if draws is not None else False)
+                   for j, x in enumerate(Xs)]
         return out if blocks else out[0]
 
-    def impute(self, X, missing, groups=None, device=0, return_var=False):
+    def impute(self, X, missing, groups=None, device=0, return_var=False, draws=None, seed=0):
         """A copy of the full-width rows X ((N, D) array or a list of blocks) with the columns `missing` replaced by
         their conditional mean given the other columns (predict_conditional).  What X holds in the missing columns is
         not looked at (NaN is fine).  Rows whose missing columns differ from row to row: predict_incomplete.
         return_var: (filled, var) with var (N, len(missing)) the predictive variance of the values filled in, in the
-        order of `missing` (lists of each for a list of blocks)."""
+        order of `missing` (lists of each for a list of blocks).
+        draws = m: multiple imputation -- a list of m completed copies, copy i filled with draw i of every row from
+        p(x_missing | x_known, training data) (a list per block for a list of blocks)."""
+        if draws is not None and return_var:
+            raise ValueError("draws and return_var are separate calls: ask for one of them")
         blocks = isinstance(X, (list, tuple))
         D = self.dims()[2]
         Xs = [np.array(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (X if blocks else [X])]
         miss = [int(c) for c in missing]
         given = [c for c in range(D) if c not in set(miss)]
+        if draws is not None:
+            res = self.predict_conditional([x[:, given] for x in Xs], given, miss, groups, device, draws=draws, seed=seed)
+            out = []
+            for x, r in zip(Xs, res):
+                copies = []
+                for i in range(int(draws)):
+                    c = x.copy()
+                    c[:, miss] = r.draws[:, i, :]
+                    copies.append(c)
+                out.append(copies)
+            return out if blocks else out[0]
         res = self.predict_conditional([x[:, given] for x in Xs], given, miss, groups, device, variance=return_var)
         for x, r in zip(Xs, res):
             x[:, miss] = r.mean
@@ -922,6 +1013,39 @@ class Model:
             return Xs if blocks else Xs[0]
         var = [r.var for r in res]
         return (Xs, var) if blocks else (Xs[0], var[0])
+
+    # -- new rows --------------------------------------------------------------------------------------
+    def sample_context(self, ctx, counts, groups=None, seed=0, row_offset=0):
+        """Fill ctx with len(counts) blocks of counts[b] new rows, each a draw from the density predict() scores as logp:
+        block b with the weights of learned group groups[b] (None: 0) (lc_model_sample).  Whatever ctx held is replaced;
+        read the rows with ctx.get_rows, their components with ctx.get_sample_labels, or score them with any predict
+        call.  Rows [a, b) of a call with row_offset 0 are the rows of a call for b - a rows with row_offset = a."""
+        Nj = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+        g = None
+        if groups is not None:
+            garr = np.ascontiguousarray(groups, dtype=np.int32)
+            if garr.shape != (Nj.size,):
+                raise ValueError("groups needs one learned group index per block")
+            g = garr.ctypes.data_as(c_int_p)
+        check(lib().lc_model_sample(self._h, ctx._h, Nj.size, Nj.ctypes.data_as(c_int64_p), g, int(seed), int(row_offset)))
+
+    def sample(self, n, seed=0, groups=None, device=0):
+        """Sample(rows (n, D), label (n,)): n new rows from the model (group 0, or groups), and the component each came
+        from.  A list of counts gives a list of Samples, block b drawn with learned group groups[b]."""
+        blocks = isinstance(n, (list, tuple, np.ndarray))
+        counts = [int(c) for c in n] if blocks else [int(n)]
+        if groups is not None and not blocks:
+            groups = [int(np.asarray(groups).reshape(-1)[0])]
+        D = self.dims()[2]
+        with Context(device) as ctx:
+            self.sample_context(ctx, counts, groups, seed)
+            out = []
+            for j, c in enumerate(counts):
+                rows = np.zeros((c, D))
+                if c:
+                    check(lib().lc_ctx_get_rows(ctx._h, j, 0, c, dptr(rows)))
+                out.append(Sample(rows, ctx.get_sample_labels(j, 0, c)))
+        return out if blocks else out[0]
 
     # -- rows with holes (DESIGN 4.15) -------------------------------------------------------------------------------
     def predict_incomplete_context(self, ctx, groups=None, variance=False):
@@ -1074,6 +1198,22 @@ def gw_conditional_var(nu, beta, iW, given, target=None):
                                       None if tv is None else tv.ctypes.data_as(c_int_p), 0 if tv is None else tv.size,
                                       dptr(S), C.byref(g)))
     return S, g.value
+
+
+def gw_conditional_cov(nu, beta, iW, given, target=None):
+    """The scale matrix of the conditional Student-t behind the draws (lc_gw_conditional_cov) from one Gauss-Wishart
+    posterior -> (S, L): S = iW_bb - iW_ba iW_aa^-1 iW_ab (ntarget x ntarget, in the order of target; None: the columns
+    not given, ascending) and L its lower Cholesky factor.  DomainError when S is not numerically positive definite."""
+    iW = np.ascontiguousarray(iW, dtype=np.float64)
+    D = iW.shape[0]
+    gv = np.ascontiguousarray(given, dtype=np.int32).reshape(-1)
+    tv = None if target is None else np.ascontiguousarray(target, dtype=np.int32).reshape(-1)
+    Db = tv.size if tv is not None else len([c for c in range(D) if c not in set(int(g) for g in gv)])
+    S, L = np.zeros((Db, Db)), np.zeros((Db, Db))
+    check(lib().lc_gw_conditional_cov(D, nu, beta, dptr(iW), gv.ctypes.data_as(c_int_p), gv.size,
+                                      None if tv is None else tv.ctypes.data_as(c_int_p), 0 if tv is None else tv.size,
+                                      dptr(S), dptr(L)))
+    return S, L
 
 
 def gw_precision(nu, beta, m, iW):

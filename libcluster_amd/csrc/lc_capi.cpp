@@ -1174,6 +1174,52 @@ int lc_ctx_get_conditional_var(lc_ctx* ctx, int j, int64_t row0, int64_t n, doub
   });
 }
 
+// ---- draws of the conditional, new rows from a model ------------------------
+static_assert(LC_DRAWS_MAX == lck::DRAWS_MAX, "the header and the kernels agree on the draws a row may have");
+int lc_model_predict_conditional_draws(lc_model* m, lc_ctx* ctx, const int* groups, const int* given, int ngiven,
+                                       const int* target, int ntarget, int ndraws, uint64_t seed) {
+  return guarded([&] {
+    need(m, "model");
+    need(ctx, "ctx");
+    ctx->impl.predict_clear();  // (a failure leaves no prediction behind)
+    if (!model_alive(m)) throw std::invalid_argument("the model was freed");
+    if (ndraws < 1 || ndraws > LC_DRAWS_MAX) throw std::invalid_argument("ndraws must be in 1 ... 64");
+    lcp::predict_conditional(ctx->impl, m->model, groups, given, ngiven, target, ntarget, /*want_var=*/false, ndraws, seed);
+  });
+}
+
+int lc_ctx_get_conditional_draws(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* draws, int32_t* label) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.get_conditional_draws(j, row0, n, draws, label);
+  });
+}
+
+int lc_ctx_conditional_draws(lc_ctx* ctx, int* ndraws, int* ntarget) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    const int nd = ctx->impl.conditional_width() > 0 ? ctx->impl.conditional_draws() : 0;
+    if (ndraws) *ndraws = nd;
+    if (ntarget) *ntarget = nd > 0 ? ctx->impl.conditional_width() : 0;
+  });
+}
+
+int lc_model_sample(lc_model* m, lc_ctx* ctx, int J, const int64_t* Nj, const int* groups, uint64_t seed, int64_t row_offset) {
+  return guarded([&] {
+    need(m, "model");
+    need(ctx, "ctx");
+    if (!model_alive(m)) throw std::invalid_argument("the model was freed");
+    lcp::sample(ctx->impl, m->model, J, Nj, groups, seed, row_offset);
+  });
+}
+
+int lc_ctx_get_sample_labels(lc_ctx* ctx, int j, int64_t row0, int64_t n, int32_t* label) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.get_sample_labels(j, row0, n, label);
+  });
+}
+
 // ---- rows with holes -------------------------------------------------
 static_assert(LC_HOLES_MAX == lck::HOLES_MAX, "the header and the kernels agree on the holes a row may have");
 int lc_model_predict_incomplete(lc_model* m, lc_ctx* ctx, const int* groups) {
@@ -1332,6 +1378,16 @@ int lc_gw_conditional_var(int D, double nu, double beta, const double* iW, const
     if (D < 1) throw std::invalid_argument("D must be >= 1!");
     const std::vector<int> tg = lcp::conditional_split(D, given, ngiven, target, ntarget);
     lcp::gw_conditional_var(D, nu, beta, iW, std::vector<int>(given, given + ngiven), tg, S, g);
+  });
+}
+
+int lc_gw_conditional_cov(int D, double nu, double beta, const double* iW, const int* given, int ngiven, const int* target,
+                          int ntarget, double* S, double* L) {
+  return guarded([&] {
+    need(iW, "iW");
+    if (D < 1) throw std::invalid_argument("D must be >= 1!");
+    const std::vector<int> tg = lcp::conditional_split(D, given, ngiven, target, ntarget);
+    lcp::gw_conditional_cov(D, nu, beta, iW, std::vector<int>(given, given + ngiven), tg, S, L);
   });
 }
 

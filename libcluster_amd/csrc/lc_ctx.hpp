@@ -285,6 +285,7 @@ class Context {
     pred_cond_var_ = false;
     pred_holes_ = false;
     pred_holes_var_ = false;
+    pred_cond_draws_ = 0;
   }
   // Conditional prediction: after a raw E-step with zero constants over the context's (given) columns left
   // Kp columns in qZ, per row E[x_target | x_given] (Db columns) and log p(x_given) into the context's conditional outputs
@@ -301,6 +302,20 @@ class Context {
   void predict_cond_var(int Kp, int Db, const double* S, const double* g);
   // rows [row0, row0+n) of group j of that variance (var may be null); throws when the prediction held has none
   void get_conditional_var(int j, int64_t row0, int64_t n, double* var, int64_t row_stride) const;
+  // Draws of the conditional, right after predict_cond with the same Kp and Db, on the columns and logp it left:
+  // ndraws draws of the target columns per row and their components (lck::PredictCondDrawsLaunch; L Kp x Db x Db lower
+  // Cholesky factors of the Schur complements, row-major, cq Kp, host arrays).
+  void predict_cond_draws(int Kp, int Db, int ndraws, uint64_t seed, const double* L, const double* cq);
+  // rows [row0, row0+n) of group j of those draws: draws [n x ndraws x Db], label [n x ndraws] (either may be null)
+  void get_conditional_draws(int j, int64_t row0, int64_t n, double* draws, int32_t* label) const;
+  int conditional_draws() const { return pred_cond_draws_; }  // draws per row of the conditional prediction held (0: none)
+  // New rows from a model: J blocks of Nj rows at width D replace whatever the context held, as set_data
+  // does (lck::SampleLaunch for mode and tables: cdf J x Kp, klast J, loc Kp x D, fac Kp x D x D or Kp x D, shape Kp, host
+  // arrays).  The component of every row stays on the device (get_sample_labels).
+  void sample(int mode, int J, const int64_t* Nj, int D, int Kp, const double* cdf, const int* klast, const double* loc,
+              const double* fac, const double* shape, uint64_t seed, int64_t row_offset);
+  // components of rows [row0, row0+n) of group j; throws when the context's rows do not come from sample()
+  void get_sample_labels(int j, int64_t row0, int64_t n, int32_t* label) const;
   // Rows with holes (a NaN in X is an unknown value).  holes_scan: one read of X leaves the per-row hole
   // records on the device and returns the number of rows with holes, the largest count and the first row (in block, row
   // order) that has more than lck::HOLES_MAX holes or no known column (*bad_block = -1: none), with its count.
@@ -497,6 +512,14 @@ class Context {
   DevBuf<double> pcvar_, pvtab_;
   bool pred_cond_var_ = false;
   lck::PredictCondLaunch predict_cond_args(int Kp, int Db) const;  // over the tables predict_cond left in ptab_
+  // ... and, when pred_cond_draws_ > 0, that many draws per row [NP x pred_cond_draws_ x pred_cond_] with their components
+  // [NP x pred_cond_draws_] and the tables of that pass [cq Kp | Lt Kp x Dbp x Dbp]
+  DevBuf<double> pcdraws_, pdtab_;
+  DevBuf<int> pcdlabel_;
+  int pred_cond_draws_ = 0;
+  // the components of the rows when they come from sample() ([NP]; sampled_ is cleared by whatever replaces the rows)
+  DevBuf<int> slabel_;
+  bool sampled_ = false;
   // ... of the last prediction of rows with holes: count [NP], cols [NP x HOLES_MAX], log p(x_known) [NP], the scan's
   // three integers; pred_holes_: X holds the completed rows of such a prediction
   DevBuf<int> hcount_, hcols_;

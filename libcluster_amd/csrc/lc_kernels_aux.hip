@@ -1,6 +1,7 @@
 // Reductions, column sums, fills; the split-search data passes (partobs / splitobs / auglabels); the synthetic mixture generator
 // (one translation unit per kernel family; the file header of lc_kernels_estep.hip maps kernels to the reference)
 #include "lc_device.hpp"
+#include "lc_philox.hpp"
 
 namespace lck {
 
@@ -501,26 +502,7 @@ hipError_t launch_aug_from_sub(double* q, int64_t ldq, int k, int K, const int64
 // ===========================================================================
 // synthetic mixture (bench workload)
 // ===========================================================================
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                              uint32_t k1, uint32_t out[4]) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
-    const uint32_t hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += W0; k1 += W1;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-__device__ __forceinline__ double u01(uint32_t a, uint32_t b) {
-  // 53-bit uniform in (0,1)
-  const uint64_t v = (((uint64_t)a << 32) | b) >> 11;
-  return ((double)v + 0.5) * (1.0 / 9007199254740992.0);
-}
-
+// (philox4x32_10 and u01: lc_philox.hpp, shared with lc_kernels_sample.hip)
 // 16 rows (one row-group => one group of observations) per 256-thread block; eps staged in LDS.
 // Philox counter = (group id << 40) + row inside the group (+ row_offset), so any shard of any group can
 // be regenerated independently.  Labels: uniform, or by inverse CDF of the group's mixing proportions.
@@ -547,7 +529,7 @@ __global__ void __launch_bounds__(256) synth_kernel(SynthLaunch a) {
     const int r = t / npair, p = t % npair;
     const uint64_t g = gbase + (uint64_t)r;
     uint32_t o[4];
-    philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)p, 1u, k0, k1, o);
+    philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)p, RNG_TAG_SYNTH_NORMAL, k0, k1, o);
     const double u1 = u01(o[0], o[1]), u2 = u01(o[2], o[3]);
     const double rad = sqrt(-2.0 * log(u1));
     double sn, cs;
@@ -558,7 +540,7 @@ __global__ void __launch_bounds__(256) synth_kernel(SynthLaunch a) {
   if (threadIdx.x < 16) {
     const uint64_t g = gbase + (uint64_t)threadIdx.x;
     uint32_t o[4];
-    philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), 0u, 2u, k0, k1, o);
+    philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), 0u, RNG_TAG_SYNTH_LABEL, k0, k1, o);
     int z;
     if (a.cdf) {
       const double u = u01(o[0], o[1]);

@@ -246,6 +246,114 @@ void Context::get_conditional(int j, int64_t row0, int64_t n, double* mean, int6
   LC_HIP(hipStreamSynchronize(stream_));
 }
 
+void Context::predict_cond_draws(int Kp, int Db, int ndraws, uint64_t seed, const double* L, const double* cq) {
+  use_device();
+  pred_cond_draws_ = 0;
+  if (pred_cond_ != Db || Kp < 1) throw std::logic_error("predict_cond_draws: no conditional prediction of this width");
+  if (ndraws < 1 || ndraws > lck::DRAWS_MAX) throw std::invalid_argument("ndraws must be in 1 ... 64");
+  if (NP_ == 0) {
+    pred_cond_draws_ = ndraws;
+    return;
+  }
+  if (qz_[cur_].K != Kp) throw std::logic_error("predict_cond_draws: the columns of predict_cond are gone");
+  const int Dbp = (Db + 3) / 4 * 4;
+  pcdraws_.reserve((size_t)NP_ * ndraws * Db);
+  pcdlabel_.reserve((size_t)NP_ * ndraws);
+  // tables: [cq Kp | Lt Kp x Dbp x Dbp] (the factor transposed: a wave reads one column of L_k side by side), the pads zero
+  hpack_.assign((size_t)Kp + (size_t)Kp * Dbp * Dbp, 0.0);
+  std::copy(cq, cq + Kp, hpack_.data());
+  for (int k = 0; k < Kp; ++k) {
+    double* Lt = hpack_.data() + Kp + (size_t)k * Dbp * Dbp;
+    for (int t = 0; t < Db; ++t)
+      for (int c = 0; c <= t; ++c) Lt[(size_t)c * Dbp + t] = L[((size_t)k * Db + t) * Db + c];
+  }
+  pdtab_.reserve(hpack_.size());
+  LC_HIP(hipMemcpyAsync(pdtab_.p, hpack_.data(), hpack_.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+  lck::PredictCondDrawsLaunch v;
+  v.c = predict_cond_args(Kp, Db);
+  v.goff = J_ > 1 ? goff_d_.p : nullptr;
+  v.cq = pdtab_.p;
+  v.Lt = pdtab_.p + Kp;
+  v.ndraws = ndraws;
+  v.seed = seed;
+  v.draws = pcdraws_.p;
+  v.label = pcdlabel_.p;
+  LC_HIP(lck::launch_predict_cond_draws(v, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ is free again)
+  pred_cond_draws_ = ndraws;
+}
+
+void Context::get_conditional_draws(int j, int64_t row0, int64_t n, double* draws, int32_t* label) const {
+  use_device();
+  if (pred_cond_ < 1 || pred_cond_draws_ < 1)
+    throw std::invalid_argument("the context holds no draws of a conditional prediction (lc_model_predict_conditional_draws)");
+  if (j < 0 || j >= J_ || row0 < 0 || n < 0 || row0 + n > Nj_[j]) throw std::invalid_argument("row range out of bounds");
+  if (n == 0) return;
+  const size_t at = (size_t)(goff_[j] + row0) * pred_cond_draws_, cnt = (size_t)n * pred_cond_draws_;
+  static_assert(sizeof(int) == sizeof(int32_t), "the components are int32");
+  if (draws)
+    LC_HIP(hipMemcpyAsync(draws, pcdraws_.p + at * pred_cond_, cnt * pred_cond_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  if (label) LC_HIP(hipMemcpyAsync(label, pcdlabel_.p + at, cnt * sizeof(int), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+}
+
+void Context::sample(int mode, int J, const int64_t* Nj, int D, int Kp, const double* cdf, const int* klast, const double* loc,
+                     const double* fac, const double* shape, uint64_t seed, int64_t row_offset) {
+  use_device();
+  if (Kp < 1) throw std::invalid_argument("K must be >= 1");
+  build_layout(J, Nj, D);  // (whatever the context held is gone: data, qZ and predictions)
+  if (mode == 0) require_gw_width();
+  if (NP_ == 0) {
+    sampled_ = true;
+    return;
+  }
+  slabel_.reserve((size_t)NP_);
+  DevBuf<int> dlast;
+  dlast.reserve((size_t)J);
+  LC_HIP(hipMemcpyAsync(dlast.p, klast, (size_t)J * sizeof(int), hipMemcpyHostToDevice, stream_));
+  // tables: [cdf J x Kp | loc Kp x D | fac Kp x D (x D) | shape Kp]
+  const size_t nc = (size_t)J * Kp, nl = (size_t)Kp * D, nf = mode == 0 ? nl * D : nl;
+  hpack_.assign(nc + nl + nf + (size_t)Kp, 0.0);
+  double* h = hpack_.data();
+  std::copy(cdf, cdf + nc, h);
+  if (loc) std::copy(loc, loc + nl, h + nc);
+  std::copy(fac, fac + nf, h + nc + nl);
+  std::copy(shape, shape + Kp, h + nc + nl + nf);
+  ptab_.reserve(hpack_.size());
+  LC_HIP(hipMemcpyAsync(ptab_.p, hpack_.data(), hpack_.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+  lck::SampleLaunch a;
+  a.mode = mode;
+  a.DP = DP_;
+  a.D = D;
+  a.Kp = Kp;
+  a.X = X_.p;
+  a.label = slabel_.p;
+  a.nrows = Nj[0];
+  a.NP = NP_;
+  a.row_offset = row_offset;
+  a.seed = seed;
+  a.rginfo = J > 1 ? rginfo_.p : nullptr;
+  a.goff = J > 1 ? goff_d_.p : nullptr;
+  a.cdf = ptab_.p;
+  a.klast = dlast.p;
+  a.loc = ptab_.p + nc;
+  a.fac = ptab_.p + nc + nl;
+  a.shape = ptab_.p + nc + nl + nf;
+  LC_HIP(lck::launch_sample(a, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));  // (hpack_, ptab_ and the local table are free again)
+  sampled_ = true;
+}
+
+void Context::get_sample_labels(int j, int64_t row0, int64_t n, int32_t* label) const {
+  use_device();
+  if (!sampled_) throw std::invalid_argument("the context's rows do not come from lc_model_sample");
+  if (j < 0 || j >= J_ || row0 < 0 || n < 0 || row0 + n > Nj_[j]) throw std::invalid_argument("row range out of bounds");
+  if (n == 0 || !label) return;
+  static_assert(sizeof(int) == sizeof(int32_t), "the components are int32");
+  LC_HIP(hipMemcpyAsync(label, slabel_.p + (size_t)(goff_[j] + row0), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+}
+
 void Context::holes_scan(int64_t* holed_rows, int* max_count, int* bad_block, int64_t* bad_row, int* bad_count) {
   use_device();
   pred_holes_ = false;
@@ -668,7 +776,7 @@ namespace {
 // the existence of the variance is looked at only when one of them is asked for
 void conditional_tables(int D, double nu, double beta, const double* m, const double* iW, const std::vector<int>& given,
                         const std::vector<int>& target, double* A, double* ma, double* B, double* mb, double* G, double* s,
-                        double* e, double* S, double* gv) {
+                        double* e, double* S, double* gv, double* Scov = nullptr, double* Lcov = nullptr) {
   const int Da = (int)given.size(), Db = (int)target.size();
   const double nup = nu + 1 - D;  // Student-t degrees of freedom: of the FULL model's width (the marginal keeps them)
   if (!(nup > 0.0) || !(beta > 0.0)) throw std::invalid_argument("nu must exceed D - 1 and beta must be positive");
@@ -691,7 +799,9 @@ void conditional_tables(int D, double nu, double beta, const double* m, const do
     for (int i = 0; i < Da; ++i) ma[i] = m[given[(size_t)i]];
   if (mb)
     for (int t = 0; t < Db; ++t) mb[t] = m[target[(size_t)t]];
-  if (B || S) {  // row t of B solves iW_aa b = iW_a,t: L y = iW_a,t, then L^T b = y; the Schur complement's diagonal needs y only
+  const bool cov = Scov || Lcov;
+  std::vector<double> Y(cov ? (size_t)Db * Da : 0);  // Y^T: row t = L^-1 iW_a,t (the full Schur complement needs them all)
+  if (B || S || cov) {  // row t of B solves iW_aa b = iW_a,t: L y = iW_a,t, then L^T b = y; the Schur complement's diagonal needs y only
     std::vector<double> y((size_t)Da);
     for (int t = 0; t < Db; ++t) {
       const int ct = target[(size_t)t];
@@ -705,6 +815,7 @@ void conditional_tables(int D, double nu, double beta, const double* m, const do
         for (int i = 0; i < Da; ++i) v -= y[(size_t)i] * y[(size_t)i];
         S[t] = v;
       }
+      if (cov) std::copy(y.begin(), y.end(), Y.begin() + (size_t)t * Da);
       if (!B) continue;
       double* b = B + (size_t)t * Da;
       for (int i = Da - 1; i >= 0; --i) {
@@ -720,8 +831,29 @@ void conditional_tables(int D, double nu, double beta, const double* m, const do
   if (s) *s = beta / ((1 + beta) * nu);
   if (e) *e = (nup + Da) / 2;
   if (gv) *gv = (1 + beta) / (beta * (nup + Da - 2.0));
+  if (cov) {  // S = iW_bb - Y^T Y, entry by entry as its diagonal above; then its own Cholesky factor
+    std::vector<double> Sf((size_t)Db * Db);
+    for (int t = 0; t < Db; ++t)
+      for (int u = 0; u <= t; ++u) {
+        double v = iW[(size_t)target[(size_t)t] * D + target[(size_t)u]];
+        for (int i = 0; i < Da; ++i) v -= Y[(size_t)t * Da + i] * Y[(size_t)u * Da + i];
+        Sf[(size_t)t * Db + u] = Sf[(size_t)u * Db + t] = v;
+      }
+    if (Scov) std::copy(Sf.begin(), Sf.end(), Scov);
+    // (factored whichever output is wanted: an S that is not positive definite is an error, not a result)
+    if (!lch::cholesky(Sf, Db))
+      throw std::domain_error("the Schur complement iW_bb - iW_ba iW_aa^-1 iW_ab is not numerically positive definite");
+    if (Lcov) std::copy(Sf.begin(), Sf.end(), Lcov);
+  }
 }
 }  // namespace
+
+void gw_conditional_cov(int D, double nu, double beta, const double* iW, const std::vector<int>& given,
+                        const std::vector<int>& target, double* S, double* L) {
+  std::vector<double> tmp(S || L ? 0 : (size_t)target.size() * target.size());  // (neither wanted: the checks still run)
+  conditional_tables(D, nu, beta, nullptr, iW, given, target, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                     nullptr, nullptr, S || L ? S : tmp.data(), L);
+}
 
 void gw_conditional(int D, double nu, double beta, const double* m, const double* iW, const std::vector<int>& given,
                     const std::vector<int>& target, double* A, double* ma, double* B, double* mb, double* G, double* s,
@@ -737,7 +869,7 @@ void gw_conditional_var(int D, double nu, double beta, const double* iW, const s
 }
 
 void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* groups, const int* given, int ngiven,
-                         const int* target, int ntarget, bool want_var) {
+                         const int* target, int ntarget, bool want_var, int ndraws, uint64_t seed) {
   ctx.predict_clear();  // (whatever an earlier prediction left must not outlive a failure of this one)
   const int K = (int)model.clusters.size(), J = (int)model.weights.size(), Jc = ctx.J();
   if (K < 1) throw std::invalid_argument("the model has no clusters");
@@ -748,6 +880,7 @@ void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* 
   const std::vector<int> gv(given, given + (ngiven > 0 && given ? ngiven : 0));
   const std::vector<int> tg = conditional_split(D, given, ngiven, target, ntarget);
   const int Da = ngiven, Db = (int)tg.size();
+  if (ndraws < 0 || ndraws > lck::DRAWS_MAX) throw std::invalid_argument("ndraws must be in 1 ... 64");
   if (ctx.D() != Da)
     throw std::invalid_argument("the context has " + std::to_string(ctx.D()) + " columns, given names " + std::to_string(Da));
   for (int b = 0; b < Jc; ++b) {
@@ -765,6 +898,7 @@ void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* 
   const lch::ClusterAny prior(model.ckind, model.clusters[0].prior(), D);  // clearobs state: a cluster that saw no data
   std::vector<double> A((size_t)Kp * Da * Da), ma((size_t)Kp * Da), B((size_t)Kp * Db * Da), mb((size_t)Kp * Db),
       G((size_t)Kp), ps((size_t)Kp), pe((size_t)Kp), S(want_var ? (size_t)Kp * Db : 0, 0.0), gvar(want_var ? (size_t)Kp : 0, 0.0);
+  std::vector<double> Lcov(ndraws > 0 ? (size_t)Kp * Db * Db : 0), cq(ndraws > 0 ? (size_t)Kp : 0);
   for (int k = 0; k < Kp; ++k) {
     const lch::GaussWishState& g = k < K ? model.clusters[(size_t)k].gw : prior.gw;
     bool var_k = want_var;
@@ -786,7 +920,8 @@ void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* 
     conditional_tables(D, g.nu, g.beta, g.m.data(), g.iW.data(), gv, tg, A.data() + (size_t)k * Da * Da,
                        ma.data() + (size_t)k * Da, B.data() + (size_t)k * Db * Da, mb.data() + (size_t)k * Db, &G[(size_t)k],
                        &ps[(size_t)k], &pe[(size_t)k], var_k ? S.data() + (size_t)k * Db : nullptr,
-                       var_k ? &gvar[(size_t)k] : nullptr);
+                       var_k ? &gvar[(size_t)k] : nullptr, nullptr, ndraws > 0 ? Lcov.data() + (size_t)k * Db * Db : nullptr);
+    if (ndraws > 0) cq[(size_t)k] = (1 + g.beta) / (2 * g.beta);  // c_k eta / 2: the draw divides by G = chi^2_eta / 2
   }
   std::vector<double> tt((size_t)Jc * Kp), zero((size_t)Jc * Kp, 0.0);
   for (int b = 0; b < Jc; ++b) {
@@ -798,6 +933,81 @@ void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* 
   ctx.estep(Kp, A.data(), ma.data(), zero.data(), nullptr, nullptr, /*raw=*/true);
   ctx.predict_cond(Kp, Db, tt.data(), ps.data(), pe.data(), ma.data(), B.data(), mb.data());
   if (want_var) ctx.predict_cond_var(Kp, Db, S.data(), gvar.data());
+  if (ndraws > 0) ctx.predict_cond_draws(Kp, Db, ndraws, seed, Lcov.data(), cq.data());
+}
+
+void sample(lcc::Context& ctx, const lce::Model& model, int Jc, const int64_t* Nj, const int* groups, uint64_t seed,
+            int64_t row_offset) {
+  const int K = (int)model.clusters.size(), J = (int)model.weights.size();
+  if (K < 1) throw std::invalid_argument("the model has no clusters");
+  if (Jc < 1 || !Nj) throw std::invalid_argument("need at least one block of rows");
+  for (int b = 0; b < Jc; ++b) {
+    if (Nj[b] < 0) throw std::invalid_argument("negative block size");
+    const int j = groups ? groups[b] : 0;
+    if (j < 0 || j >= J) throw std::invalid_argument("group index out of range");
+  }
+  const int ck = model.ckind, D = model.clusters[0].D();
+  if (ck == lch::C_GAUSSWISH && lck::padded_dim_wide(D) > lck::GW_MAX_DP)
+    throw std::invalid_argument("D > 1024 is not supported by the Gauss-Wishart kernels (the diagonal and exponential "
+                                "families take any D)");
+  std::vector<double> Epi((size_t)J * K), Erest((size_t)J);
+  bool rest = false;
+  for (int j = 0; j < J; ++j) {
+    if ((int)model.weights[(size_t)j].alpha1.size() != K) throw std::invalid_argument("weights and clusters disagree");
+    weights_predictive(model.weights[(size_t)j], Epi.data() + (size_t)j * K, &Erest[(size_t)j]);
+    rest = rest || Erest[(size_t)j] > 0.0;
+  }
+  const int Kp = K + (rest ? 1 : 0);
+  // per block: the running sums of the weights in the order 0 ... K - 1, then the prior component
+  std::vector<double> cdf((size_t)Jc * Kp);
+  std::vector<int> klast((size_t)Jc, 0);
+  for (int b = 0; b < Jc; ++b) {
+    const int j = groups ? groups[b] : 0;
+    double run = 0.0;
+    for (int k = 0; k < Kp; ++k) {
+      const double w = k < K ? Epi[(size_t)j * K + k] : Erest[(size_t)j];
+      run += w;
+      cdf[(size_t)b * Kp + k] = run;
+      if (w > 0.0) klast[(size_t)b] = k;
+    }
+  }
+  const lch::ClusterAny prior(ck, model.clusters[0].prior(), D);  // clearobs state: a cluster that saw no data
+  std::vector<double> loc((size_t)Kp * D, 0.0), shape((size_t)Kp);
+  std::vector<double> fac(ck == lch::C_GAUSSWISH ? (size_t)Kp * D * D : (size_t)Kp * D);
+  for (int k = 0; k < Kp; ++k) {
+    const lch::ClusterAny& c = k < K ? model.clusters[(size_t)k] : prior;
+    if (ck == lch::C_GAUSSWISH) {
+      // the Student-t of gw_predictive: nu' degrees of freedom, scale matrix (1 + beta) / (beta nu') iW; with
+      // chi^2_nu' = 2 G the row is m + sqrt((1 + beta) / (2 beta)) chol(iW) z / sqrt(G), G ~ Gamma(nu' / 2)
+      const lch::GaussWishState& g = c.gw;
+      const double nup = g.nu + 1 - D;
+      if (!(nup > 0.0) || !(g.beta > 0.0)) throw std::invalid_argument("nu must exceed D - 1 and beta must be positive");
+      std::vector<double> L(g.iW);
+      if (!lch::cholesky(L, D)) throw std::invalid_argument("Matrix A is not positive definite");
+      const double sc = std::sqrt((1 + g.beta) / (2 * g.beta));
+      for (size_t i = 0; i < L.size(); ++i) fac[(size_t)k * D * D + i] = sc * L[i];
+      std::copy(g.m.begin(), g.m.end(), loc.begin() + (size_t)k * D);
+      shape[(size_t)k] = nup / 2;
+      continue;
+    }
+    // separable families, from the density predict() scores: prod_d (1 + term_d)^-e
+    const Predictive p = predictive(c);
+    for (int d = 0; d < D; ++d) {
+      const size_t i = (size_t)k * D + d;
+      if (ck == lch::C_NORMGAMMA) {
+        // (1 + w (x - a)^2)^-e is a Student-t with n = 2 e - 1 degrees of freedom and scale^2 = 1 / (n w):
+        // x = a + z / sqrt(2 w G), G ~ Gamma(n / 2)
+        loc[i] = p.a[(size_t)d];
+        fac[i] = 1.0 / std::sqrt(2 * p.w[(size_t)d]);
+      } else {
+        // (1 + w x)^-e is a Lomax with shape e - 1 and scale 1 / w: x = ((1 - u)^(-1 / (e - 1)) - 1) / w
+        fac[i] = 1.0 / p.w[(size_t)d];
+      }
+    }
+    shape[(size_t)k] = ck == lch::C_NORMGAMMA ? p.e - 0.5 : p.e - 1.0;
+  }
+  ctx.sample(ck == lch::C_GAUSSWISH ? 0 : ck == lch::C_NORMGAMMA ? 1 : 2, Jc, Nj, D, Kp, cdf.data(), klast.data(), loc.data(),
+             fac.data(), shape.data(), seed, row_offset);
 }
 
 void gw_precision(int D, double nu, double beta, const double* iW, double* P, double* G, double* s, double* e) {

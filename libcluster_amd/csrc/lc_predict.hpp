@@ -191,6 +191,53 @@ struct PredictHolesVarLaunch {
 };
 hipError_t launch_predict_holes_var(const PredictHolesVarLaunch& a, hipStream_t stream);
 
+// ---- draws (lc_kernels_sample.hip; random numbers: lc_philox.hpp) ------------------------------------------------
+constexpr int DRAWS_MAX = 64;  // draws per row of a conditional prediction (LC_DRAWS_MAX of the C header): one lane each
+// sample_gw_kernel / sample_diag_kernel: new rows from a learned model, synth_kernel's shape (16 rows per 256-thread block,
+// one block of the context per row group).  Row g = (block id << 40) + row_offset + row inside its block chooses component
+// z by inverse CDF (first k with cdf[k] > u, else klast) and becomes
+//   mode 0 (Gauss-Wishart): loc_z + fac_z eps / sqrt(G),  G ~ Gamma(shape_z) per row, fac_z lower triangular (normals in LDS)
+//   mode 1 (NormGamma):     loc_zd + fac_zd eps_d / sqrt(G_d),  G_d ~ Gamma(shape_z) per entry
+//   mode 2 (ExpGamma):      fac_zd expm1(-log(u_d) / shape_z)   (Lomax by inverse CDF)
+// Pad rows and pad columns are written as zeros, the label of a pad row as -1.
+struct SampleLaunch {
+  int mode = 0;
+  int DP = 0, D = 0, Kp = 0;
+  double* X = nullptr;   // [NP x DP]
+  int* label = nullptr;  // [NP]
+  int64_t nrows = 0;     // valid rows (single block)
+  int64_t NP = 0;
+  int64_t row_offset = 0;
+  uint64_t seed = 0;
+  const int* rginfo = nullptr;     // [NP / 16] or nullptr (single block)
+  const int64_t* goff = nullptr;   // [J + 1] padded block offsets, or nullptr
+  const double* cdf = nullptr;     // [J x Kp] running sums of the weights of the block's learned group
+  const int* klast = nullptr;      // [J] last component with positive weight
+  const double* loc = nullptr;     // [Kp x D]
+  const double* fac = nullptr;     // [Kp x D x D] (mode 0) or [Kp x D]
+  const double* shape = nullptr;   // [Kp]
+};
+hipError_t launch_sample(const SampleLaunch& a, hipStream_t stream);
+
+// cond_draws_kernel: after predict_cond_kernel, on the same launch arguments and what it left (t_k in the Kp columns,
+// logp).  Per valid row and draw i < ndraws: component k by inverse CDF over r_k = exp(t_k - logp), then
+//   x_b = M_k(x_a) + sqrt(cq_k (1 + s_k d_k^2) / G) L_k z,  G ~ Gamma(e_k),  M_k = [x_a - m_a,k, 1] T_k
+// (cq_k = (1 + beta) / (2 beta): the Student-t with 2 e_k = nu' + Da degrees of freedom).  A wave owns its 64 rows: lane =
+// row in the choice and the gamma draw (four draws of every row at a time), then the rows one after the other with lane t =
+// target column t in the products; M_k is formed once for consecutive draws of a row that chose the same component.  No
+// atomics, no LDS, no barrier: the same bits on every call.
+struct PredictCondDrawsLaunch {
+  PredictCondLaunch c;              // as launched before (col and logp are read here)
+  const int64_t* goff = nullptr;    // [J + 1] padded block offsets, or nullptr (single block)
+  const double* Lt = nullptr;       // [Kp x Dbp x Dbp] Lt[k][j][t] = chol(S_k)[t][j] (j <= t), zero elsewhere
+  const double* cq = nullptr;       // [Kp]
+  int ndraws = 0;
+  uint64_t seed = 0;
+  double* draws = nullptr;  // [NP x ndraws x Db]
+  int* label = nullptr;     // [NP x ndraws]
+};
+hipError_t launch_predict_cond_draws(const PredictCondDrawsLaunch& a, hipStream_t stream);
+
 }  // namespace lck
 
 namespace lch {
@@ -231,8 +278,23 @@ void gw_conditional_var(int D, double nu, double beta, const double* iW, const s
 // models only; all K clusters take part (and the prior component of StickBreak weights), as in predict()'s logp.
 // want_var: also the diagonal of the mixture's predictive covariance of the target columns (Context::get_conditional_var).
 // Throws std::domain_error, before anything is launched, when a component with weight has nu' + Da <= 2.
+// ndraws > 0: also that many draws of the target columns per row, each from the mixture of the clusters'
+// conditional Student-t densities (Context::get_conditional_draws); mean and logp are the bits of the call without.  Throws
+// std::domain_error, before anything is launched, when a cluster's Schur complement is not numerically positive definite.
 void predict_conditional(lcc::Context& ctx, const lce::Model& model, const int* groups, const int* given, int ngiven,
-                         const int* target, int ntarget, bool want_var = false);
+                         const int* target, int ntarget, bool want_var = false, int ndraws = 0, uint64_t seed = 0);
+// The full conditional scale matrix of that Student-t from the same posterior and split, on the Cholesky factor of iW_aa
+// that gw_conditional uses: with Y = L_aa^-1 iW_ab, S [Db x Db] = iW_bb - Y^T Y (no inverse) and L [Db x Db] its lower
+// Cholesky factor (the upper part zero).  Either output may be null.  Throws std::domain_error when S is not numerically
+// positive definite (whichever output is wanted), and std::invalid_argument as gw_conditional does.
+void gw_conditional_cov(int D, double nu, double beta, const double* iW, const std::vector<int>& given,
+                        const std::vector<int>& target, double* S, double* L);
+// New rows from the model's posterior predictive: J blocks of Nj rows at the model's width into ctx, block b
+// with the weights of learned group groups[b] (null: 0); every row is a draw from the density whose logarithm predict()
+// returns as logp (all K clusters and, with StickBreak weights, the prior component).  The component of every row stays on
+// the device (Context::get_sample_labels; K = the prior component).  Throws std::invalid_argument, with ctx untouched.
+void sample(lcc::Context& ctx, const lce::Model& model, int J, const int64_t* Nj, const int* groups, uint64_t seed,
+            int64_t row_offset);
 // The host table of one Gauss-Wishart posterior for rows with holes, NH = lck::HOLES_MAX + 1:
 //   P [D x D] = nu iW^-1 = A^T A with the whitener A (symmetric)
 //   G [NH]: G[nb] = lgam(e[nb]) - lgam(nu'/2) - (Da/2) log(nu' pi) + (Da log(nu' beta / (1 + beta)) - log|iW| + nb log nu) / 2
