@@ -18,9 +18,10 @@
  * reference is built with -DEIGEN_DEFAULT_TO_ROW_MAJOR, CMakeLists.txt:59-61)
  * are accepted without a copy on the caller's side.
  *
- * Random numbers (lc_ctx_synth, lc_model_sample, lc_model_predict_conditional_draws): Philox-4x32-10.  The key
+ * Random numbers (lc_ctx_synth, lc_model_sample, lc_model_predict_conditional_draws, lc_model_predict_incomplete_draws;
+ * DESIGN 4.16, 4.16.1): Philox-4x32-10.  The key
  * is the 64-bit seed (k0 = low word, k1 = high word).  (c0, c1) are the low and high word of
- *   g = (block << 40) + row_offset + row inside its block      (row_offset = 0 for conditional draws)
+ *   g = (block << 40) + row_offset + row inside its block      (row_offset = 0 for conditional and incomplete draws)
  * c3 = tag | (sub << 8); o[0..3] are the output words, u01(a, b) = ((a << 32 | b) >> 11 + 0.5) / 2^53, and a Box-Muller
  * pair is sqrt(-2 log u01(o[0], o[1])) (cos, sin)(2 pi u01(o[2], o[3])).
  *   tag   c2            sub        stream
@@ -35,6 +36,9 @@
  *   0x15  pair p        0          ExpGamma: the Lomax uniforms of columns 2p (o[0], o[1]) and 2p + 1 (o[2], o[3])
  * lc_model_sample draws one row per counter: i = 0, and the slot of a gamma draw is 0 (Gauss-Wishart: one per row) or the
  * column (NormGamma: one per entry).  lc_model_predict_conditional_draws: i = the draw, one gamma draw per draw.
+ * lc_model_predict_incomplete_draws uses the same streams: i = the draw, one gamma draw per draw, and pair p holds the
+ * normals of the holes in slots 2p, 2p + 1 of the row's cols (only the first ceil(count / 2) pairs are generated).  For equal
+ * seeds the choice uniform of (block, row, draw) is the one lc_model_predict_conditional_draws uses.
  */
 #ifndef LIBCLUSTER_HIP_H
 #define LIBCLUSTER_HIP_H
@@ -468,6 +472,30 @@ int lc_model_predict_incomplete_var(lc_model* m, lc_ctx* ctx, const int* groups 
  * no incomplete prediction on ctx, one without variance (lc_model_predict_incomplete), a row range out of bounds,
  * row_stride < LC_HOLES_MAX. */
 int lc_ctx_get_completed_var(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* var, int64_t row_stride);
+/* ---- draws of the unknown values of rows with holes (nothing in the reference corresponds).  Everything
+ * lc_model_predict_incomplete does (the context's rows hold the MEAN-completed rows afterwards), and per row ndraws draws of
+ * its holes from the mixture of the clusters' conditional Student-t densities: multiple imputation for rows that each miss
+ * their own columns.  With the notation above, L L^T = H = (P_k)_bb and e_k(nb) = (nu' + Da) / 2, draw i of a row
+ *   chooses k by inverse CDF over r_k = exp(t_k - logp) (0 ... K-1, then the prior component),
+ *   draws G ~ Gamma(e_k(nb)) and the normals z of its holes, and is
+ *   x_b = M_k + sqrt((1 + beta_k) nu_k / (2 beta_k) (1 + s_k d_a^2) / G) v,   L^T v = z
+ * (sqrt(nu) L^-T is a factor of S_k = nu H^-1: the Student-t of 2 e_k(nb) degrees of freedom, location M_k and scale matrix
+ * (1 + beta) / (beta (nu' + Da)) (1 + s d_a^2) S_k).  No moment has to exist: the prior component draws too, and there is no
+ * LC_EDOMAIN case.  The random numbers are in the table at the top of this file: a draw is a function of (seed, block, row,
+ * draw, the row's values) and of nothing else -- not of ndraws, the number of rows or the row's neighbours.  Completed rows,
+ * logp, count and cols are those of lc_model_predict_incomplete, bit for bit.
+ * LC_EINVAL: the cases of lc_model_predict_incomplete (raised before anything is written, the NaNs stay), ndraws outside
+ * [1, LC_DRAWS_MAX].  A context without any hole is valid. */
+int lc_model_predict_incomplete_draws(lc_model* m, lc_ctx* ctx, const int* groups /* [J of ctx] or NULL */, int ndraws,
+                                      uint64_t seed);
+/* rows [row0, row0+n) of block j of the draws of the last lc_model_predict_incomplete_draws on ctx: draws is n x ndraws x
+ * LC_HOLES_MAX, contiguous; slot i belongs to cols[i] of lc_ctx_get_completed, the slots i >= count are exactly 0.0, and so is
+ * every slot of a row without holes.  label is n x ndraws: the component of every draw (K = the prior component), -1 for
+ * every draw of a row without holes (nothing is drawn for it).  Either output may be NULL.  LC_EINVAL: no such prediction on
+ * ctx (none, or one without draws), a row range out of bounds. */
+int lc_ctx_get_completed_draws(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* draws, int32_t* label);
+/* ndraws of the last lc_model_predict_incomplete_draws on ctx, 0 when ctx holds no such prediction (never an error for that) */
+int lc_ctx_completed_draws(lc_ctx* ctx, int* ndraws);
 /* ---- ranking on the device (nothing in the reference corresponds): the m best rows of each of C device-resident
  * columns, 1 <= m <= 64, without bringing the columns to the host.  Entry a is better than entry b when its score is larger
  * (largest != 0; smaller otherwise), or the scores compare equal (+0.0 and -0.0 do) and a comes first in the context (lower

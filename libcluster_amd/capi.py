@@ -106,6 +106,23 @@ class CompletionVar(NamedTuple):
     var: np.ndarray
 
 
+class CompletionDraws(NamedTuple):
+    """Completion with draws of the filled values (lc_model_predict_incomplete_draws): draws (N, m, HOLES_MAX) = m draws per
+    row of its unknown values from p(x_unknown | x_known, training data), slot i belongs to cols[:, i], 0 beyond count and
+    in rows without holes; label (N, m) int32 = the component of every draw (K = the prior component), -1 in rows without
+    holes.  rows holds the MEAN-completed rows; rows, logp, count and cols are those of the call without draws, bit for bit."""
+    rows: np.ndarray
+    logp: np.ndarray
+    count: np.ndarray
+    cols: np.ndarray
+    draws: np.ndarray
+    label: np.ndarray
+
+    @property
+    def var(self):
+        return None
+
+
 HOLES_MAX = 8  # LC_HOLES_MAX: the NaNs one row may hold
 
 
@@ -348,6 +365,9 @@ def lib() -> C.CDLL:
     L.lc_model_predict_incomplete_var.argtypes = [C.c_void_p, C.c_void_p, c_int_p]
     L.lc_ctx_get_completed_var.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, C.c_int64]
     L.lc_gw_precision_var.argtypes = [C.c_int, C.c_double, C.c_double, c_double_p]
+    L.lc_model_predict_incomplete_draws.argtypes = [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_uint64]
+    L.lc_ctx_get_completed_draws.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, c_int32_p]
+    L.lc_ctx_completed_draws.argtypes = [C.c_void_p, c_int_p]
     L.lc_model_predict_conditional_draws.argtypes = [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, c_int_p, C.c_int,
                                                      C.c_int, C.c_uint64]
     L.lc_ctx_get_conditional_draws.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, c_int32_p]
@@ -740,16 +760,35 @@ class Context:
         check(lib().lc_ctx_get_sample_labels(self._h, j, row0, n, lab.ctypes.data_as(C.POINTER(C.c_int32))))
         return lab
 
-    def get_completed(self, j, row0, n, variance=False):
+    def completed_draws(self):
+        """The draws per row of the completed rows the context holds (lc_ctx_completed_draws); 0: none."""
+        nd = C.c_int()
+        check(lib().lc_ctx_completed_draws(self._h, C.byref(nd)))
+        return nd.value
+
+    def get_completed(self, j, row0, n, variance=False, draws=False):
         """Rows [row0, row0+n) of block j after the last Model.predict_incomplete_context on this context ->
         Completion(rows (n, D), logp (n,), count (n,), cols (n, HOLES_MAX)).  variance: CompletionVar, with var
-        (n, HOLES_MAX) (lc_ctx_get_completed_var; ValueError when that call was made without variance=True)."""
+        (n, HOLES_MAX) (lc_ctx_get_completed_var; ValueError when that call was made without variance=True).  draws: True,
+        or the number of draws per row of that call -> CompletionDraws, with draws (n, m, HOLES_MAX) and label (n, m)
+        (lc_ctx_get_completed_draws; ValueError when that call was made without draws)."""
+        if variance and draws:
+            raise ValueError("a completion holds its variance or draws, not both")
         D = self.dims()[1]
         rows, logp = np.zeros((n, D)), np.zeros(n)
         count, cols = np.zeros(n, dtype=np.int32), np.full((n, HOLES_MAX), -1, dtype=np.int32)
         c_int32_p = C.POINTER(C.c_int32)
         check(lib().lc_ctx_get_completed(self._h, j, row0, n, dptr(rows), D, dptr(logp), count.ctypes.data_as(c_int32_p),
                                          cols.ctypes.data_as(c_int32_p)))
+        if draws:
+            m = self.completed_draws()  # (the library's own count sizes the buffers)
+            if m < 1:
+                raise ValueError("the context holds no draws of completed rows (lc_model_predict_incomplete_draws)")
+            if draws is not True and int(draws) != m:
+                raise ValueError(f"the context's completed rows have {m} draws per row, not {int(draws)}")
+            dr, lab = np.zeros((n, m, HOLES_MAX)), np.zeros((n, m), dtype=np.int32)
+            check(lib().lc_ctx_get_completed_draws(self._h, j, row0, n, dptr(dr), lab.ctypes.data_as(c_int32_p)))
+            return CompletionDraws(rows, logp, count, cols, dr, lab)
         if not variance:
             return Completion(rows, logp, count, cols)
         var = np.zeros((n, HOLES_MAX))
@@ -980,10 +1019,13 @@ class Model:
                    for j, x in enumerate(Xs)]
         return out if blocks else out[0]
 
-    def impute(self, X, missing, groups=None, device=0, return_var=False, draws=None, seed=0):
+    def impute(self, X, missing=None, groups=None, device=0, return_var=False, draws=None, seed=0):
         """A copy of the full-width rows X ((N, D) array or a list of blocks) with the columns `missing` replaced by
         their conditional mean given the other columns (predict_conditional).  What X holds in the missing columns is
-        not looked at (NaN is fine).  Rows whose missing columns differ from row to row: predict_incomplete.
+        not looked at (NaN is fine).
+        missing None: the NaNs of X say what is missing, every row with its own set (predict_incomplete, up to HOLES_MAX
+        per row): the filled copy, or with draws = m the list of m completed copies, copy i with draw i in every hole;
+        return_var is not offered there (predict_incomplete(variance=True) gives the variance by slot).
         return_var: (filled, var) with var (N, len(missing)) the predictive variance of the values filled in, in the
         order of `missing` (lists of each for a list of blocks).
         draws = m: multiple imputation -- a list of m completed copies, copy i filled with draw i of every row from
@@ -991,6 +1033,24 @@ class Model:
         if draws is not None and return_var:
             raise ValueError("draws and return_var are separate calls: ask for one of them")
         blocks = isinstance(X, (list, tuple))
+        if missing is None:
+            if return_var:
+                raise ValueError("return_var needs the columns `missing`: predict_incomplete(variance=True) gives the "
+                                 "variance of the values filled into NaNs")
+            res = self.predict_incomplete(list(X) if blocks else [X], groups, device, draws=draws, seed=seed)
+            if draws is None:
+                out = [r.rows for r in res]
+            else:
+                out = []
+                for r in res:
+                    copies = []
+                    ri, si = np.nonzero(r.cols >= 0)
+                    for i in range(int(draws)):
+                        c = r.rows.copy()
+                        c[ri, r.cols[ri, si]] = r.draws[ri, i, si]
+                        copies.append(c)
+                    out.append(copies)
+            return out if blocks else out[0]
         D = self.dims()[2]
         Xs = [np.array(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (X if blocks else [X])]
         miss = [int(c) for c in missing]
@@ -1048,33 +1108,49 @@ class Model:
         return out if blocks else out[0]
 
     # -- rows with holes -------------------------------------------------------------------------------
-    def predict_incomplete_context(self, ctx, groups=None, variance=False):
+    def predict_incomplete_context(self, ctx, groups=None, variance=False, draws=None, seed=0):
         """Complete the full-width rows resident in ctx in place: every NaN (up to HOLES_MAX per row, every row its own
         set) becomes E[x_unknown | x_known, training data] (lc_model_predict_incomplete).  Nothing is downloaded: read
         the rows with ctx.get_completed.  A second call on the same context finds no NaN any more.
         variance: also the predictive variance of every filled value (lc_model_predict_incomplete_var; DomainError, with
-        the NaNs left in place, where it does not exist); read it with ctx.get_completed(..., variance=True)."""
+        the NaNs left in place, where it does not exist); read it with ctx.get_completed(..., variance=True).
+        draws = m (1 ... DRAWS_MAX): also m draws per row of its unknown values from p(x_unknown | x_known, training
+        data) (lc_model_predict_incomplete_draws; a draw depends on seed, block, row, its index and the row's values only;
+        no moment has to exist); read them with ctx.get_completed(..., draws=m).  The context's rows hold the means."""
+        if draws is not None and variance:
+            raise ValueError("draws and variance are separate calls: ask for one of them")
         g = None
         if groups is not None:
             garr = np.ascontiguousarray(groups, dtype=np.int32)
             if garr.shape != (ctx.dims()[0],):
                 raise ValueError("groups needs one learned group index per block of the context")
             g = garr.ctypes.data_as(c_int_p)
+        if draws is not None:
+            m = int(draws)
+            if m < 1 or m > DRAWS_MAX:
+                raise ValueError(f"draws must be in 1 ... {DRAWS_MAX}")
+            check(lib().lc_model_predict_incomplete_draws(self._h, ctx._h, g, m, int(seed)))
+            return
         fn = lib().lc_model_predict_incomplete_var if variance else lib().lc_model_predict_incomplete
         check(fn(self._h, ctx._h, g))
 
-    def predict_incomplete(self, X, groups=None, device=0, variance=False):
+    def predict_incomplete(self, X, groups=None, device=0, variance=False, draws=None, seed=0):
         """Completion(rows, logp, count, cols) for the host rows X ((N, D) array, NaN = unknown), or a list of them for a
         list of blocks (block b mixed with learned group groups[b], default 0).  rows is a filled copy: X keeps its NaNs.
-        variance: CompletionVar, with var (N, HOLES_MAX) the predictive variance of the filled values."""
+        variance: CompletionVar, with var (N, HOLES_MAX) the predictive variance of the filled values.
+        draws = m: CompletionDraws(rows, logp, count, cols, draws (N, m, HOLES_MAX), label (N, m)): m draws per row of its
+        unknown values, the same bits for the same seed; rows holds the means."""
+        if draws is not None and variance:
+            raise ValueError("draws and variance are separate calls: ask for one of them")
         blocks = isinstance(X, (list, tuple))
         Xs = self._blocks(X)
         if not Xs:
             return []
         with Context(device) as ctx:
             ctx.set_data(Xs)
-            self.predict_incomplete_context(ctx, groups, variance)
-            out = [ctx.get_completed(j, 0, x.shape[0], variance) for j, x in enumerate(Xs)]
+            self.predict_incomplete_context(ctx, groups, variance, draws, seed)
+            out = [ctx.get_completed(j, 0, x.shape[0], variance, draws if draws is not None else False)
+                   for j, x in enumerate(Xs)]
         return out if blocks else out[0]
 
     # -- ranking (DESIGN 4.13) -------------------------------------------------------------------------------------

@@ -1258,6 +1258,32 @@ int lc_ctx_get_completed_var(lc_ctx* ctx, int j, int64_t row0, int64_t n, double
   });
 }
 
+// ---- draws of the filled values ----------------------------------------
+int lc_model_predict_incomplete_draws(lc_model* m, lc_ctx* ctx, const int* groups, int ndraws, uint64_t seed) {
+  return guarded([&] {
+    need(m, "model");
+    need(ctx, "ctx");
+    ctx->impl.predict_clear();  // (a failure leaves no prediction behind)
+    if (!model_alive(m)) throw std::invalid_argument("the model was freed");
+    if (ndraws < 1 || ndraws > LC_DRAWS_MAX) throw std::invalid_argument("ndraws must be in 1 ... 64");
+    lcp::predict_incomplete(ctx->impl, m->model, groups, /*want_var=*/false, ndraws, seed);
+  });
+}
+
+int lc_ctx_get_completed_draws(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* draws, int32_t* label) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.get_completed_draws(j, row0, n, draws, label);
+  });
+}
+
+int lc_ctx_completed_draws(lc_ctx* ctx, int* ndraws) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    if (ndraws) *ndraws = ctx->impl.completed_draws();
+  });
+}
+
 // ---- ranking -----------------------------------------------------
 int lc_ctx_top_rows(lc_ctx* ctx, int what, int ncols, int m, int largest, int by_label, int32_t* count, int32_t* group,
                     int64_t* row, double* score) {

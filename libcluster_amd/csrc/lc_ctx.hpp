@@ -285,6 +285,7 @@ class Context {
     pred_cond_var_ = false;
     pred_holes_ = false;
     pred_holes_var_ = false;
+    pred_holes_draws_ = 0;
     pred_cond_draws_ = 0;
   }
   // Conditional prediction: after a raw E-step with zero constants over the context's (given) columns left
@@ -324,11 +325,13 @@ class Context {
   // (lck::PredictHolesLaunch for the tables: tt J x NH x Kp, ps Kp, pe NH x Kp, mean Kp x D, P Kp x D x D host arrays,
   // NH = lck::HOLES_MAX + 1).  qZ is left holding the raw columns.  gnu (NH x Kp host values g_k(nb) nu_k):
   // also the predictive variance of every filled value (lck::PredictHolesVarLaunch), in a buffer that only such a call
-  // reserves; null: what the call did before, and no variance is readable afterwards.
+  // reserves; null: what the call did before, and no variance is readable afterwards.  ndraws > 0 (cqnu Kp
+  // host values, not together with gnu): also ndraws draws of every unknown value with their components
+  // (lck::HolesDrawsLaunch), in buffers that only such a call reserves; qZ then holds t_k for the rows with holes.
   void holes_scan(int64_t* holed_rows, int* max_count, int* bad_block, int64_t* bad_row, int* bad_count);
   void holes_fill(const double* fill);
   void predict_holes(int Kp, const double* tt, const double* ps, const double* pe, const double* mean, const double* P,
-                     const double* gnu = nullptr);
+                     const double* gnu = nullptr, const double* cqnu = nullptr, int ndraws = 0, uint64_t seed = 0);
   // rows [row0, row0+n) of group j after the last predict_holes (any output may be null): the completed rows (row_stride
   // >= D doubles apart), logp, count and cols [n x lck::HOLES_MAX] (ascending, -1 beyond count)
   void get_completed(int j, int64_t row0, int64_t n, double* rows, int64_t row_stride, double* logp, int32_t* count,
@@ -336,6 +339,10 @@ class Context {
   // ... and their variances [n x lck::HOLES_MAX] (row_stride >= lck::HOLES_MAX doubles apart; slot i belongs to cols[i], 0
   // beyond count; var may be null): throws when the last predict_holes had no gnu
   void get_completed_var(int j, int64_t row0, int64_t n, double* var, int64_t row_stride) const;
+  // ... and their draws [n x ndraws x lck::HOLES_MAX] (slot i belongs to cols[i], 0 beyond count) with the component of
+  // every draw [n x ndraws] (-1 in a row without holes); either may be null: throws when the last predict_holes drew none
+  void get_completed_draws(int j, int64_t row0, int64_t n, double* draws, int32_t* label) const;
+  int completed_draws() const { return pred_holes_ ? pred_holes_draws_ : 0; }  // draws per row held (0: none)
   // ---- ranking ----------------------------------------------------------------------------------------------
   // The m best rows of each column (lck::TopRowsLaunch for the order): what = 0 the first ncols columns of qZ, 1 / 2 the
   // logZ / logp of the last prediction (one column; ncols is not looked at).  by_label: column c only sees the rows the
@@ -529,6 +536,11 @@ class Context {
   // ... and, when pred_holes_var_, the variance of the filled values [NP x HOLES_MAX]
   DevBuf<double> hvar_;
   bool pred_holes_var_ = false;
+  // ... and, when pred_holes_draws_ > 0, that many draws of the filled values [NP x pred_holes_draws_ x HOLES_MAX] with
+  // their components [NP x pred_holes_draws_]
+  DevBuf<double> hdraws_;
+  DevBuf<int> hdlabel_;
+  int pred_holes_draws_ = 0;
   // top_rows: the first stage's partial lists and the result [C x m scores | C x m positions]
   DevBuf<double> topkey_, topout_;
   DevBuf<int64_t> toppos_;

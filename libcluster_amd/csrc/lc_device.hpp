@@ -335,6 +335,14 @@ __device__ __forceinline__ double wave_max(double v) {
   return v;
 }
 
+// lane `src` (wave-uniform) of a double, through the scalar unit
+__device__ __forceinline__ double readlane_f64(double v, int src) {
+  const long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), src);
+  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
 // group of a padded row and whether it holds an observation (rginfo: lck::rginfo_pack per row group, or null for a single
 // group of nrows rows)
 __device__ __forceinline__ bool row_valid(int64_t row, const int* rginfo, int64_t nrows, int& j) {

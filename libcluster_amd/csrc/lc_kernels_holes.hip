@@ -5,6 +5,8 @@
 // out of the distances again -- per (row, cluster) a rank-nb correction with the cluster's precision matrix
 // P_k = nu_k iW_k^-1 -- and writes the mixture of the clusters' linear experts into the holes.  Rows without holes take
 // predict_rows_kernel's predictive loop.
+// holes_draws_kernel then draws the unknown values: per draw a component by its responsibility and a
+// value from that component's conditional Student-t, on the factor of (P_k)_bb that predict_holes_kernel forms as well.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -12,6 +14,7 @@
 #include <type_traits>
 
 #include "lc_device.hpp"
+#include "lc_philox.hpp"
 #include "lc_predict.hpp"
 
 namespace lck {
@@ -124,9 +127,13 @@ __device__ __forceinline__ double fold8(const double (&acc)[HOLES_MAX], int lane
 // held to two waves per SIMD, which it reaches without scratch (248 registers) with the fill values in scalar registers.
 __device__ __forceinline__ const PredictHolesLaunch& holes_args(const PredictHolesLaunch& x) { return x; }
 __device__ __forceinline__ const PredictHolesLaunch& holes_args(const PredictHolesVarLaunch& x) { return x.h; }
-template <bool VAR>
+__device__ __forceinline__ const PredictHolesLaunch& holes_args(const PredictHolesKeepLaunch& x) { return x.h; }
+// <false, true> is <false> with one store more: the lane that owns cluster k keeps t_k of a row with holes
+// where it read the raw column, for holes_draws_kernel.
+template <bool VAR, bool KEEP = false>
 __global__ __launch_bounds__(PH_THREADS, VAR ? 2 : 0) void predict_holes_kernel(
-    std::conditional_t<VAR, PredictHolesVarLaunch, PredictHolesLaunch> aa) {
+    std::conditional_t<KEEP, PredictHolesKeepLaunch, std::conditional_t<VAR, PredictHolesVarLaunch, PredictHolesLaunch>> aa) {
+  static_assert(!(VAR && KEEP), "the draws call forms no variance");
   const PredictHolesLaunch& a = holes_args(aa);
   [[maybe_unused]] const double* __restrict__ gnu = nullptr;
   [[maybe_unused]] double* __restrict__ var = nullptr;
@@ -312,6 +319,9 @@ __global__ __launch_bounds__(PH_THREADS, VAR ? 2 : 0) void predict_holes_kernel(
       const double d2full = -2.0 * a.col[(size_t)k * a.ldq + hr];
       const double d2a = fmax(d2full - quad, 0.0);
       const double t = on ? tt[k] - log(prod) - pe[k] * log1p_nonneg(a.pscale[k] * d2a, ltab) : NINF;
+      if constexpr (KEEP) {
+        if (on) aa.tcol[(size_t)k * a.ldq + hr] = t;
+      }
       // fold the chunk into the running sums
       const double mnew = fmax(mrun, wave_max(t));
       const double f = exp_nonpos(mrun - mnew, etab), e = exp_nonpos(t - mnew, etab);
@@ -361,7 +371,178 @@ __global__ __launch_bounds__(PH_THREADS, VAR ? 2 : 0) void predict_holes_kernel(
   }
 }
 
+// Draws of the unknown values of rows with holes (the arithmetic is in lc_predict.hpp).  The rows with holes
+// of a wave one after the other, as in predict_holes_kernel: nb, the hole columns and the block are wave-uniform.
+__global__ __launch_bounds__(PH_THREADS) void holes_draws_kernel(HolesDrawsLaunch v) {
+  const PredictHolesLaunch& a = v.h;
+  constexpr int NH = HOLES_MAX + 1;
+  const int lane = threadIdx.x & 63;
+  const int64_t NP = a.nrg * RG;
+  const int64_t row = (int64_t)blockIdx.x * PH_THREADS + threadIdx.x, wrow0 = row - lane;
+  if (wrow0 >= NP) return;  // (whole waves only: the ballots and the fold below need every lane)
+  int j = 0;
+  const bool valid = row < NP && row_valid(row, a.rginfo, a.nrows, j);
+  const int cnt = valid ? a.count[row] : 0;
+  const int DP = a.DP, Kp = a.Kp, m = v.ndraws;
+  const bool mine = lane < m;  // lane i = draw i
+  unsigned long long todo = __ballot(valid && cnt > 0);
+  while (todo) {
+    const int src = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    const int64_t hr = wrow0 + src;
+    const int nb = __builtin_amdgcn_readfirstlane(__shfl(cnt, src));
+    const int jh = __builtin_amdgcn_readfirstlane(__shfl(j, src));
+    const double* __restrict__ xr = a.X + (size_t)hr * DP;  // the mean-completed row
+    int c[HOLES_MAX];
+    double xb[HOLES_MAX];
+#pragma unroll
+    for (int i = 0; i < HOLES_MAX; ++i) {
+      c[i] = i < nb ? __builtin_amdgcn_readfirstlane(a.cols[(size_t)hr * HOLES_MAX + i]) : 0;
+      xb[i] = i < nb ? xr[c[i]] : 0.0;
+    }
+    const double* __restrict__ tt = a.ttab + ((size_t)jh * NH + nb) * Kp;
+    const double* __restrict__ pe = a.pexp + (size_t)nb * Kp;
+    const double* __restrict__ tc = a.col + hr;  // t_k at tc[k * ldq]
+    const double logp = a.logp[hr];
+    const uint64_t g = ((uint64_t)jh << 40) + (uint64_t)(hr - (v.goff ? v.goff[jh] : 0));
+    const RngStream st = rng_stream(g, v.seed, (uint32_t)lane);
+    uint32_t o[4];
+    // the component: lane kk forms r of cluster k0 + kk once, every lane walks the running sum (the same in all) against its own u
+    st.block(RNG_TAG_CHOICE, 0u, o);
+    const double uu = u01(o[0], o[1]);
+    double cum = 0.0;
+    int k1 = -1, last = 0;
+    for (int k0 = 0; k0 < Kp; k0 += 64) {
+      const int kc = Kp - k0 < 64 ? Kp - k0 : 64;
+      const double rl = lane < kc ? exp(tc[(size_t)(k0 + lane) * a.ldq] - logp) : 0.0;
+      for (int kk = 0; kk < kc; ++kk) {
+        const double r = readlane_f64(rl, kk);
+        if (r > 0.0) {
+          cum += r;
+          if (k1 < 0) {  // still looking: remember the last component with weight, take the first whose sum exceeds u
+            last = k0 + kk;
+            if (cum > uu) k1 = k0 + kk;
+          }
+        }
+      }
+    }
+    if (k1 < 0) k1 = last;
+    const double G = mine ? gamma_draw(st, pe[k1]) : 1.0;
+    double z[HOLES_MAX];
+#pragma unroll
+    for (int p = 0; p < HOLES_MAX / 2; ++p) {
+      z[2 * p] = 0.0;
+      z[2 * p + 1] = 0.0;
+      if (2 * p < nb) {
+        st.block(RNG_TAG_NORMAL, (uint32_t)p, o);
+        box_muller(o, z[2 * p], z[2 * p + 1]);
+      }
+    }
+    if (mine) v.label[(size_t)hr * m + lane] = k1;
+    // the distinct components the draws chose, one after the other (a hard row has one)
+    unsigned long long rem = __ballot(mine);
+    while (rem) {
+      const int k = __builtin_amdgcn_readlane(k1, __ffsll((long long)rem) - 1);
+      const bool sel = mine && k1 == k;
+      rem &= ~__ballot(sel);
+      const double* __restrict__ Pk = a.P + (size_t)k * DP * DP;
+      const double* __restrict__ mk = a.mean + (size_t)k * DP;
+      // u = (P_k y)_b: predict_holes_kernel's reads and fold, then the eight sums into every lane
+      double acc[HOLES_MAX];
+#pragma unroll
+      for (int i = 0; i < HOLES_MAX; ++i) acc[i] = 0.0;
+      for (int d = lane; d < DP; d += 64) {
+        const double y = xr[d] - mk[d];  // (pad columns: 0 - 0)
+#pragma unroll
+        for (int i = 0; i < HOLES_MAX; ++i)
+          if (i < nb) acc[i] = fma(Pk[(size_t)c[i] * DP + d], y, acc[i]);
+      }
+      const double us = fold8(acc, lane);
+      double u[HOLES_MAX];
+#pragma unroll
+      for (int i = 0; i < HOLES_MAX; ++i) u[i] = readlane_f64(us, ((i & 1) << 5) | ((i & 2) << 3) | ((i & 4) << 1));
+      // H = P_bb padded with the identity, H = L L^T (the same in every lane: a SIMD does it once for all of them)
+      double L[HOLES_MAX][HOLES_MAX];
+#pragma unroll
+      for (int i = 0; i < HOLES_MAX; ++i)
+#pragma unroll
+        for (int jj = 0; jj <= i; ++jj) L[i][jj] = i < nb ? Pk[(size_t)c[i] * DP + c[jj]] : i == jj ? 1.0 : 0.0;
+      double inv[HOLES_MAX], prod = 1.0;
+#pragma unroll
+      for (int jj = 0; jj < HOLES_MAX; ++jj) {
+        inv[jj] = 1.0;
+        if (jj < nb) {
+          double sjj = L[jj][jj];
+#pragma unroll
+          for (int q = 0; q < jj; ++q) sjj = fma(-L[jj][q], L[jj][q], sjj);
+          const double ljj = sqrt(sjj);
+          inv[jj] = 1.0 / ljj;
+          prod *= ljj;
+#pragma unroll
+          for (int i = jj + 1; i < HOLES_MAX; ++i) {
+            double sij = L[i][jj];
+#pragma unroll
+            for (int q = 0; q < jj; ++q) sij = fma(-L[i][q], L[jj][q], sij);
+            L[i][jj] = sij * inv[jj];
+          }
+        }
+      }
+      // w = H^-1 u (in place in u): M_k = x_b - w
+#pragma unroll
+      for (int i = 0; i < HOLES_MAX; ++i) {
+        double s = u[i];
+#pragma unroll
+        for (int q = 0; q < i; ++q) s = fma(-L[i][q], u[q], s);
+        u[i] = s * inv[i];
+      }
+#pragma unroll
+      for (int i = HOLES_MAX - 1; i >= 0; --i) {
+        double s = u[i];
+#pragma unroll
+        for (int q = i + 1; q < HOLES_MAX; ++q) s = fma(-L[q][i], u[q], s);
+        u[i] = s * inv[i];
+      }
+      // 1 + s_k d_a^2 back from t_k = ttab - log prod L_ii - e_k log1p(s_k d_a^2), as cond_draws_kernel recovers it
+      const double h = fmax(exp((tt[k] - log(prod) - tc[(size_t)k * a.ldq]) / pe[k]), 1.0);
+      const double f = sqrt(v.cqnu[k] * h / G);
+      // L^T x = z with the lane's own z: sqrt(nu) L^-T is a factor of S_k = nu H^-1 (nu is in cqnu)
+      double x[HOLES_MAX];
+#pragma unroll
+      for (int i = HOLES_MAX - 1; i >= 0; --i) {
+        double s = z[i];
+#pragma unroll
+        for (int q = i + 1; q < HOLES_MAX; ++q) s = fma(-L[q][i], x[q], s);
+        x[i] = s * inv[i];
+      }
+      if (sel) {
+        double* __restrict__ dr = v.draws + ((size_t)hr * m + lane) * HOLES_MAX;
+#pragma unroll
+        for (int i = 0; i < HOLES_MAX; ++i)
+          if (i < nb) dr[i] = fma(f, x[i], xb[i] - u[i]);
+      }
+    }
+  }
+}
+
 }  // namespace
+
+hipError_t launch_predict_holes_keep(const PredictHolesKeepLaunch& a, hipStream_t stream) {
+  const int64_t rows = a.h.nrg * RG;
+  if (rows == 0) return hipSuccess;
+  if (a.h.Kp < 1 || a.h.DP < 1 || !a.tcol || a.tcol != a.h.col) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((predict_holes_kernel<false, true>), dim3((unsigned)((rows + PH_THREADS - 1) / PH_THREADS)), dim3(PH_THREADS), 0,
+                     stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_holes_draws(const HolesDrawsLaunch& v, hipStream_t stream) {
+  const int64_t rows = v.h.nrg * RG;
+  if (rows == 0) return hipSuccess;
+  if (v.h.Kp < 1 || v.h.DP < 1 || !v.cqnu || !v.draws || !v.label || v.ndraws < 1 || v.ndraws > DRAWS_MAX)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(holes_draws_kernel, dim3((unsigned)((rows + PH_THREADS - 1) / PH_THREADS)), dim3(PH_THREADS), 0, stream, v);
+  return hipGetLastError();
+}
 
 hipError_t launch_holes_scan(const HolesScanLaunch& a, hipStream_t stream) {
   const int64_t rows = a.nrg * RG;

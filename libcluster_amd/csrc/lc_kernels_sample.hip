@@ -147,14 +147,6 @@ __global__ void __launch_bounds__(256) sample_diag_kernel(SampleLaunch a) {
   }
 }
 
-// lane `src` (wave-uniform) of a double, through the scalar unit
-__device__ __forceinline__ double readlane_f64(double v, int src) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), src);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 constexpr int CD_THREADS = PC_THREADS;
 constexpr int CD_BATCH = 8;  // table values loaded side by side: the gathers come from L2, one at a time leaves the wave waiting
 constexpr int CD_DRAWS = 4;  // draws of a row whose component and scale are resident between the two parts of the kernel

@@ -1,6 +1,6 @@
 // Counter-based random numbers on the device: Philox-4x32-10, 53-bit uniforms, a Box-Muller pair and a
 // Marsaglia-Tsang gamma draw.  Shared by the synthetic-data generator (lc_kernels_aux.hip) and the model samplers
-// (lc_kernels_sample.hip).  Every value is a function of its counter and the key alone: nothing here depends on the launch
+// (lc_kernels_sample.hip; holes_draws_kernel in lc_kernels_holes.hip).  Every value is a function of its counter and the key alone: nothing here depends on the launch
 // shape or on what other lanes do.  The counter table is in the header comment of include/libcluster_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>

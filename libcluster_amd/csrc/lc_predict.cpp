@@ -419,14 +419,18 @@ void Context::holes_fill(const double* fill) {
 }
 
 void Context::predict_holes(int Kp, const double* tt, const double* ps, const double* pe, const double* mean,
-                            const double* P, const double* gnu) {
+                            const double* P, const double* gnu, const double* cqnu, int ndraws, uint64_t seed) {
   use_device();
   if (Kp < 1) throw std::invalid_argument("K must be >= 1");
   pred_holes_ = false;
   pred_holes_var_ = false;
+  pred_holes_draws_ = 0;
+  if (ndraws < 0 || ndraws > lck::DRAWS_MAX) throw std::invalid_argument("ndraws must be in 1 ... 64");
+  if (ndraws > 0 && (gnu || !cqnu)) throw std::logic_error("predict_holes: draws come with cqnu and without the variance");
   if (NP_ == 0) {
     pred_holes_ = true;
     pred_holes_var_ = gnu != nullptr;
+    pred_holes_draws_ = ndraws;
     return;
   }
   if (qz_[cur_].cap < Kp || !qz_[cur_].buf.p) throw std::logic_error("predict_holes: no raw E-step columns");
@@ -435,11 +439,13 @@ void Context::predict_holes(int Kp, const double* tt, const double* ps, const do
   const int D = D_, DP = DP_;
   hlogp_.reserve((size_t)NP_);
   if (gnu) hvar_.reserve((size_t)NP_ * lck::HOLES_MAX);
-  // tables: [tt J x NH x Kp | ps Kp | pe NH x Kp | mean Kp x DP | P Kp x DP x DP], the pads zero; with gnu: [... | gnu NH x Kp]
+  // tables: [tt J x NH x Kp | ps Kp | pe NH x Kp | mean Kp x DP | P Kp x DP x DP], the pads zero; with gnu: [... | gnu NH x Kp],
+  // with draws: [... | cqnu Kp]
   const size_t nt = (size_t)J_ * NH * Kp, ne = (size_t)NH * Kp, nm = (size_t)Kp * DP, nP = nm * DP;
-  hpack_.assign(nt + (size_t)Kp + ne + nm + nP + (gnu ? ne : 0), 0.0);
+  hpack_.assign(nt + (size_t)Kp + ne + nm + nP + (gnu ? ne : 0) + (ndraws > 0 ? (size_t)Kp : 0), 0.0);
   double* h = hpack_.data();
   if (gnu) std::copy(gnu, gnu + ne, h + nt + Kp + ne + nm + nP);
+  if (ndraws > 0) std::copy(cqnu, cqnu + Kp, h + nt + Kp + ne + nm + nP);
   std::copy(tt, tt + nt, h);
   std::copy(ps, ps + Kp, h + nt);
   std::copy(pe, pe + ne, h + nt + Kp);
@@ -475,6 +481,25 @@ void Context::predict_holes(int Kp, const double* tt, const double* ps, const do
     v.gnu = a.P + nP;
     v.var = hvar_.p;
     LC_HIP(lck::launch_predict_holes_var(v, stream_));
+  } else if (ndraws > 0) {
+    // every valid row's slots on every call: draws 0 and components -1 (all bits set), then the rows with holes over them
+    hdraws_.reserve((size_t)NP_ * ndraws * lck::HOLES_MAX);
+    hdlabel_.reserve((size_t)NP_ * ndraws);
+    LC_HIP(hipMemsetAsync(hdraws_.p, 0, (size_t)NP_ * ndraws * lck::HOLES_MAX * sizeof(double), stream_));
+    LC_HIP(hipMemsetAsync(hdlabel_.p, 0xff, (size_t)NP_ * ndraws * sizeof(int), stream_));
+    lck::PredictHolesKeepLaunch kp;
+    kp.h = a;
+    kp.tcol = qz_[cur_].buf.p;
+    LC_HIP(lck::launch_predict_holes_keep(kp, stream_));
+    lck::HolesDrawsLaunch v;
+    v.h = a;
+    v.goff = J_ > 1 ? goff_d_.p : nullptr;
+    v.cqnu = a.P + nP;
+    v.ndraws = ndraws;
+    v.seed = seed;
+    v.draws = hdraws_.p;
+    v.label = hdlabel_.p;
+    LC_HIP(lck::launch_holes_draws(v, stream_));
   } else {
     LC_HIP(lck::launch_predict_holes(a, stream_));
   }
@@ -484,6 +509,22 @@ void Context::predict_holes(int Kp, const double* tt, const double* ps, const do
   dcache_invalidate();  // (the observations changed)
   pred_holes_ = true;
   pred_holes_var_ = gnu != nullptr;
+  pred_holes_draws_ = ndraws;
+}
+
+void Context::get_completed_draws(int j, int64_t row0, int64_t n, double* draws, int32_t* label) const {
+  use_device();
+  if (!pred_holes_ || pred_holes_draws_ < 1)
+    throw std::invalid_argument("the context holds no draws of completed rows (lc_model_predict_incomplete_draws)");
+  if (j < 0 || j >= J_ || row0 < 0 || n < 0 || row0 + n > Nj_[j]) throw std::invalid_argument("row range out of bounds");
+  if (n == 0) return;
+  const size_t at = (size_t)(goff_[j] + row0) * pred_holes_draws_, cnt = (size_t)n * pred_holes_draws_;
+  static_assert(sizeof(int) == sizeof(int32_t), "the components are int32");
+  if (draws)
+    LC_HIP(hipMemcpyAsync(draws, hdraws_.p + at * lck::HOLES_MAX, cnt * lck::HOLES_MAX * sizeof(double), hipMemcpyDeviceToHost,
+                          stream_));
+  if (label) LC_HIP(hipMemcpyAsync(label, hdlabel_.p + at, cnt * sizeof(int), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
 }
 
 void Context::get_completed_var(int j, int64_t row0, int64_t n, double* var, int64_t row_stride) const {
@@ -1049,8 +1090,11 @@ void gw_precision_var(int D, double nu, double beta, double* g) {
   }
 }
 
-void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* groups, bool want_var) {
+void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* groups, bool want_var, int ndraws,
+                        uint64_t seed) {
   ctx.predict_clear();  // (whatever an earlier prediction left must not outlive a failure of this one)
+  if (ndraws < 0 || ndraws > lck::DRAWS_MAX) throw std::invalid_argument("ndraws must be in 1 ... 64");
+  if (ndraws > 0 && want_var) throw std::invalid_argument("draws and the variance are two calls");
   constexpr int NH = lck::HOLES_MAX + 1;
   const int K = (int)model.clusters.size(), J = (int)model.weights.size(), Jc = ctx.J();
   if (K < 1) throw std::invalid_argument("the model has no clusters");
@@ -1146,7 +1190,17 @@ void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* g
   if (holed > 0) ctx.holes_fill(fill.data());
   // one raw E-step at full width over the K clusters (+ the prior's whitener): -d_full^2 / 2 per column
   ctx.estep(Kp, A.data(), m.data(), zero.data(), nullptr, nullptr, /*raw=*/true);
-  ctx.predict_holes(Kp, tt.data(), ps.data(), pe.data(), m.data(), P.data(), want_var ? gnu.data() : nullptr);
+  // the draws' table: cqnu_k = (1 + beta_k) nu_k / (2 beta_k), no moment has to exist
+  std::vector<double> cqnu;
+  if (ndraws > 0) {
+    cqnu.resize((size_t)Kp);
+    for (int k = 0; k < Kp; ++k) {
+      const lch::GaussWishState& g = k < K ? model.clusters[(size_t)k].gw : prior.gw;
+      cqnu[(size_t)k] = (1 + g.beta) * g.nu / (2 * g.beta);
+    }
+  }
+  ctx.predict_holes(Kp, tt.data(), ps.data(), pe.data(), m.data(), P.data(), want_var ? gnu.data() : nullptr,
+                    ndraws > 0 ? cqnu.data() : nullptr, ndraws, seed);
 }
 
 void exemplars(lcc::Context& ctx, const lce::Model& model, bool sparse, const int* groups, int mtop, int32_t* count,

@@ -238,6 +238,36 @@ struct PredictCondDrawsLaunch {
 };
 hipError_t launch_predict_cond_draws(const PredictCondDrawsLaunch& a, hipStream_t stream);
 
+// Draws for rows with holes (lc_kernels_holes.hip).  launch_predict_holes_keep: predict_holes_kernel with
+// the same bits in X and logp, which also leaves t_k of every row WITH holes in tcol[k * ldq + row] (the raw column of that
+// row and cluster, read by the one lane that then overwrites it; the rows without holes keep their raw columns).
+struct PredictHolesKeepLaunch {
+  PredictHolesLaunch h;    // as launched without draws
+  double* tcol = nullptr;  // == h.col
+};
+hipError_t launch_predict_holes_keep(const PredictHolesKeepLaunch& a, hipStream_t stream);
+// holes_draws_kernel: after that launch, on its arguments and what it left (t_k, logp, the mean-completed X).  Per row with
+// holes and draw i < ndraws: component k by inverse CDF over r_k = exp(t_k - logp) (the choice uniform of (block, row, draw)
+// is cond_draws_kernel's), G ~ Gamma(e_k(nb)), z the normals of the holes (pair p -> slots 2p, 2p + 1 of cols), then with
+// H = (P_k)_bb = L L^T, M_k = x_b - H^-1 (P_k (x - m_k))_b (the same for any value in the holes) and
+// h_k = exp((ttab[j][nb][k] - log prod_i L_ii - t_k) / e_k(nb)):
+//   x_b = M_k + sqrt(cqnu_k h_k / G) v,  L^T v = z
+// A wave works on its rows with holes one after the other: lane i = draw i in the choice, the gamma draw and the normals,
+// then per DISTINCT chosen component the lanes own columns for u (predict_holes_kernel's reads and fold) and every lane
+// runs the factorisation and the solves, with its own z in the last.  draws [row][i][slot] belongs to cols[row][slot];
+// label [row][i] = k.  Only rows with holes are written, slots < count: the launcher's caller clears draws to 0 and label
+// to -1 first.  No atomics, no LDS, no barrier: the same bits on every call, whatever ndraws and wherever the row sits.
+struct HolesDrawsLaunch {
+  PredictHolesLaunch h;            // as launched before (col holds t_k for the rows with holes)
+  const int64_t* goff = nullptr;   // [J + 1] padded block offsets, or nullptr (single block)
+  const double* cqnu = nullptr;    // [Kp] (1 + beta_k) nu_k / (2 beta_k)
+  int ndraws = 0;
+  uint64_t seed = 0;
+  double* draws = nullptr;  // [NP x ndraws x HOLES_MAX]
+  int* label = nullptr;     // [NP x ndraws]
+};
+hipError_t launch_holes_draws(const HolesDrawsLaunch& a, hipStream_t stream);
+
 }  // namespace lck
 
 namespace lch {
@@ -309,7 +339,11 @@ void gw_precision(int D, double nu, double beta, const double* iW, double* P, do
 // want_var: also the predictive variance of every filled value (Context::get_completed_var).  Throws
 // std::domain_error, after the scan and before anything is written to the observations, when a component with weight in
 // some block has nu - 1 - cmax <= 0 with cmax the largest hole count of the WHOLE context (conservative and strict).
-void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* groups, bool want_var = false);
+// ndraws > 0 (not together with want_var): also that many draws of every unknown value per row, each from
+// the mixture of the clusters' conditional Student-t densities (Context::get_completed_draws); the completed rows, logp and
+// the hole records are the bits of the call without.  No moment has to exist: no std::domain_error.
+void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* groups, bool want_var = false, int ndraws = 0,
+                        uint64_t seed = 0);
 // The table of that variance: g[nb] = (1 + beta) / (beta (nu' + Da - 2)) = (1 + beta) / (beta (nu - 1 - nb)) for nb = 0 ...
 // lck::HOLES_MAX holes, so that cluster k's conditional covariance is g[nb] (1 + s d_a^2) nu (P_bb)^-1; NaN where nb >= D or
 // nu - 1 - nb <= 0.  Throws std::invalid_argument for nu <= D - 1, beta <= 0.
