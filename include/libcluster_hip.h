@@ -233,6 +233,15 @@ int lc_ctx_speck_passes(lc_ctx* ctx, int64_t* skipping, int64_t* dense);
  * chunk and quad, the list of the rows that keep a value of that quad, and then sums every list on its own.  Same records,
  * same bound; lc_ctx_set_speck_skip(ctx, 0) turns it off with the rest. */
 int lc_ctx_speck_list_passes(lc_ctx* ctx, int64_t* lists);
+/* A Gauss-Wishart E-step at 49 <= D <= 64 (a padded width of 64 columns) whose statistics pass could take the list route
+ * (the feature-GEMM kernel owns it: more than 16 clusters there) writes, next to the responsibilities,
+ * one bit per (row, cluster quad): "the row keeps a value of the quad", taken on the value it stores.  The pass that
+ * follows then takes the probe's counts and builds its lists from those bits instead of reading qZ again.  Any other
+ * writer of qZ withdraws the bits, and the pass probes and builds from qZ as before.  Same results bit for bit.  On by
+ * default; sub-problems of the split search inherit the setting. */
+int lc_ctx_set_estep_masks(lc_ctx* ctx, int on);
+/* How many list passes of this context were built from such bits. */
+int lc_ctx_speck_mask_passes(lc_ctx* ctx, int64_t* masks);
 
 /* Device and page-locked blocks released by contexts are cached for re-use (the split search builds a context per
  * attempt); this returns all of them to the driver. */

@@ -270,6 +270,8 @@ def lib() -> C.CDLL:
     L.lc_ctx_set_speck_skip.argtypes = [C.c_void_p, C.c_int]
     L.lc_ctx_speck_passes.argtypes = [C.c_void_p, c_int64_p, c_int64_p]
     L.lc_ctx_speck_list_passes.argtypes = [C.c_void_p, c_int64_p]
+    L.lc_ctx_set_estep_masks.argtypes = [C.c_void_p, C.c_int]
+    L.lc_ctx_speck_mask_passes.argtypes = [C.c_void_p, c_int64_p]
     L.lc_ctx_get_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p]
     L.lc_ctx_set_qz.argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_int, C.c_int64, C.c_int64]
     L.lc_ctx_get_qz.argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_int64, C.c_int64]
@@ -502,6 +504,18 @@ class Context:
         """-> how many of the skipping passes summed per-quad row lists (the list route)"""
         a = C.c_int64()
         check(lib().lc_ctx_speck_list_passes(self._h, C.byref(a)))
+        return a.value
+
+    def set_estep_masks(self, on: bool = True):
+        """E-steps whose statistics pass could take the list route write one "kept" bit per (row, cluster quad) next to
+        the responsibilities (the default); the pass that follows builds its lists from them.  False: every pass probes
+        and builds from qZ.  Same results bit for bit."""
+        check(lib().lc_ctx_set_estep_masks(self._h, int(on)))
+
+    def speck_mask_passes(self):
+        """-> how many list passes were built from the kept bits of the E-step that wrote qZ"""
+        a = C.c_int64()
+        check(lib().lc_ctx_speck_mask_passes(self._h, C.byref(a)))
         return a.value
 
     def set_sharding(self, whole_groups: bool):

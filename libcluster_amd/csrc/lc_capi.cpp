@@ -483,6 +483,21 @@ int lc_ctx_speck_list_passes(lc_ctx* ctx, int64_t* lists) {
   });
 }
 
+int lc_ctx_set_estep_masks(lc_ctx* ctx, int on) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.set_estep_masks(on != 0);
+  });
+}
+
+int lc_ctx_speck_mask_passes(lc_ctx* ctx, int64_t* masks) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    need(masks, "masks");
+    *masks = ctx->impl.speck_passes_masks();
+  });
+}
+
 int lc_ctx_get_rows(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* out) {
   return guarded([&] {
     need(ctx, "ctx");

@@ -202,6 +202,7 @@ template struct DevBuf<double>;
 template struct DevBuf<int>;
 template struct DevBuf<int64_t>;
 template struct DevBuf<unsigned char>;
+template struct DevBuf<unsigned short>;
 
 Context::Context(int device, hipStream_t stream) : device_(device), stream_(stream) {
   // hipGetDeviceCount costs ~2.5 ms per call; the split search builds a context per attempt
@@ -436,10 +437,23 @@ static bool test_keep_stale() {
   static const bool on = std::getenv("LC_TEST_QHASH_KEEP_STALE") != nullptr;
   return on;
 }
+// tests (LC_TEST_QMASK_KEEP_STALE): the writers of qZ "forget" to withdraw the kept-quad masks an E-step left with the
+// buffer.  The check of LC_TEST_VERIFY_QMASK (Context::suffstat) has to notice.
+static bool test_keep_stale_masks() {
+  static const bool on = std::getenv("LC_TEST_QMASK_KEEP_STALE") != nullptr;
+  return on;
+}
 #endif
+void Context::qz_written(QZ& q) {
+#ifdef LC_TEST_HOOKS
+  if (test_keep_stale_masks()) return;
+#endif
+  q.mask_ok = false;
+}
 void Context::ensure_qz(QZ& q, int K, bool preserve) {
   use_device();
   q.hash_ok = false;  // (whoever asks for the buffer is about to write it; estep_cache and the split helpers re-validate)
+  qz_written(q);      // (... and Context::estep alone sets the masks' flag again)
 #ifdef LC_TEST_HOOKS
   if (test_keep_stale() && q.hash.p) q.hash_ok = true;
 #endif
@@ -470,6 +484,7 @@ void Context::qz_set(int j, const double* q, int K, int64_t rs, int64_t cs) {
   if (j < 0 || j >= J_) throw std::invalid_argument("group index out of range");
   if (K < 1) throw std::invalid_argument("K must be >= 1");
   qz_[cur_].hash_ok = false;
+  qz_written(qz_[cur_]);
   if (K != qz_[cur_].K) {
     ensure_qz(qz_[cur_], K, false);
     // a new K invalidates every group: start from zeros
@@ -645,6 +660,7 @@ void Context::qz_keep_columns(const std::vector<int>& keep) {
   }
   q.K = (int)keep.size();
   q.hash_ok = false;  // (columns moved: the rows' fingerprints weigh every value by its column)
+  qz_written(q);      // (... and the masks are per quad of columns)
 #ifdef LC_TEST_HOOKS
   if (test_keep_stale() && q.hash.p) q.hash_ok = true;
 #endif
@@ -661,6 +677,7 @@ void Context::qz_clone_to_alt() {
   static const bool full_only = lck::test_switch("LC_SPLIT_FULL_CLONE") != nullptr;
   if (!full_only && NP_ > 0 && Ksave >= 1 && qz_[cur_].hash_ok && a.hash_ok && a.buf.p && a.hash.p && qz_[cur_].hash.p &&
       a.cap >= Ksave + 1 && (a.K == Ksave || a.K == Ksave + 1)) {
+    qz_written(a);  // (the copy's masks are not kept up: its first pass probes and builds from qZ)
     LC_HIP(lck::launch_qz_resync(a.buf.p, qz_[cur_].buf.p, NP_, Ksave, Ksave + 1, NP_, a.hash.p, qz_[cur_].hash.p, stream_));
     a.K = Ksave;
     clone_resyncs_ += 1;
@@ -809,6 +826,7 @@ void Context::qz_split_from(const Context& sub, const RowSelection& sel, int k) 
   const bool hashed = q.hash_ok;  // (a new zero column leaves a row's fingerprint as it is; rewritten rows are marked)
   if (q.K + 1 > q.cap) ensure_qz(q, q.K + 1, true);
   q.hash_ok = hashed;
+  qz_written(q);  // (a column more and rows rewritten)
   bool mark = hashed;
 #ifdef LC_TEST_HOOKS
   if (test_keep_stale()) mark = false;
@@ -1011,16 +1029,49 @@ void Context::estep(int K, const double* A, const double* m, const double* c, do
     ensure_qz(qz_[cur_], K, false);  // E-step overwrites every column
     qz_[cur_].K = K;
   }
-  const lck::EstepLaunch a =
+  lck::EstepLaunch a =
       gw_estep_launch(K, A, m, c, X_.p, NP_, Nj_[0], target ? target : qz_[cur_].buf.p, raw, LLk != nullptr);
+  // Kept-quad masks with the responsibilities: where the statistics pass that follows could take the list
+  // route for this width and the plan's instance emits them, the sweep writes them and the selector's sample is taken from
+  // them behind the sums -- its two counts arrive under the synchronisation below, and Context::suffstat needs neither a
+  // probe's round trip nor a third reading of qZ.  (K <= 256: the probe counts one-quad rows only while a step's quads sit
+  // in one wave.)
+  QZ& q = qz_[cur_];
+  bool masks = estep_masks_ && !target && !raw && NP_ >= lck::SPECK_PROBE_MIN_ROWS && K <= 256 && speck_skip_ && !skip_zero_ &&
+               lck::speck_lists_enabled() && lck::suffstat_list_instance(DP_, DC_) && lck::estep_plan(a).emits;
+  if (masks) {
+    // ... and the dense pass of this shape runs the feature GEMM, the only route with lists (K <= 16 at this width is the
+    // few-cluster kernel's: masks nobody reads).  The plan's fill searches are not free: asked once per shape.
+    if (mask_route_K_ != K || mask_route_NP_ != NP_ || mask_route_DC_ != DC_) {
+      mask_route_feat_ = lck::suffstat_plan(DP_, DC_, NP_, K, lck::SS_DENSE).route == lck::SS_FEAT;
+      mask_route_K_ = K, mask_route_NP_ = NP_, mask_route_DC_ = DC_;
+    }
+    masks = mask_route_feat_;
+  }
+  if (masks) {
+    q.qmask.reserve((size_t)((K + 3) / 4) * (size_t)a.nrg);
+    a.qmask = q.qmask.p;
+  }
   timed(Timed::Estep, [&] { LC_HIP(lck::launch_estep(a, stream_)); });
   if (raw) {
     LC_HIP(hipStreamSynchronize(stream_));
     return;
   }
   enqueue_sums(lck::estep_grid(a), K, LLk != nullptr);
+  if (masks) {
+    speck_active_.reserve(2);
+    hprobe_.resize(1);
+    LC_HIP(lck::launch_speck_probe_masks(q.qmask.p, a.nrg, K, NP_, speck_active_.p, &q.mask_pairs, stream_, &q.mask_rows));
+    LC_HIP(hipMemcpyAsync(hprobe_.data(), speck_active_.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream_));
+  }
   run_overlap();
   LC_HIP(hipStreamSynchronize(stream_));
+  if (masks) {
+    std::memcpy(q.mask_counts, hprobe_.data(), 2 * sizeof(int));
+    q.mask_K = K;
+    q.mask_nrg = a.nrg;
+    q.mask_ok = true;
+  }
   read_sums(K, Fz, LLk);
 }
 
@@ -1167,6 +1218,26 @@ int Context::build_sparse_worklist(const unsigned char* smask, int K, const lck:
   return nrec;
 }
 
+#ifdef LC_TEST_HOOKS
+// tests (LC_TEST_VERIFY_QMASK): before a pass trusts the masks of a slot, recompute them from its qZ by the rule and throw
+// on any difference -- a writer that left mask_ok standing over values it changed is caught here
+void Context::verify_qmask(const QZ& q) {
+  const int64_t nrg = NP_ / lck::RG;
+  const size_t n = (size_t)((q.K + 3) / 4) * (size_t)nrg;
+  DevBuf<unsigned short> ref;
+  ref.reserve(n);
+  LC_HIP(lck::launch_qmask_from_qz(q.buf.p, NP_, q.K, nrg, ref.p, stream_));
+  std::vector<unsigned short> have(n), want(n);
+  LC_HIP(hipMemcpyAsync(want.data(), ref.p, n * sizeof(unsigned short), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipMemcpyAsync(have.data(), q.qmask.p, n * sizeof(unsigned short), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+  size_t nbad = 0;
+  for (size_t i = 0; i < n; ++i) nbad += have[i] != want[i] ? 1 : 0;
+  if (nbad) throw std::runtime_error("LC_TEST_VERIFY_QMASK: " + std::to_string(nbad) + " mask words are not those of qZ (K = " + std::to_string(q.K) + ")");
+  std::cerr << "[masks] verified, K " << q.K << std::endl;
+}
+#endif
+
 void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, double* xxs, double* Njk) {
   const int K = qz_[cur_].K, D = D_, DP = DP_;
   if (K < 1) throw std::invalid_argument("qZ has not been set");
@@ -1218,14 +1289,33 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
     const int nchunks = plan.nchunks, KR = plan.KR, extra = plan.extra;
     a.skip_listed = listed && skip_zero_;
     bool lists = false;  // the pass runs over per-quad row lists
+    bool from_masks = false;  // ... built from the kept-quad masks of the E-step that wrote qZ (QZ::qmask)
     if (speck_skip_ && plan.route == lck::SS_FEAT && NP_ >= lck::SPECK_PROBE_MIN_ROWS) {
       // the selector: skip only where the probe finds at least a quarter of the sampled pairs skippable
       speck_active_.reserve(2);
       int64_t pairs = 0, rows = 0;
       int counts2[2] = {0, 0};
-      LC_HIP(lck::launch_speck_probe(a.qZ, a.ldq, K, NP_, speck_active_.p, &pairs, stream_, &rows));
-      LC_HIP(hipMemcpyAsync(counts2, speck_active_.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream_));
-      LC_HIP(hipStreamSynchronize(stream_));
+      const QZ& q = qz_[cur_];
+      from_masks = estep_masks_ && q.mask_ok && q.mask_K == K && q.mask_nrg == NP_ / lck::RG && q.qmask.p != nullptr;
+#ifdef LC_TEST_HOOKS
+      // (LC_TEST_QMASK_KEEP_STALE also forgets which K the masks were written for, wherever the buffer can hold this K's
+      //  words: the writers that change K -- qz_split_from, qz_keep_columns -- are then caught by the check below and not
+      //  hidden behind mask_K)
+      if (test_keep_stale_masks() && estep_masks_ && q.mask_ok && q.mask_nrg == NP_ / lck::RG && q.qmask.p != nullptr &&
+          q.qmask.cap >= (size_t)((K + 3) / 4) * (size_t)(NP_ / lck::RG))
+        from_masks = true;
+      if (from_masks && std::getenv("LC_TEST_VERIFY_QMASK") != nullptr) verify_qmask(q);
+#endif
+      if (from_masks) {
+        // the E-step that wrote this buffer left its kept-quad masks and took the same sample from them: no probe launch,
+        // no copy and no synchronisation here
+        pairs = q.mask_pairs, rows = q.mask_rows;
+        counts2[0] = q.mask_counts[0], counts2[1] = q.mask_counts[1];
+      } else {
+        LC_HIP(lck::launch_speck_probe(a.qZ, a.ldq, K, NP_, speck_active_.p, &pairs, stream_, &rows));
+        LC_HIP(hipMemcpyAsync(counts2, speck_active_.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        LC_HIP(hipStreamSynchronize(stream_));
+      }
       const int active = counts2[0];
       // sorted batches (mode 2) where at most half of the sampled pairs are kept: with more, few batches can be sorted (a row
       // that keeps two quads leaves its batch in order) and the sort's barrier is paid for nothing -- and only below D = 128,
@@ -1259,7 +1349,12 @@ void Context::suffstat(const unsigned char* smask, double* Nk, double* xs, doubl
       const size_t lbytes = lck::ss_list_layout(nchunks, plan.chunk_rows, K).bytes;
       sslists_.reserve(lbytes);
       a.speck_skip = 0;  // (the flag belongs to launch_suffstat's instances)
-      timed(Timed::Suffstat, [&] { LC_HIP(lck::launch_suffstat_lists(a, plan, sslists_.p, lbytes, stream_)); });
+      if (from_masks) {
+        speck_masks_ += 1;
+        timed(Timed::Suffstat,
+              [&] { LC_HIP(lck::launch_suffstat_lists_masks(a, plan, qz_[cur_].qmask.p, NP_ / lck::RG, sslists_.p, lbytes, stream_)); });
+      } else
+        timed(Timed::Suffstat, [&] { LC_HIP(lck::launch_suffstat_lists(a, plan, sslists_.p, lbytes, stream_)); });
     } else
       timed(Timed::Suffstat, [&] { LC_HIP(lck::launch_suffstat(a, plan, stream_)); });
     if (listed)

@@ -174,6 +174,12 @@ class Context {
   int64_t speck_passes_dense() const { return speck_dense_; }
   // ... and how many of the skipping ones took the list route (per-quad row lists, lck::launch_suffstat_lists)
   int64_t speck_passes_lists() const { return speck_lists_; }
+  // E-steps whose statistics pass could take the list route leave kept-quad masks of the responsibilities they store
+  // (lck::EstepLaunch::qmask) and the selector's counts with them: that pass then needs neither the probe's round trip nor
+  // a third reading of qZ for its lists.  On by default; off: every pass probes and builds from qZ.  Same results either way.
+  void set_estep_masks(bool on) { estep_masks_ = on; }
+  // ... and how many list passes were built from such masks
+  int64_t speck_passes_masks() const { return speck_masks_; }
   bool group_sharded() const { return group_sharded_ && distributed(); }
   // a context for a sub-problem of this one: same device, stream and all-reduce hook
   void inherit_comm(const Context& parent) {
@@ -183,6 +189,7 @@ class Context {
     group_sharded_ = parent.group_sharded_;
     skip_zero_ = parent.skip_zero_;
     speck_skip_ = parent.speck_skip_;
+    estep_masks_ = parent.estep_masks_;
   }
 
   // ---- qZ -----------------------------------------------------------------
@@ -395,7 +402,23 @@ class Context {
     // clears hash_ok; qz_clone_to_alt copies it, qz_split_from marks the rows it rewrites.
     DevBuf<int64_t> hash;
     bool hash_ok = false;
+    // Kept-quad masks of what the buffer holds (lck::EstepLaunch::qmask, [quads of mask_K x NP / 16]), written by the E-step
+    // that wrote the buffer, with the two counts of the selector's sample taken from them (lck::launch_speck_probe_masks;
+    // they arrive under that E-step's own synchronisation).  mask_ok: they describe the buffer as it is.
+    // EVERY other writer clears it: ensure_qz() does, and so does each writer that does not come through there
+    // (qz_written()).  qz_clone_to_alt clears the copy's flag; qz_swap_alt needs nothing, the masks belong to the slot.
+    DevBuf<unsigned short> qmask;
+    bool mask_ok = false;
+    int mask_K = 0;
+    int64_t mask_nrg = 0;  // the shape they were written for
+    int mask_counts[2] = {0, 0};
+    int64_t mask_pairs = 0, mask_rows = 0;
   };
+  // a writer of q's buffer that does not come through ensure_qz(): the masks no longer describe it
+  void qz_written(QZ& q);
+#ifdef LC_TEST_HOOKS
+  void verify_qmask(const QZ& q);
+#endif
   void ensure_qz(QZ& q, int K, bool preserve);
   void build_layout(int J, const int64_t* Nj, int D);
   void allreduce(double* dbuf, int64_t count);
@@ -431,6 +454,12 @@ class Context {
   bool speck_skip_ = true;
   int64_t speck_skipping_ = 0, speck_dense_ = 0, speck_lists_ = 0;
   DevBuf<int> speck_active_;
+  bool estep_masks_ = true;
+  int mask_route_K_ = -1, mask_route_DC_ = -1;  // the shape Context::estep last asked the statistics plan's route for, and the answer
+  int64_t mask_route_NP_ = -1;
+  bool mask_route_feat_ = false;
+  int64_t speck_masks_ = 0;
+  PinnedBuf hprobe_;  // the two counts of a probe enqueued behind an E-step (8 bytes), read after its synchronisation
   DevBuf<unsigned char> sslists_;  // the row lists of a list pass (lck::ss_list_layout: about 2 bytes per row and cluster quad)
 
   int J_ = 0, D_ = 0, DP_ = 0;

@@ -41,6 +41,11 @@ __device__ __forceinline__ double mfma4(double a, double b, double c) {
   return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
 }
 
+// The list route's rule for one responsibility: kept unless it is below the speck threshold -- a NaN is kept,
+// the 0.0 of a pad row is not.  ss_list_build_kernel reads it off qZ, the E-step's sweep off the value it is about to store
+// (EstepLaunch::qmask); both have to agree to the bit, so both ask here.
+__device__ __forceinline__ bool speck_keeps(double q) { return !(q < SPECK_TAU); }
+
 // max without the canonicalising self-max hipcc puts in front of fmax (three v_max_f64 per call where one does;
 // the operands here are never signalling NaNs).  NOT for an operand that an MFMA has just written: the hazard recogniser
 // does not look inside inline asm, so the wait states an MFMA result needs before a VALU read are not inserted in front

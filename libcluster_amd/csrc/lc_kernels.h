@@ -90,6 +90,12 @@ struct EstepLaunch {
   int raw = 0;           // 1: stop after writing log q~ (no log-sum-exp, fz/ll untouched)
   int sparse = 0;        // 1: ctab holds -inf entries; waves skip clusters inactive for all their rows
   int lq_lds = 0;        // filled in by launch_estep (EstepPlan::lq_lds)
+  // Kept-quad masks of the responsibilities this launch stores, or nullptr: one 16-bit word per (cluster
+  // quad c, 16-row group g) at qmask[c * nrg + g], bit i = "row 16 g + i keeps quad c" = !(q < SPECK_TAU) for any of the
+  // quad's clusters < K, taken on the q that is stored (a NaN is kept, a pad row's 0.0 is not) -- ss_list_build_kernel's
+  // rule to the letter.  [(K + 3) / 4 x nrg], every word written.  Only the instances with EstepPlan::emits take it
+  // (launch_estep refuses the pointer on any other launch).
+  unsigned short* qmask = nullptr;
 };
 // ONE decision per launch, read by estep_grid and by every launcher: a function of the WHOLE launch -- DP, DC, K, raw,
 // sparse, nrg have to be set (D = 64 / 80 run four row groups per wave where the log q~ table fits in LDS: other rows per block)
@@ -100,6 +106,7 @@ struct EstepPlan {
   bool four_groups;     // the four-row-group instance of D = 64 / 80
   int DC, lq_lds;       // the active-width instance; log q~ waits in LDS (four row groups per wave, small K) instead of in qZ
   size_t lds_bytes;     // dynamic LDS of the launch
+  bool emits = false;   // the instance can write EstepLaunch::qmask (dense, normalising, DP = 64 with DC 64 or 56; three or four row groups per wave)
 };
 EstepPlan estep_plan(const EstepLaunch& a);
 int64_t estep_grid(const EstepLaunch& a);  // estep_plan(a).grid
@@ -240,6 +247,19 @@ bool speck_lists_enabled();                   // false in a build with -DLC_FT_S
 // GEMM's, a width without an instance and a buffer that is too small.  _build: the lists alone; the other: lists + sums.
 hipError_t launch_suffstat_list_build(const SuffstatLaunch& a, const SuffstatPlan& p, void* lists, size_t bytes, hipStream_t stream);
 hipError_t launch_suffstat_lists(const SuffstatLaunch& a, const SuffstatPlan& p, void* lists, size_t bytes, hipStream_t stream);
+// The same lists and the same probe counts from the kept-quad masks an E-step left behind (EstepLaunch::qmask: [nq x nrg]
+// 16-bit words, nrg = a.NP / 16) instead of from qZ, which is not read at all: one block per (row chunk, cluster quad)
+// walks the chunk's bit range of the quad -- addressed by bit, a chunk need not start on a word --, popcounts give the
+// places, no atomics.  Same layout, lengths and entries as launch_suffstat_list_build / the same two counts, *pairs and
+// *rows as launch_speck_probe, whatever the masks hold.
+hipError_t launch_suffstat_list_build_masks(const SuffstatLaunch& a, const SuffstatPlan& p, const unsigned short* qmask, int64_t nrg,
+                                            void* lists, size_t bytes, hipStream_t stream);
+hipError_t launch_suffstat_lists_masks(const SuffstatLaunch& a, const SuffstatPlan& p, const unsigned short* qmask, int64_t nrg,
+                                       void* lists, size_t bytes, hipStream_t stream);
+hipError_t launch_speck_probe_masks(const unsigned short* qmask, int64_t nrg, int K, int64_t NP, int* active, int64_t* pairs,
+                                    hipStream_t stream, int64_t* rows = nullptr);
+// the masks of a qZ buffer by the rule alone (tests: LC_TEST_VERIFY_QMASK recomputes what a pass is about to trust)
+hipError_t launch_qmask_from_qz(const double* qZ, int64_t ldq, int K, int64_t nrg, unsigned short* qmask, hipStream_t stream);
 // SuffstatLaunch::speck_skip of a pass that skips: 2 (sorted batches); 1 in a build with -DLC_FT_SPECK_SORT=0 (decided in
 // lc_kernels_suffstat.hip, a device source, so that tools/variants.py can build the unsorted rule for a same-visit A/B)
 int speck_skip_mode();

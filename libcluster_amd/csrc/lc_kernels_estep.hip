@@ -29,6 +29,10 @@
 namespace lck {
 
 constexpr int ES_PF = 4;  // LDS reads in flight ahead of their use (2...10 are within 1 %)
+// -DLC_ESTEP_QMASK=0 (tools/variants.py): no instance emits kept-quad masks -- the statistics pass builds its lists from qZ
+#ifndef LC_ESTEP_QMASK
+#define LC_ESTEP_QMASK 1
+#endif
 
 // ===========================================================================
 // E-step
@@ -50,14 +54,28 @@ constexpr int ES_PF = 4;  // LDS reads in flight ahead of their use (2...10 are 
 // sum exp(x-max), log+max, exp(x - logZ).
 // blocks per CU the register budget is set for.  D = 64: three row groups per wave (96 VGPRs of X fragments) at
 // three waves per SIMD measured 22.2 ms against 22.6 for four row groups at two waves per SIMD (N=10M, K=32).
+// EMIT, four row groups per wave (lane (lo4, hi) owns row lo4 of row group rg0 + hi; called by the lanes whose row group
+// exists, the others add no bit): quarter hi of the ballot is the word of row group rg0 + hi
+__device__ __forceinline__ void emit_rowlanes(const EstepLaunch& a, bool keep, int quad, int64_t rg0, int lane) {
+  const unsigned long long b = __ballot(keep);
+  if ((lane & 15) == 0) a.qmask[(int64_t)quad * a.nrg + rg0 + (lane >> 4)] = (unsigned short)((b >> (lane & 48)) & 0xffffull);
+}
 template <int DP, int R>
 struct EstepOcc { static constexpr int BLOCKS = DP == 64 && R == 3 ? 3 : 2; };
 
 // DC <= DP: the active width (estep_active_width, lc_kernels.h) -- the row stride of X stays DP, the tile rows walked and
 // the parameter record are those of DC columns.
-template <int DP, int DC, int R, int WAVES, bool SPARSE>
+// EMIT: the instance writes the kept-quad masks of what it stores (EstepLaunch::qmask, never null here): one iteration kb of
+// the second pass of the sweep IS one cluster quad (k = kb + hi), so per (kb, r) one compare on the q that is stored
+// (speck_keeps, the list builder's rule), one ballot and the fold of its four 16-lane quarters; lane 0 stores the word.
+// Four row groups per wave: a lane owns a row and walks all k -- four k ORed into a bit, one ballot per quad is the four
+// words of the wave's row groups (emit_rowlanes).
+// The statistics pass that follows builds its row lists from these 2 bytes per (16 rows, quad) instead of re-reading qZ
+// (DESIGN 4.2b).  Only the dense D = 64 instances exist with EMIT; every other instance is the code it was.
+template <int DP, int DC, int R, int WAVES, bool SPARSE, bool EMIT = false>
 __global__ void __launch_bounds__(WAVES * 64, (EstepOcc<DP, R>::BLOCKS)) estep_kernel(EstepLaunch a) {
   static_assert(DC % 4 == 0 && DC <= DP && DC > DP - 16, "active width");
+  static_assert(!EMIT || !SPARSE, "masks: dense launches");
   constexpr int NT = DC / 4;
   constexpr int NTILES = NT * (NT + 1) / 2;
   constexpr int NREAD = NTILES + NT;  // LDS reads per cluster
@@ -362,11 +380,28 @@ __global__ void __launch_bounds__(WAVES * 64, (EstepOcc<DP, R>::BLOCKS)) estep_k
           lql[k * NTHR + tid] = e;
         }
         const double inv = rcp_pos(s);
+        if constexpr (EMIT) {  // (quad by quad: the same stores in the same order, a ballot behind every fourth)
+          for (int kb = 0; kb < K; kb += 4) {
+            bool kq = false;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const int k = kb + i;
+              if (k < K) {
+                double q = lql[k * NTHR + tid] * inv;
+                if (!myrow) q = 0.0;
+                qp[(int64_t)k * a.ldq] = q;
+                kq = kq || speck_keeps(q);
+              }
+            }
+            emit_rowlanes(a, kq, kb >> 2, rg0, lane);
+          }
+        } else {
 #pragma unroll 8
         for (int k = 0; k < K; ++k) {
           double q = lql[k * NTHR + tid] * inv;
           if (!myrow) q = 0.0;
           qp[(int64_t)k * a.ldq] = q;
+        }
         }
       }
       fz = (myok && myrow) ? log(s) + mymx : 0.0;
@@ -376,6 +411,7 @@ __global__ void __launch_bounds__(WAVES * 64, (EstepOcc<DP, R>::BLOCKS)) estep_k
       for (int k = 0; k < K; ++k) s += exp_nonpos((lqm ? lql[k * NTHR + tid] : qp[(int64_t)k * a.ldq]) - mymx, etab);
     }
     const double logZ = log(s) + mymx;
+    [[maybe_unused]] bool kq = false;
     for (int k = 0; k < K; ++k) {
       double ll = 0.0;
       if (myok) {
@@ -383,6 +419,10 @@ __global__ void __launch_bounds__(WAVES * 64, (EstepOcc<DP, R>::BLOCKS)) estep_k
         double q = exp_nonpos(lq - logZ, etab);
         if (!myrow) q = 0.0;
         qp[(int64_t)k * a.ldq] = q;
+        if constexpr (EMIT) {
+          kq = kq || speck_keeps(q);
+          if ((k & 3) == 3 || k == K - 1) emit_rowlanes(a, kq, k >> 2, rg0, lane), kq = false;
+        }
         if (a.ll_part && q > 0.0) ll = q * (lq - a.ctab[(int64_t)mygrp * K + k]);
       }
       if (a.ll_part) {  // wave-uniform
@@ -417,6 +457,15 @@ __global__ void __launch_bounds__(WAVES * 64, (EstepOcc<DP, R>::BLOCKS)) estep_k
           double q = exp_nonpos(lq - logZ[r], etab);
           if (!rowok[r]) q = 0.0;
           *qp = q;
+          if constexpr (EMIT) {
+            // (the lanes with k >= K are not here and add no bit; lane 0 holds k = kb < K and always is)
+            const unsigned long long b = __ballot(speck_keeps(q));
+            const unsigned w = (unsigned)(b | (b >> 16) | (b >> 32) | (b >> 48)) & 0xffffu;
+            // the words of the wave's row groups: a wave-uniform address in SGPRs (computed from rg0 it is a VGPR pair that
+            // hipcc keeps alive across the cluster loop, whose ring then loses the register it reads ahead into)
+            unsigned short* mw = a.qmask + ((int64_t)blockIdx.x * WAVES + __builtin_amdgcn_readfirstlane(wave)) * R;
+            if (lane == 0) mw[(int64_t)(kb >> 2) * a.nrg + r] = (unsigned short)w;
+          }
           if (a.ll_part && q > 0.0) ll += q * (lq - a.ctab[(int64_t)grp[r] * K + k]);
         }
       }
@@ -800,7 +849,7 @@ static size_t estep_lds_base(int DC, int K, int R, int WAVES) {
 // (0.82 -> 0.85 of the peak), K = 20 5.31 -> 5.19; K = 4 loses 2 % and keeps three (gpurun_out/r06r).  Dense, normalising
 // launches only.  ONE decision for the instance, its LDS and the grid the caller sizes its partial sums by (estep_grid).
 EstepPlan estep_plan(const EstepLaunch& a) {
-  EstepPlan p{false, 0, -1, false, a.DC > 0 ? a.DC : a.DP, 0, 0};
+  EstepPlan p{false, 0, -1, false, a.DC > 0 ? a.DC : a.DP, 0, 0, false};
   const int DP = a.DP, DC = p.DC;
   auto finish = [&](bool ok, int rows_per_block, size_t lds_bytes) {
     const int64_t rgpb = rows_per_block / RG;
@@ -821,16 +870,18 @@ EstepPlan estep_plan(const EstepLaunch& a) {
   // the active-width instances: DP; DP - 8 from 32 columns on (four row groups: those two only); DP - 4 and DP - 12 at 32 and 48
   const bool ok = DC == DP || (DP >= 32 && DC == DP - 8) || ((DP == 32 || DP == 48) && (DC == DP - 4 || DC == DP - 12));
   p.lq_lds = lq_fits(R, WAVES) ? 1 : 0;
+  p.emits = LC_ESTEP_QMASK != 0 && ok && DP == 64 && (DC == 64 || DC == 56) && !a.sparse && !a.raw;
   return finish(ok, R * WAVES * RG, estep_lds_base(DC, a.K, R, WAVES) + (p.lq_lds ? (size_t)a.K * WAVES * 64 * sizeof(double) : 0));
 }
 int64_t estep_grid(const EstepLaunch& a) { return estep_plan(a).grid; }
 
-template <int DP, int DC, bool SPARSE, int R = estep_cfg_r(DP), int WAVES = estep_cfg_waves(DP)>
+template <int DP, int DC, bool SPARSE, int R = estep_cfg_r(DP), int WAVES = estep_cfg_waves(DP), bool EMIT = false>
 static hipError_t launch_estep_s(const EstepLaunch& a, const EstepPlan& p, hipStream_t stream) {
   if (p.DC != DC || p.rows_per_block != R * WAVES * RG) return hipErrorInvalidValue;  // (the instance is the plan's)
+  if (EMIT != (a.qmask != nullptr) || (EMIT && !p.emits)) return hipErrorInvalidValue;
   EstepLaunch b = a;
   b.lq_lds = p.lq_lds;  // log q~ stays in LDS until the normalisation
-  auto kern = estep_kernel<DP, DC, R, WAVES, SPARSE>;
+  auto kern = estep_kernel<DP, DC, R, WAVES, SPARSE, EMIT>;
   static LdsGrant grant;  // largest dynamic-LDS size already granted, per device
   if (hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(kern), p.lds_bytes, grant); e != hipSuccess) return e;
   if (p.grid <= 0) return hipSuccess;
@@ -840,6 +891,16 @@ static hipError_t launch_estep_s(const EstepLaunch& a, const EstepPlan& p, hipSt
 
 template <int DP>
 static hipError_t launch_estep_t(const EstepLaunch& a, const EstepPlan& p, hipStream_t stream) {
+  if constexpr (DP == 64) {  // the emitting instances: the launch asks for masks and the plan's instance has them
+    if (a.qmask && p.emits) {
+      if (p.four_groups)
+        return p.DC == DP - 8 ? launch_estep_s<DP, DP - 8, false, 4, 4, true>(a, p, stream)
+                              : launch_estep_s<DP, DP, false, 4, 4, true>(a, p, stream);
+      constexpr int R = estep_cfg_r(DP), WAVES = estep_cfg_waves(DP);
+      return p.DC == DP - 8 ? launch_estep_s<DP, DP - 8, false, R, WAVES, true>(a, p, stream)
+                            : launch_estep_s<DP, DP, false, R, WAVES, true>(a, p, stream);
+    }
+  }
   if constexpr (DP == 64 || DP == 80) {
     if (p.four_groups)
       return p.DC == DP - 8 ? launch_estep_s<DP, DP - 8, false, 4, 4>(a, p, stream) : launch_estep_s<DP, DP, false, 4, 4>(a, p, stream);
@@ -857,6 +918,7 @@ static hipError_t launch_estep_t(const EstepLaunch& a, const EstepPlan& p, hipSt
 hipError_t launch_estep(const EstepLaunch& a, hipStream_t stream) {
   const EstepPlan p = estep_plan(a);
   if (!p.ok) return hipErrorInvalidValue;  // (a width or an active width without an instance: nothing falls through to another one)
+  if (a.qmask && !p.emits) return hipErrorInvalidValue;  // (masks are written by the emitting instances or not asked for)
   if (a.DP > 128) return launch_estep_wide(a, p, stream);  // -inf entries of ctab need no special handling there
   switch (a.DP) {
     case 16: return launch_estep_t<16>(a, p, stream);

@@ -1061,6 +1061,22 @@ __global__ void __launch_bounds__(64 * ft_waves(DP), 2) suffstat_feat_kernel(Suf
 // launch_speck_probe: one thread per (sampled step, cluster quad), one atomic per wave
 // (a step's quads sit in nqp consecutive lanes, nqp = the power of two >= nq: lanes c >= nq idle.  The second count -- rows
 // that keep exactly one quad -- is a popcount over those lanes of the row's "kept" ballot; nqp > 64: not counted)
+// rk: bit i = row i of this thread's (step, quad c) keeps a value of the quad -> the two counts (all lanes of the block call)
+__device__ __forceinline__ void speck_probe_count(unsigned rk, int c, int nqp, int* active) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long b = __ballot(rk != 0);
+  if (lane == 0 && b != 0) atomicAdd(active, __popcll(b));
+  if (nqp <= 64) {
+    const unsigned long long grp = (nqp == 64 ? ~0ull : ((1ull << nqp) - 1ull)) << (lane & ~(nqp - 1));
+    int single = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned long long br = __ballot((rk >> i) & 1u);
+      single += __popcll(__ballot(c == 0 && __popcll(br & grp) == 1));
+    }
+    if (lane == 0 && single != 0) atomicAdd(active + 1, single);
+  }
+}
 __global__ void __launch_bounds__(256) speck_probe_kernel(const double* qZ, int64_t ldq, int K, int64_t stride, int nsteps, int nq,
                                                            int nqp, int* active) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1079,35 +1095,56 @@ __global__ void __launch_bounds__(256) speck_probe_kernel(const double* qZ, int6
       }
     }
   }
-  const int lane = threadIdx.x & 63;
-  const unsigned long long b = __ballot(rk != 0);
-  if (lane == 0 && b != 0) atomicAdd(active, __popcll(b));
-  if (nqp <= 64) {
-    const unsigned long long grp = (nqp == 64 ? ~0ull : ((1ull << nqp) - 1ull)) << (lane & ~(nqp - 1));
-    int single = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned long long br = __ballot((rk >> i) & 1u);
-      single += __popcll(__ballot(c == 0 && __popcll(br & grp) == 1));
-    }
-    if (lane == 0 && single != 0) atomicAdd(active + 1, single);
-  }
+  speck_probe_count(rk, c, nqp, active);
 }
-hipError_t launch_speck_probe(const double* qZ, int64_t ldq, int K, int64_t NP, int* active, int64_t* pairs, hipStream_t stream,
-                              int64_t* rows) {
+// the same sample read off the kept-quad masks of an E-step (EstepLaunch::qmask): a step's four rows are four bits of one
+// 16-bit word (a step starts on a multiple of four rows), bit i of rk what speck_probe_kernel computes from qZ
+__global__ void __launch_bounds__(256) speck_probe_masks_kernel(const unsigned short* __restrict__ qmask, int64_t nrg, int64_t stride,
+                                                                 int nsteps, int nq, int nqp, int* active) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int c = (int)(t % nqp);
+  unsigned rk = 0;
+  if (t / nqp < nsteps && c < nq) {
+    const int64_t row = 4 * stride * (t / nqp);
+    rk = ((unsigned)qmask[(int64_t)c * nrg + (row >> 4)] >> (unsigned)(row & 15)) & 0xfu;
+  }
+  speck_probe_count(rk, c, nqp, active);
+}
+// the sample of both probes: steps looked at, their stride, quads and quads rounded up to a power of two; false: nothing to look at
+static bool speck_probe_sample(int K, int64_t NP, int64_t* pairs, int64_t* rows, int* nsteps, int64_t* stride, int* nq, int* nqp) {
   const int64_t steps = NP / 4;
   *pairs = 0;
   if (rows) *rows = 0;
+  if (steps < 1 || K < 1) return false;
+  *nsteps = (int)(steps < SPECK_PROBE_STEPS ? steps : SPECK_PROBE_STEPS), *nq = (K + 3) / 4;
+  *stride = steps / *nsteps;  // (the last sampled step: stride * (nsteps - 1) < steps)
+  *nqp = 1;
+  while (*nqp < *nq) *nqp *= 2;
+  *pairs = (int64_t)*nsteps * *nq;
+  if (rows && *nqp <= 64) *rows = 4 * (int64_t)*nsteps;
+  return true;
+}
+hipError_t launch_speck_probe(const double* qZ, int64_t ldq, int K, int64_t NP, int* active, int64_t* pairs, hipStream_t stream,
+                              int64_t* rows) {
+  int nsteps = 0, nq = 0, nqp = 0;
+  int64_t stride = 0;
+  const bool any = speck_probe_sample(K, NP, pairs, rows, &nsteps, &stride, &nq, &nqp);
   if (hipError_t e = hipMemsetAsync(active, 0, 2 * sizeof(int), stream); e != hipSuccess) return e;
-  if (steps < 1 || K < 1) return hipSuccess;
-  const int nsteps = (int)(steps < SPECK_PROBE_STEPS ? steps : SPECK_PROBE_STEPS), nq = (K + 3) / 4;
-  const int64_t stride = steps / nsteps;  // (the last sampled step: stride * (nsteps - 1) < steps)
-  int nqp = 1;
-  while (nqp < nq) nqp *= 2;
-  *pairs = (int64_t)nsteps * nq;
-  if (rows && nqp <= 64) *rows = 4 * (int64_t)nsteps;
+  if (!any) return hipSuccess;
   hipLaunchKernelGGL(speck_probe_kernel, dim3((unsigned)(((int64_t)nsteps * nqp + 255) / 256)), dim3(256), 0, stream, qZ, ldq, K, stride,
                      nsteps, nq, nqp, active);
+  return hipGetLastError();
+}
+hipError_t launch_speck_probe_masks(const unsigned short* qmask, int64_t nrg, int K, int64_t NP, int* active, int64_t* pairs,
+                                    hipStream_t stream, int64_t* rows) {
+  int nsteps = 0, nq = 0, nqp = 0;
+  int64_t stride = 0;
+  if (!qmask || !active || !pairs || nrg * RG < NP) return hipErrorInvalidValue;
+  const bool any = speck_probe_sample(K, NP, pairs, rows, &nsteps, &stride, &nq, &nqp);
+  if (hipError_t e = hipMemsetAsync(active, 0, 2 * sizeof(int), stream); e != hipSuccess) return e;
+  if (!any) return hipSuccess;
+  hipLaunchKernelGGL(speck_probe_masks_kernel, dim3((unsigned)(((int64_t)nsteps * nqp + 255) / 256)), dim3(256), 0, stream, qmask, nrg,
+                     stride, nsteps, nq, nqp, active);
   return hipGetLastError();
 }
 
@@ -1255,7 +1292,7 @@ __global__ void __launch_bounds__(256) ss_list_build_kernel(const double* __rest
 #pragma unroll
         for (int i = 0; i < 32; ++i) {
           const int k = 4 * (q0 + c8) + i;
-          if (valid && k < K && !(v[i] < SPECK_TAU)) m |= 1u << (c8 + i / 4);
+          if (valid && k < K && speck_keeps(v[i])) m |= 1u << (c8 + i / 4);
         }
       }
       int mycnt = 0;
@@ -1535,6 +1572,110 @@ hipError_t launch_suffstat_lists(const SuffstatLaunch& a, const SuffstatPlan& p,
   SsListLayout lay;
   if (hipError_t e = ss_list_check(a, p, lists, bytes, &lay); e != hipSuccess) return e;
   if (hipError_t e = launch_suffstat_list_build(a, p, lists, bytes, stream); e != hipSuccess) return e;
+  const bool narrow = a.DC == 56;
+  if (lay.wide) return narrow ? launch_ss_list_i<64, 56, unsigned>(a, lay, lists, stream) : launch_ss_list_i<64, 64, unsigned>(a, lay, lists, stream);
+  return narrow ? launch_ss_list_i<64, 56, unsigned short>(a, lay, lists, stream)
+                : launch_ss_list_i<64, 64, unsigned short>(a, lay, lists, stream);
+}
+
+// ---- the lists from the kept-quad masks of the E-step that wrote qZ (EstepLaunch::qmask) ------------------------------------
+// One block per (row chunk, cluster quad) walks the chunk's bits of the quad 4096 rows at a time: thread t takes the sixteen
+// rows from r0 + 16 t on -- a chunk starts on a multiple of 4 rows, not of 16, so the sixteen bits come out of two words --,
+// a popcount per thread, a scan over the wave and the four waves' totals through LDS give every kept row its place: ascending
+// row order, no atomics, and qZ is not read (10 MB of masks against 2.56 GB at the north star).
+template <typename IT>
+__global__ void __launch_bounds__(256) ss_list_build_masks_kernel(const unsigned short* __restrict__ qmask, int64_t nrg, int64_t NP,
+                                                                   int64_t chunk_rows, int nq, int* __restrict__ lens, IT* __restrict__ ent) {
+  __shared__ int wcnt[2][4];
+  const int chunk = blockIdx.x / nq, c = blockIdx.x % nq, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t r0 = (int64_t)chunk * chunk_rows;
+  const int64_t r1 = (r0 + chunk_rows) < NP ? (r0 + chunk_rows) : NP;
+  if (r0 >= r1) {
+    if (tid == 0) lens[blockIdx.x] = 0;
+    return;
+  }
+  const unsigned short* mq = qmask + (int64_t)c * nrg;
+  IT* seg = ent + (int64_t)blockIdx.x * chunk_rows;
+  int base = 0, par = 0;
+  for (int64_t t0 = r0; t0 < r1; t0 += 4096, par ^= 1) {
+    const int64_t row = t0 + 16 * tid;
+    unsigned m = 0;
+    if (row < r1) {  // (row < NP <= 16 nrg: the first word exists; the second one only where it is needed)
+      const int64_t w = row >> 4;
+      const unsigned sh = (unsigned)(row & 15);
+      const unsigned lo = mq[w], hi = sh != 0 && w + 1 < nrg ? mq[w + 1] : 0u;
+      m = ((lo | (hi << 16)) >> sh) & 0xffffu;
+      if (r1 - row < 16) m &= (1u << (unsigned)(r1 - row)) - 1u;
+    }
+    const int cnt = __popc(m);
+    int inc = cnt;  // inclusive scan over the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(inc, d);
+      if (lane >= d) inc += up;
+    }
+    if (lane == 63) wcnt[par][wave] = inc;
+    __syncthreads();  // (one barrier per tile: the counts alternate between two buffers)
+    int before = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int n = wcnt[par][w];
+      before += w < wave ? n : 0;
+      tot += n;
+    }
+    int at = base + before + inc - cnt;
+    while (m) {
+      const int i = __ffs((int)m) - 1;
+      m &= m - 1;
+      seg[at++] = (IT)(row - r0 + i);
+    }
+    base += tot;
+  }
+  if (tid == 0) lens[blockIdx.x] = base;
+}
+// the rule itself: the masks of what a qZ buffer holds (one thread per (row, quad); a wave's ballot is four words)
+__global__ void __launch_bounds__(256) qmask_from_qz_kernel(const double* __restrict__ qZ, int64_t ldq, int K, int64_t nrg,
+                                                             unsigned short* __restrict__ qmask) {
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int c = blockIdx.y, lane = threadIdx.x & 63;
+  bool keep = false;
+  if (row < nrg * RG) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int k = 4 * c + i;
+      if (k < K && speck_keeps(qZ[(int64_t)k * ldq + row])) keep = true;
+    }
+  }
+  const unsigned long long b = __ballot(keep);
+  if ((lane & 15) == 0 && row < nrg * RG) qmask[(int64_t)c * nrg + (row >> 4)] = (unsigned short)((b >> lane) & 0xffffull);
+}
+hipError_t launch_qmask_from_qz(const double* qZ, int64_t ldq, int K, int64_t nrg, unsigned short* qmask, hipStream_t stream) {
+  if (!qZ || !qmask || K < 1 || nrg < 1 || ldq < nrg * RG || (K + 3) / 4 > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(qmask_from_qz_kernel, dim3((unsigned)((nrg * RG + 255) / 256), (unsigned)((K + 3) / 4)), dim3(256), 0, stream, qZ, ldq,
+                     K, nrg, qmask);
+  return hipGetLastError();
+}
+hipError_t launch_suffstat_list_build_masks(const SuffstatLaunch& a, const SuffstatPlan& p, const unsigned short* qmask, int64_t nrg,
+                                            void* lists, size_t bytes, hipStream_t stream) {
+  SsListLayout lay;
+  if (hipError_t e = ss_list_check(a, p, lists, bytes, &lay); e != hipSuccess) return e;
+  if (!qmask || nrg * RG < a.NP) return hipErrorInvalidValue;
+  int* lens = static_cast<int*>(lists);
+  void* ent = static_cast<char*>(lists) + lay.ent_off;
+  const dim3 grid((unsigned)(a.nchunks * lay.nq));
+  if (lay.wide)
+    hipLaunchKernelGGL(ss_list_build_masks_kernel<unsigned>, grid, dim3(256), 0, stream, qmask, nrg, a.NP, a.chunk_rows, lay.nq, lens,
+                       static_cast<unsigned*>(ent));
+  else
+    hipLaunchKernelGGL(ss_list_build_masks_kernel<unsigned short>, grid, dim3(256), 0, stream, qmask, nrg, a.NP, a.chunk_rows, lay.nq, lens,
+                       static_cast<unsigned short*>(ent));
+  return hipGetLastError();
+}
+hipError_t launch_suffstat_lists_masks(const SuffstatLaunch& a, const SuffstatPlan& p, const unsigned short* qmask, int64_t nrg,
+                                       void* lists, size_t bytes, hipStream_t stream) {
+  SsListLayout lay;
+  if (hipError_t e = launch_suffstat_list_build_masks(a, p, qmask, nrg, lists, bytes, stream); e != hipSuccess) return e;
+  if (hipError_t e = ss_list_check(a, p, lists, bytes, &lay); e != hipSuccess) return e;
   const bool narrow = a.DC == 56;
   if (lay.wide) return narrow ? launch_ss_list_i<64, 56, unsigned>(a, lay, lists, stream) : launch_ss_list_i<64, 64, unsigned>(a, lay, lists, stream);
   return narrow ? launch_ss_list_i<64, 56, unsigned short>(a, lay, lists, stream)

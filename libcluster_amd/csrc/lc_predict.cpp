@@ -63,6 +63,7 @@ void Context::predict_rows(int K, int Kp, const double* c, const double* pc, con
   LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ and ptab_ are free again)
   qz_[cur_].K = K;
   qz_[cur_].hash_ok = false;
+  qz_written(qz_[cur_]);
   pred_vb_ = true;
   pred_logp_ = pred_logp_ || Kp > 0;
 }
@@ -162,6 +163,7 @@ void Context::predict_cond(int Kp, int Db, const double* tt, const double* ps, c
   LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ is free again; ptab_ keeps the tables for predict_cond_var)
   qz_[cur_].K = Kp;
   qz_[cur_].hash_ok = false;
+  qz_written(qz_[cur_]);
   pred_cond_ = Db;
 }
 
@@ -506,6 +508,7 @@ void Context::predict_holes(int Kp, const double* tt, const double* ps, const do
   LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ and ptab_ are free again)
   qz_[cur_].K = Kp;
   qz_[cur_].hash_ok = false;
+  qz_written(qz_[cur_]);
   dcache_invalidate();  // (the observations changed)
   pred_holes_ = true;
   pred_holes_var_ = gnu != nullptr;

@@ -911,6 +911,118 @@ LC_HOOK lcx_test_suffstat_lists(const double* X, int DP, int DC, i64 NP, const d
   return 0;
 }
 
+// ---- kept-quad masks (EstepLaunch::qmask; tests/test_gpu_estep_masks.py binds these) -------------------------------------------
+// lc_test_estep with a mask buffer: qmask (io) [nmask >= quads of K x nrg] or null -- the launcher refuses the pointer on a
+// launch whose plan does not emit (hipErrorInvalidValue comes back as such).  Everything else as lc_test_estep.
+LC_HOOK lcx_test_estep_masks(const double* X, int DP, int DC, i64 nrg, const double* params, const double* ctab, int J, const int* rginfo,
+                             i64 nrows, int K, double* qZ, int Kbuf, i64 ldq, double* fz_part, i64 nfz, double* ll_part, i64 nll,
+                             unsigned short* qmask, i64 nmask, int* emits) {
+  if (!X || !params || !ctab || !qZ || !fz_part || !emits || K < 1 || K > 4096 || Kbuf < K || Kbuf > 8192 || J < 1 || J > (1 << 20)) return -1;
+  if (nrg < 1 || nrg > HOT_MAX_NRG || ldq < nrg * RG || !gw_width_ok(DP, DC)) return -1;
+  if (rginfo ? !rginfo_ok(rginfo, nrg, J) : (J != 1 || nrows < 0 || nrows > nrg * RG)) return -1;
+  if (qmask && nmask < (i64)((K + 3) / 4) * nrg) return -1;
+  lck::EstepLaunch a{};
+  a.DP = DP;
+  a.DC = DC;
+  a.K = K;
+  a.nrg = nrg;
+  a.nrows = nrows;
+  a.ldq = ldq;
+  const lck::EstepPlan p = lck::estep_plan(a);
+  if (!p.ok || p.grid < 1 || p.lds_bytes > HOT_LDS_LIMIT) return -1;
+  if (nfz < p.grid || (ll_part && nll < p.grid * K)) return -1;
+  *emits = p.emits ? 1 : 0;
+  Scope s;
+  a.X = s.in(X, (size_t)(nrg * RG) * DP);
+  a.params = s.in(params, (size_t)K * (size_t)lck::estep_pstride(DP, p.DC));
+  a.ctab = s.in(ctab, (size_t)J * K);
+  a.rginfo = rginfo ? s.in(rginfo, (size_t)nrg) : nullptr;
+  a.qZ = s.io(qZ, (size_t)Kbuf * (size_t)ldq);
+  a.fz_part = s.io(fz_part, (size_t)nfz);
+  a.ll_part = ll_part ? s.io(ll_part, (size_t)nll) : nullptr;
+  a.qmask = qmask ? s.io(qmask, (size_t)nmask) : nullptr;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_estep(a, nullptr));
+}
+
+// The two list builders side by side.  qZ [K x ldq]; qmask [quads x NP / 16] (the masks of that qZ: the caller's business);
+// chunk_rows > 0: that many rows per chunk (a multiple of 4) and as many chunks as cover NP, instead of the plan's.
+// which = 0: launch_suffstat_list_build (reads qZ), 1: launch_suffstat_list_build_masks (reads qmask).  out [2] = nchunks,
+// chunk_rows; lens_out / ent_out as lcx_test_suffstat_lists hands them back; -2: a length outside its segment.
+LC_HOOK lcx_test_list_build(int which, const double* qZ, int DC, i64 NP, int K, i64 ldq, const unsigned short* qmask, i64 chunk_rows,
+                            i64* out, int* lens_out, i64 nlens, int* ent_out, i64 nent) {
+  const int DP = 64;
+  if (!qZ || !qmask || !out || !lens_out || !ent_out || K < 1 || K > 4096 || !gw_width_ok(DP, DC)) return -1;
+  if (NP < RG || NP % RG || NP > HOT_MAX_NRG * RG || ldq < NP || chunk_rows < 0 || chunk_rows % 4) return -1;
+  lck::SuffstatPlan p = lck::suffstat_plan(DP, DC, NP, K, lck::SS_DENSE);
+  if (chunk_rows > 0) {
+    p.chunk_rows = chunk_rows;
+    p.nchunks = (int)((NP + chunk_rows - 1) / chunk_rows);
+  }
+  if (p.nchunks < 1 || p.chunk_rows < 4 || (i64)p.nchunks * p.chunk_rows < NP) return -1;
+  out[0] = p.nchunks, out[1] = p.chunk_rows;
+  const lck::SsListLayout lay = lck::ss_list_layout(p.nchunks, p.chunk_rows, K);
+  const i64 nseg = (i64)p.nchunks * lay.nq, nrg = NP / RG;
+  if (nlens < nseg || nent < nseg * p.chunk_rows) return -1;
+  Scope s;
+  lck::SuffstatLaunch a{};
+  a.DP = DP;
+  a.DC = DC;
+  a.X = s.scratch<double>(16);  // (the builders never read X; the launchers' checks want a pointer)
+  a.NP = NP;
+  a.qZ = s.in(qZ, (size_t)K * (size_t)ldq);
+  a.ldq = ldq;
+  a.K = K;
+  a.mode = lck::SS_DENSE;
+  a.nchunks = p.nchunks;
+  a.KR = p.KR;
+  a.chunk_rows = p.chunk_rows;
+  const unsigned short* dmask = s.in(qmask, (size_t)lay.nq * (size_t)nrg);
+  unsigned char* lists = s.scratch<unsigned char>(lay.bytes);
+  if (!s.ok()) return s.finish(hipSuccess);
+  hipError_t e = hipMemset(lists, 0xff, lay.bytes);
+  if (e == hipSuccess)
+    e = which ? lck::launch_suffstat_list_build_masks(a, p, dmask, nrg, lists, lay.bytes, nullptr)
+              : lck::launch_suffstat_list_build(a, p, lists, lay.bytes, nullptr);
+  const int rc = s.finish(e);
+  if (rc != 0) return rc;
+  std::vector<unsigned char> raw(lay.bytes);
+  if (hipMemcpy(raw.data(), lists, lay.bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  const int* lens = reinterpret_cast<const int*>(raw.data());
+  for (i64 g = 0; g < nseg; ++g)
+    if (lens[g] < 0 || lens[g] > p.chunk_rows) return -2;
+  for (i64 g = 0; g < nseg; ++g) {
+    lens_out[g] = lens[g];
+    for (int i = 0; i < lens[g]; ++i) {
+      const size_t at = (size_t)g * (size_t)p.chunk_rows + (size_t)i;
+      ent_out[at] = lay.wide ? (int)reinterpret_cast<const unsigned*>(raw.data() + lay.ent_off)[at]
+                             : (int)reinterpret_cast<const unsigned short*>(raw.data() + lay.ent_off)[at];
+    }
+  }
+  return 0;
+}
+
+// The two probes side by side: which = 0: launch_speck_probe on qZ [K x ldq], 1: launch_speck_probe_masks on qmask [quads x NP / 16].
+// out [4] = kept pairs, one-quad rows, pairs looked at, rows looked at.
+LC_HOOK lcx_test_speck_probe(int which, const double* qZ, i64 ldq, int K, i64 NP, const unsigned short* qmask, i64* out) {
+  if (!qZ || !qmask || !out || K < 1 || K > 4096 || NP < RG || NP % RG || NP > HOT_MAX_NRG * RG || ldq < NP || ldq % 2) return -1;
+  const i64 nrg = NP / RG;
+  Scope s;
+  const double* dq = s.in(qZ, (size_t)K * (size_t)ldq);
+  const unsigned short* dm = s.in(qmask, (size_t)((K + 3) / 4) * (size_t)nrg);
+  int* act = s.scratch<int>(2);
+  if (!s.ok()) return s.finish(hipSuccess);
+  int64_t pairs = 0, rows = 0;
+  const hipError_t e = which ? lck::launch_speck_probe_masks(dm, nrg, K, NP, act, &pairs, nullptr, &rows)
+                             : lck::launch_speck_probe(dq, ldq, K, NP, act, &pairs, nullptr, &rows);
+  const int rc = s.finish(e);
+  if (rc != 0) return rc;
+  int h[2] = {0, 0};
+  if (hipMemcpy(h, act, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  out[0] = h[0], out[1] = h[1], out[2] = pairs, out[3] = rows;
+  return 0;
+}
+
 // lcx_test_suffstat_list_deal: the list kernel's tile map (lck::ftl_feature) evaluated on the host, no device involved.
 // info [6] = shared deal at this width (0 / 1), waves, tiles per wave, ftl_paired, ftl_split, the ones-column; feat (io)
 // [nfeat >= waves * tiles * 16 * 4]: u, w, kind (FtKind), shared of lane l16 of tile t of wave v at ((v * tiles + t) * 16 + l16) * 4.

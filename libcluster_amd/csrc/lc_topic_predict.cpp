@@ -56,6 +56,7 @@ void Context::topic_infer(int K, int T, const double* a, const double* E, int ma
   LC_HIP(hipStreamSynchronize(stream_));  // (hpack_, ptab_ and Nj_ are free again)
   qz_[cur_].K = K;
   qz_[cur_].hash_ok = false;
+  qz_written(qz_[cur_]);
   pred_vb_ = true;
   pred_docs_T_ = T;
 }

@@ -132,6 +132,16 @@ def check(asm: str):
             problems.append(f"{name}: {sz} bytes of scratch")
     if not any("estep_kernel" in n for n in scratch):
         problems.append("no .amdhsa_kernel descriptor of an estep_kernel instance found")
+    # the instances that emit kept-quad masks (last template argument true): all four of D = 64 are there, and those with
+    # three row groups per wave keep three waves per SIMD (512 / 3 registers in steps of 8: at most 168 VGPRs)
+    vgprs = {n: int(v) for n, v in re.findall(r"\.amdhsa_kernel\s+(\S+)\n(?:[^\n]*\n)*?\s*\.amdhsa_next_free_vgpr\s+(\d+)", asm)}
+    for dc in (64, 56):
+        for r in (3, 4):
+            name = f"_ZN3lck12estep_kernelILi64ELi{dc}ELi{r}ELi4ELb0ELb1EEEvNS_11EstepLaunchE"
+            if name not in vgprs:
+                problems.append(f"no emitting instance {name} found")
+            elif vgprs[name] > (168 if r == 3 else 256):
+                problems.append(f"{name}: {vgprs[name]} VGPRs cost the instance a wave per SIMD")
     for m in re.finditer(r"^(_ZN3lck12estep_kernel\w+):[^\n]*\n(.*?)\n\.Lfunc_end\d+:", asm, re.S | re.M):
         name, body = m.group(1), m.group(2).splitlines()
         seen += 1

@@ -5,6 +5,10 @@ them all in ONE GPU call.
     tools/variants.py build NAME [-DFLAG ...]     # -> tools/variants/NAME.so (git-ignored, travels with gpurun)
     tools/variants.py run [--shape N,D,K] [--what estep,suffstat,diag] [NAME ...]   # on the GPU box
 
+Switches the device sources know: -DLC_FT_SPECK_LISTS=0, -DLC_FT_SPECK_SORT=0, -DLC_FT_LIST_SHARE64=n, -DLC_FTL_SPREAD=n,
+-DLC_FTL_BR=n, -DLC_WIDE_FORCE_STREAM, -DLC_ESTEP_QMASK=0 (no E-step instance emits kept-quad masks: every statistics pass
+probes and builds its lists from qZ, as before the masks).
+
 `run` starts one child process per variant (LC_LIB_PATH), which synthesises the north-star shape, runs three fixed
 VBEM iterations (F printed to 15 digits: a variant that changes results shows here) and reports the average
 E-step / statistics kernel times over the timed launches."""
