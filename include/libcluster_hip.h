@@ -518,6 +518,34 @@ int lc_ctx_completed_draws(lc_ctx* ctx, int* ndraws);
  * (LC_RANK_LOGP: one with a log density), by_label together with LC_RANK_LOGZ / LC_RANK_LOGP, a context without data. */
 enum { LC_RANK_QZ = 0, LC_RANK_LOGZ = 1, LC_RANK_LOGP = 2 };
 int lc_ctx_top_rows(lc_ctx* ctx, int what, int ncols, int m, int largest, int by_label, int32_t* count, int32_t* group, int64_t* row, double* score);
+/* ---- order and threshold queries over the same columns: quantiles, counts at thresholds and the rows beyond a
+ * threshold, without bringing the columns to the host.  All three take their columns as lc_ctx_top_rows does: `what` is
+ * LC_RANK_QZ with ncols, or LC_RANK_LOGZ, or LC_RANK_LOGP (C = 1, ncols is not looked at); by_label != 0: column c only sees the
+ * rows the last prediction on ctx labelled c.  Only valid rows take part (never a pad row, in contexts of one and of several
+ * blocks alike), and never a row whose score is NaN: n_c below is the number of participating rows of column c.  LC_EINVAL in
+ * the cases lc_ctx_top_rows names for these arguments, with the same messages.  A context whose blocks are all empty answers
+ * with counts of 0 and LC_OK.  None of the calls changes the prediction, the qZ or the observations of ctx.  A context inside a
+ * communicator answers for ITS OWN rows only: nothing here is reduced across ranks. */
+#define LC_QUANTILES_MAX 16
+/* value[c*nprobs + i] = the order statistic of rank r_i of column c's n_c participating scores, bit for bit one of
+ * them; rank[c*nprobs + i] = r_i; count[c] = n_c.  Order: the IEEE total order restricted to non-NaN values
+ * (-inf < ... < -0.0 < +0.0 < ... < +inf), so the answer is unique down to the sign of zero.
+ * r_i = min(n_c - 1, max(0, (int64)ceil(probs[i] * (double)n_c) - 1))  (numpy's method="inverted_cdf").
+ * n_c = 0: value NaN, rank -1.  probs need not be sorted and may repeat.
+ * LC_EINVAL additionally: nprobs outside 1 ... LC_QUANTILES_MAX, a prob outside [0, 1] or NaN. */
+int lc_ctx_score_quantiles(lc_ctx* ctx, int what, int ncols, int by_label, const double* probs, int nprobs,
+                           int64_t* count, int64_t* rank, double* value);
+/* atmost[c*nthr + i] = the number of participating scores s of column c with s <= thr[i] (IEEE comparison:
+ * -0.0 <= +0.0 holds both ways); count[c] = n_c.  thr may hold +-inf; a NaN threshold is LC_EINVAL;
+ * nthr in 1 ... LC_QUANTILES_MAX. */
+int lc_ctx_score_counts(lc_ctx* ctx, int what, int ncols, int by_label, const double* thr, int nthr,
+                        int64_t* count, int64_t* atmost);
+/* every participating row of ONE column (col; 0 for LOGZ / LOGP) with score <= thr (above == 0) or >= thr (above != 0),
+ * in context order (block, then row) -- not by score.  *total = how many there are; the first min(total, capacity) of
+ * them are written to group / row / score (any may be NULL, capacity may be 0: the count only).  by_label: only rows
+ * labelled col.  LC_EINVAL additionally: col outside [0, ncols), capacity < 0, a NaN threshold. */
+int lc_ctx_rows_beyond(lc_ctx* ctx, int what, int ncols, int col, int by_label, double thr, int above, int64_t capacity,
+                       int64_t* total, int32_t* group, int64_t* row, double* score);
 /* Exemplars: lc_model_predict(m, ctx, groups, 0), then per cluster k the mtop rows labelled k (by that prediction) with the
  * largest Eloglike_k(x) -- for Gauss-Wishart clusters the smallest expected Mahalanobis distance; the responsibility is no
  * use here: in a separated mixture most rows of a cluster have q = 1.0 exactly.  C = K; score = Eloglike_k(x_n), the raw

@@ -136,6 +136,34 @@ class TopRows(NamedTuple):
     score: np.ndarray
 
 
+QUANTILES_MAX = 16  # LC_QUANTILES_MAX: the probs / thresholds of one order or threshold query
+
+
+class ScoreQuantiles(NamedTuple):
+    """Order statistics of each of C device columns (lc_ctx_score_quantiles): count (C,) int64 = the participating rows
+    (valid, score not NaN), rank (C, nprobs) int64 = min(n - 1, max(0, ceil(p n) - 1)) (numpy's "inverted_cdf"), value
+    (C, nprobs) = the score of that rank, bit for bit one of the column's; NaN / -1 where count is 0."""
+    count: np.ndarray
+    rank: np.ndarray
+    value: np.ndarray
+
+
+class ScoreCounts(NamedTuple):
+    """lc_ctx_score_counts: count (C,) int64 as ScoreQuantiles, atmost (C, nthr) int64 = the participating scores <= the
+    threshold."""
+    count: np.ndarray
+    atmost: np.ndarray
+
+
+class FlaggedRows(NamedTuple):
+    """The rows of one column beyond a threshold, in context order (lc_ctx_rows_beyond): total = how many there are;
+    group int32 (block of the context / of X), row int64 (row of that block), score: the first min(total, limit)."""
+    total: int
+    group: np.ndarray
+    row: np.ndarray
+    score: np.ndarray
+
+
 class TopicPrediction(NamedTuple):
     """Outputs of TopicModel.predict (lc_tmodel_predict).  Per document: qY (docs, T), label_t (int32), Fyz, Fz, sweeps
     (int32); per document lists of per-row arrays: label (int32), logZ, qZ ((N_i, K) each, or None)."""
@@ -350,6 +378,11 @@ def lib() -> C.CDLL:
     L.lc_ctx_top_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p, c_int64_p,
                                   c_double_p]
     L.lc_model_exemplars.argtypes = [C.c_void_p, C.c_void_p, c_int_p, C.c_int, c_int32_p, c_int32_p, c_int64_p, c_double_p]
+    L.lc_ctx_score_quantiles.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_int64_p, c_int64_p,
+                                         c_double_p]
+    L.lc_ctx_score_counts.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_int64_p, c_int64_p]
+    L.lc_ctx_rows_beyond.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int64,
+                                     c_int64_p, c_int32_p, c_int64_p, c_double_p]
     L.lc_model_predict_conditional.argtypes = [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, c_int_p, C.c_int]
     L.lc_ctx_get_conditional.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, C.c_int64, c_double_p]
     L.lc_model_predict_conditional_var.argtypes = [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, c_int_p, C.c_int]
@@ -824,6 +857,53 @@ class Context:
         return _top_rows_call(lambda *out: lib().lc_ctx_top_rows(self._h, what, int(ncols), int(m), int(bool(largest)),
                                                                  int(bool(by_label)), *out), int(ncols), int(m))
 
+    def _score_columns(self, by, ncols):
+        what = {"qz": RANK_QZ, "logz": RANK_LOGZ, "logp": RANK_LOGP}.get(by)
+        if what is None:
+            raise ValueError("by must be 'qz', 'logz' or 'logp'")
+        if what != RANK_QZ:
+            ncols = 1
+        elif ncols is None:
+            ncols = self.dims()[3]
+        return what, int(ncols)
+
+    def score_quantiles(self, probs, by="logp", ncols=None, by_label=False):
+        """ScoreQuantiles of each column at the probabilities probs (1 ... QUANTILES_MAX values in [0, 1], any order),
+        selected on the device (lc_ctx_score_quantiles): the columns, by_label and the rows that take part as top_rows;
+        the quantile is numpy's method="inverted_cdf" in the order -inf < ... < -0.0 < +0.0 < ... < +inf."""
+        what, ncols = self._score_columns(by, ncols)
+        p = np.ascontiguousarray(np.atleast_1d(probs), dtype=np.float64).reshape(-1)
+        shape = (max(ncols, 0), min(p.size, QUANTILES_MAX))  # (out-of-range arguments are the library's to refuse)
+        count = np.zeros(shape[0], dtype=np.int64)
+        rank, value = np.full(shape, -1, dtype=np.int64), np.full(shape, np.nan)
+        check(lib().lc_ctx_score_quantiles(self._h, what, ncols, int(bool(by_label)), dptr(p), p.size,
+                                           count.ctypes.data_as(c_int64_p), rank.ctypes.data_as(c_int64_p), dptr(value)))
+        return ScoreQuantiles(count, rank, value)
+
+    def score_counts(self, thresholds, by="logp", ncols=None, by_label=False):
+        """ScoreCounts of each column at 1 ... QUANTILES_MAX thresholds (+-inf allowed), counted on the device
+        (lc_ctx_score_counts): how many participating scores are <= each threshold."""
+        what, ncols = self._score_columns(by, ncols)
+        t = np.ascontiguousarray(np.atleast_1d(thresholds), dtype=np.float64).reshape(-1)
+        shape = (max(ncols, 0), min(t.size, QUANTILES_MAX))
+        count, atmost = np.zeros(shape[0], dtype=np.int64), np.zeros(shape, dtype=np.int64)
+        check(lib().lc_ctx_score_counts(self._h, what, ncols, int(bool(by_label)), dptr(t), t.size,
+                                        count.ctypes.data_as(c_int64_p), atmost.ctypes.data_as(c_int64_p)))
+        return ScoreCounts(count, atmost)
+
+    def rows_beyond(self, threshold, by="logp", col=0, above=False, by_label=False, limit=1 << 20, ncols=None):
+        """FlaggedRows of ONE column: every participating row with score <= threshold (above: >=), in context order,
+        compacted on the device (lc_ctx_rows_beyond).  total counts them all; at most limit of them are returned."""
+        what, ncols = self._score_columns(by, ncols)
+        cap = max(int(limit), 0)
+        group, row, score = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int64), np.empty(cap)
+        total = C.c_int64(0)
+        check(lib().lc_ctx_rows_beyond(self._h, what, ncols, int(col), int(bool(by_label)), float(threshold), int(bool(above)),
+                                       int(limit), C.byref(total), group.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       row.ctypes.data_as(c_int64_p), dptr(score)))
+        n = min(total.value, cap)
+        return FlaggedRows(total.value, group[:n].copy(), row[:n].copy(), score[:n].copy())
+
     def get_doc_predictions(self, doc0, n, T):
         """Documents [doc0, doc0+n) of the last TopicModel.predict_context on this context -> (qY (n, T), label_t int32,
         Fyz, Fz, sweeps int32)."""
@@ -1198,6 +1278,20 @@ class Model:
             ctx.set_data(self._blocks(X))
             self.predict_context(ctx, groups)
             return ctx.top_rows(m, by="logp", largest=False)
+
+    def logp_quantiles(self, X, probs, groups=None, device=0):
+        """ScoreQuantiles (one column) of the logp of predict over all rows of X, selected on the device."""
+        with Context(device) as ctx:
+            ctx.set_data(self._blocks(X))
+            self.predict_context(ctx, groups)
+            return ctx.score_quantiles(probs, by="logp")
+
+    def flag(self, X, threshold, groups=None, device=0, limit=1 << 20):
+        """FlaggedRows of the rows of X with logp <= threshold, in the order of X: the detector next to logp_quantiles."""
+        with Context(device) as ctx:
+            ctx.set_data(self._blocks(X))
+            self.predict_context(ctx, groups)
+            return ctx.rows_beyond(threshold, by="logp", limit=limit)
 
     def release_data(self):
         """Free the training observations and qZ; the parameters (and predict) stay."""

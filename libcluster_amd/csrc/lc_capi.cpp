@@ -1312,6 +1312,39 @@ int lc_ctx_top_rows(lc_ctx* ctx, int what, int ncols, int m, int largest, int by
   });
 }
 
+// ---- order and threshold queries -------------------------------
+int lc_ctx_score_quantiles(lc_ctx* ctx, int what, int ncols, int by_label, const double* probs, int nprobs, int64_t* count,
+                           int64_t* rank, double* value) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    need(probs, "probs");
+    need(count, "count");
+    need(rank, "rank");
+    need(value, "value");
+    ctx->impl.score_quantiles(what, ncols, by_label != 0, probs, nprobs, count, rank, value);
+  });
+}
+
+int lc_ctx_score_counts(lc_ctx* ctx, int what, int ncols, int by_label, const double* thr, int nthr, int64_t* count,
+                        int64_t* atmost) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    need(thr, "thr");
+    need(count, "count");
+    need(atmost, "atmost");
+    ctx->impl.score_counts(what, ncols, by_label != 0, thr, nthr, count, atmost);
+  });
+}
+
+int lc_ctx_rows_beyond(lc_ctx* ctx, int what, int ncols, int col, int by_label, double thr, int above, int64_t capacity,
+                       int64_t* total, int32_t* group, int64_t* row, double* score) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    need(total, "total");
+    ctx->impl.rows_beyond(what, ncols, col, by_label != 0, thr, above != 0, capacity, total, group, row, score);
+  });
+}
+
 int lc_model_exemplars(lc_model* m, lc_ctx* ctx, const int* groups, int mtop, int32_t* count, int32_t* group, int64_t* row,
                        double* score) {
   return guarded([&] {

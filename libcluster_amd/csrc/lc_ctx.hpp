@@ -356,6 +356,14 @@ class Context {
   // last prediction labelled c.  count[C]; group, row, score [C x m], best first, -1 / -1 / NaN past count[c].
   void top_rows(int what, int ncols, int m, bool largest, bool by_label, int32_t* count, int32_t* group, int64_t* row,
                 double* score);
+  // Order and threshold queries over the same columns (lck::ScoreSelectLaunch, ScoreCountsLaunch,
+  // RowsBeyondLaunch; the outputs are those of lc_ctx_score_quantiles, lc_ctx_score_counts, lc_ctx_rows_beyond).  None of
+  // them changes the prediction, the qZ or the observations.
+  void score_quantiles(int what, int ncols, bool by_label, const double* probs, int nprobs, int64_t* count, int64_t* rank,
+                       double* value);
+  void score_counts(int what, int ncols, bool by_label, const double* thr, int nthr, int64_t* count, int64_t* atmost);
+  void rows_beyond(int what, int ncols, int col, bool by_label, double thr, bool above, int64_t capacity, int64_t* total,
+                   int32_t* group, int64_t* row, double* score);
   // Two-level models (lc_topic_predict.cpp): after a raw E-step left L_nk = Eloglike_k(x_n) in K columns of
   // qZ, every group of the context is one document: its qY, label_t, Fyz, Fz and sweep count into the context's
   // per-document outputs, label / logZ per row as above (lck::TopicInferLaunch; a: J x T, E: T x K host arrays).
@@ -570,9 +578,17 @@ class Context {
   DevBuf<double> hdraws_;
   DevBuf<int> hdlabel_;
   int pred_holes_draws_ = 0;
-  // top_rows: the first stage's partial lists and the result [C x m scores | C x m positions]
+  // top_rows: the first stage's partial lists and the result [C x m scores | C x m positions]; the order and threshold
+  // queries keep their integer scratch and results in toppos_ and the flagged rows' scores in topkey_
   DevBuf<double> topkey_, topout_;
   DevBuf<int64_t> toppos_;
+  // the columns `what` names, after the argument checks top_rows and the order and threshold queries share
+  struct RankColumns {
+    const double* col = nullptr;
+    int C = 1;
+  };
+  RankColumns rank_columns(int what, int ncols, bool by_label) const;
+  lck::ScoreColumns score_columns(const RankColumns& rc, bool by_label, const char* who) const;  // NP_ > 0
   // per-document outputs of the last topic_infer ([J x T], [J x 2], [J x 2]); pred_docs_T_ = its T (0: none)
   DevBuf<double> tqy_, tf_;
   DevBuf<int> tint_;

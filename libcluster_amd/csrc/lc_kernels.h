@@ -674,6 +674,58 @@ struct TopRowsLaunch {
 int top_rows_chunks(int64_t NP);
 hipError_t launch_top_rows(const TopRowsLaunch& a, hipStream_t stream);
 
+// ---- order and threshold queries (lc_kernels_select.hip) over the same columns ---------------------------------
+// The columns and filters of TopRowsLaunch; `label`: column c only sees the rows with label[row] == label0 + c.  NaN scores and
+// pad rows take part in nothing.
+constexpr int SEL_MAX = 16;             // LC_QUANTILES_MAX: ranks / thresholds per call
+constexpr int SEL_STATE_WORDS = 58;     // 8-byte words of the per-column state between the passes of the radix select
+constexpr int SEL_HIST_WORDS = SEL_MAX * 256;  // ... and of its global histograms (one of 256 bins per active prefix)
+constexpr int SEL_GRID_BLOCKS = 2048;   // blocks of 256 threads the histogram / counts kernels spread over all columns (8 per CU)
+struct ScoreColumns {
+  const double* col = nullptr;  // [C x ld]
+  int64_t ld = 0;
+  int C = 0;
+  int64_t NP = 0;               // padded rows (multiple of 16)
+  const int* rginfo = nullptr;  // [NP / 16] or nullptr (single group; the valid rows are the first nrows)
+  int64_t nrows = 0;
+  const int* label = nullptr;   // [NP] or nullptr: no filter
+  int label0 = 0;
+};
+// Order statistics: rank r_i = min(n - 1, max(0, ceil(probs[i] n) - 1)) of the column's n participating scores in the total
+// order -inf < ... < -0.0 < +0.0 < ... < +inf.  out: [C] n | [C x nprobs] r_i (-1: n = 0) | [C x nprobs] the bits of the value
+// (0 where the rank is -1).  NP > 0.  The launcher zeroes hist; state needs no initial value.
+struct ScoreSelectLaunch {
+  ScoreColumns s;
+  int nprobs = 0;                       // 1 ... SEL_MAX
+  double probs[SEL_MAX] = {};
+  unsigned long long* hist = nullptr;   // [C x SEL_HIST_WORDS]
+  long long* state = nullptr;           // [C x SEL_STATE_WORDS]
+  long long* out = nullptr;             // [C + 2 C nprobs]
+};
+hipError_t launch_score_select(const ScoreSelectLaunch& a, hipStream_t stream);
+// out[c][0] = n, out[c][1 + i] = the participating scores <= thr[i] (IEEE comparison); the launcher zeroes out
+struct ScoreCountsLaunch {
+  ScoreColumns s;
+  int nthr = 0;                         // 1 ... SEL_MAX
+  double thr[SEL_MAX] = {};
+  unsigned long long* out = nullptr;    // [C x (1 + nthr)]
+};
+hipError_t launch_score_counts(const ScoreCountsLaunch& a, hipStream_t stream);
+// The participating rows of ONE column (s.C = 1) with score <= thr (above = 0) or >= thr, in row order: *total = how many,
+// pos / score = the first min(total, capacity) of them (padded rows).
+struct RowsBeyondLaunch {
+  ScoreColumns s;
+  double thr = 0.0;
+  int above = 0;
+  int64_t capacity = 0;
+  int nchunks = 0;                      // top_rows_chunks(NP)
+  long long* chunkoff = nullptr;        // [nchunks] scratch: the chunk counts, then their exclusive scan
+  long long* total = nullptr;           // [1]
+  long long* pos = nullptr;             // [capacity]
+  double* score = nullptr;              // [capacity]
+};
+hipError_t launch_rows_beyond(const RowsBeyondLaunch& a, hipStream_t stream);
+
 // synthetic mixture generator (bench): Philox4x32-10, counter = global row.
 struct SynthLaunch {
   int DP, D, K;

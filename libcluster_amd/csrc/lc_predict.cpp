@@ -564,26 +564,155 @@ void Context::get_completed(int j, int64_t row0, int64_t n, double* rows, int64_
   LC_HIP(hipStreamSynchronize(stream_));
 }
 
+Context::RankColumns Context::rank_columns(int what, int ncols, bool by_label) const {
+  if (J_ < 1) throw std::invalid_argument("the context holds no observations (lc_ctx_set_data / lc_ctx_synth)");
+  if (what < 0 || what > 2) throw std::invalid_argument("unknown ranking source (LC_RANK_QZ, LC_RANK_LOGZ, LC_RANK_LOGP)");
+  RankColumns rc;
+  if (what == 0) {
+    const int K = qz_[cur_].K;
+    if (ncols < 1 || ncols > K) throw std::invalid_argument("ncols must be in 1 ... K, the columns of the context's qZ (" + std::to_string(K) + ")");
+    if (by_label && !pred_vb_) throw std::invalid_argument("the context holds no prediction (lc_model_predict): no labels to rank by");
+    rc.C = ncols;
+    rc.col = qz_[cur_].buf.p;
+  } else {
+    if (by_label) throw std::invalid_argument("by_label ranks the columns of qZ, not logZ / logp");
+    if (!pred_vb_) throw std::invalid_argument("the context holds no prediction (lc_model_predict)");
+    if (what == 2 && !pred_logp_) throw std::invalid_argument("the context's prediction has no log density");
+    rc.col = what == 1 ? plogz_.p : plogp_.p;
+  }
+  return rc;
+}
+
+lck::ScoreColumns Context::score_columns(const RankColumns& rc, bool by_label, const char* who) const {
+  if (!rc.col || (by_label && !plabel_.p)) throw std::logic_error(std::string(who) + ": the column is not on the device");
+  lck::ScoreColumns s;
+  s.col = rc.col;
+  s.ld = NP_;
+  s.C = rc.C;
+  s.NP = NP_;
+  s.rginfo = J_ > 1 ? rginfo_.p : nullptr;
+  s.nrows = Nj_[0];
+  s.label = by_label ? plabel_.p : nullptr;
+  return s;
+}
+
+void Context::score_quantiles(int what, int ncols, bool by_label, const double* probs, int nprobs, int64_t* count,
+                              int64_t* rank, double* value) {
+  use_device();
+  const RankColumns rc = rank_columns(what, ncols, by_label);
+  if (nprobs < 1 || nprobs > lck::SEL_MAX) throw std::invalid_argument("nprobs must be in 1 ... 16");
+  for (int i = 0; i < nprobs; ++i)
+    if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) throw std::invalid_argument("every prob must be in [0, 1]");
+  const size_t C = (size_t)rc.C, n = C * (size_t)nprobs;
+  std::fill(count, count + C, (int64_t)0);
+  std::fill(rank, rank + n, (int64_t)-1);
+  std::fill(value, value + n, std::numeric_limits<double>::quiet_NaN());
+  if (NP_ == 0) return;
+  lck::ScoreSelectLaunch a;
+  a.s = score_columns(rc, by_label, "score_quantiles");
+  a.nprobs = nprobs;
+  std::copy(probs, probs + nprobs, a.probs);
+  const size_t nhist = C * lck::SEL_HIST_WORDS, nstate = C * lck::SEL_STATE_WORDS, nout = C + 2 * n;
+  toppos_.reserve(nhist + nstate + nout);
+  static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(double) == sizeof(int64_t), "the results travel in 8-byte slots");
+  a.hist = reinterpret_cast<unsigned long long*>(toppos_.p);
+  a.state = reinterpret_cast<long long*>(toppos_.p + nhist);
+  a.out = reinterpret_cast<long long*>(toppos_.p + nhist + nstate);
+  LC_HIP(lck::launch_score_select(a, stream_));
+  hred_.resize(nout);
+  LC_HIP(hipMemcpyAsync(hred_.data(), a.out, nout * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+  std::memcpy(count, hred_.data(), C * sizeof(int64_t));
+  std::memcpy(rank, hred_.data() + C, n * sizeof(int64_t));
+  for (size_t i = 0; i < n; ++i)
+    if (rank[i] >= 0) std::memcpy(value + i, hred_.data() + C + n + i, sizeof(double));  // (the bits of one of the scores)
+}
+
+void Context::score_counts(int what, int ncols, bool by_label, const double* thr, int nthr, int64_t* count, int64_t* atmost) {
+  use_device();
+  const RankColumns rc = rank_columns(what, ncols, by_label);
+  if (nthr < 1 || nthr > lck::SEL_MAX) throw std::invalid_argument("nthr must be in 1 ... 16");
+  for (int i = 0; i < nthr; ++i)
+    if (thr[i] != thr[i]) throw std::invalid_argument("a threshold is NaN");
+  const size_t C = (size_t)rc.C, n = C * (size_t)nthr;
+  std::fill(count, count + C, (int64_t)0);
+  std::fill(atmost, atmost + n, (int64_t)0);
+  if (NP_ == 0) return;
+  lck::ScoreCountsLaunch a;
+  a.s = score_columns(rc, by_label, "score_counts");
+  a.nthr = nthr;
+  std::copy(thr, thr + nthr, a.thr);
+  toppos_.reserve(C + n);
+  a.out = reinterpret_cast<unsigned long long*>(toppos_.p);
+  LC_HIP(lck::launch_score_counts(a, stream_));
+  hred_.resize(C + n);
+  LC_HIP(hipMemcpyAsync(hred_.data(), a.out, (C + n) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+  for (size_t c = 0; c < C; ++c) {
+    std::memcpy(count + c, hred_.data() + c * (1 + (size_t)nthr), sizeof(int64_t));
+    std::memcpy(atmost + c * (size_t)nthr, hred_.data() + c * (1 + (size_t)nthr) + 1, (size_t)nthr * sizeof(int64_t));
+  }
+}
+
+void Context::rows_beyond(int what, int ncols, int col, bool by_label, double thr, bool above, int64_t capacity,
+                          int64_t* total, int32_t* group, int64_t* row, double* score) {
+  use_device();
+  RankColumns rc = rank_columns(what, ncols, by_label);
+  if (col < 0 || col >= rc.C) throw std::invalid_argument("col must be in 0 ... ncols - 1 (0 for logZ / logp)");
+  if (capacity < 0) throw std::invalid_argument("capacity must not be negative");
+  if (thr != thr) throw std::invalid_argument("a threshold is NaN");
+  *total = 0;
+  if (NP_ == 0) return;
+  lck::RowsBeyondLaunch a;
+  a.s = score_columns(rc, by_label, "rows_beyond");
+  a.s.col += (size_t)col * (size_t)NP_;
+  a.s.C = 1;
+  a.s.label0 = col;
+  a.thr = thr;
+  a.above = above ? 1 : 0;
+  a.capacity = std::min<int64_t>(capacity, NP_);  // (no more rows than the context pads to can qualify)
+  if (!group && !row && !score) a.capacity = 0;   // the count only
+  a.nchunks = lck::top_rows_chunks(NP_);
+  const size_t cap = (size_t)a.capacity;
+  toppos_.reserve((size_t)a.nchunks + 1 + cap);
+  topkey_.reserve(cap);
+  a.chunkoff = reinterpret_cast<long long*>(toppos_.p);
+  a.total = reinterpret_cast<long long*>(toppos_.p + a.nchunks);
+  a.pos = reinterpret_cast<long long*>(toppos_.p + a.nchunks + 1);
+  a.score = topkey_.p;
+  LC_HIP(lck::launch_rows_beyond(a, stream_));
+  hred_.resize(1);
+  LC_HIP(hipMemcpyAsync(hred_.data(), a.total, sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+  std::memcpy(total, hred_.data(), sizeof(int64_t));
+  const size_t nw = (size_t)std::min<int64_t>(*total, a.capacity);
+  if (nw == 0) return;
+  if (group || row) {
+    hred_.resize(nw);
+    LC_HIP(hipMemcpyAsync(hred_.data(), a.pos, nw * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+  }
+  if (score) LC_HIP(hipMemcpyAsync(score, a.score, nw * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+  if (!group && !row) return;
+  size_t j = 0;  // (the positions ascend: the block only moves forward)
+  for (size_t i = 0; i < nw; ++i) {
+    int64_t pos;
+    std::memcpy(&pos, hred_.data() + i, sizeof(pos));
+    while (j + 1 < (size_t)J_ && pos >= goff_[j + 1]) ++j;
+    if (pos < goff_[j] || pos - goff_[j] >= Nj_[j]) throw std::logic_error("rows_beyond: a flagged position is no observation");
+    if (group) group[i] = (int32_t)j;
+    if (row) row[i] = pos - goff_[j];
+  }
+}
+
 void Context::top_rows(int what, int ncols, int m, bool largest, bool by_label, int32_t* count, int32_t* group,
                        int64_t* row, double* score) {
   use_device();
   if (J_ < 1) throw std::invalid_argument("the context holds no observations (lc_ctx_set_data / lc_ctx_synth)");
   if (m < 1 || m > lck::TOP_MAX_M) throw std::invalid_argument("m must be in 1 ... 64");
-  if (what < 0 || what > 2) throw std::invalid_argument("unknown ranking source (LC_RANK_QZ, LC_RANK_LOGZ, LC_RANK_LOGP)");
-  const double* col = nullptr;
-  int C = 1;
-  if (what == 0) {
-    const int K = qz_[cur_].K;
-    if (ncols < 1 || ncols > K) throw std::invalid_argument("ncols must be in 1 ... K, the columns of the context's qZ (" + std::to_string(K) + ")");
-    if (by_label && !pred_vb_) throw std::invalid_argument("the context holds no prediction (lc_model_predict): no labels to rank by");
-    C = ncols;
-    col = qz_[cur_].buf.p;
-  } else {
-    if (by_label) throw std::invalid_argument("by_label ranks the columns of qZ, not logZ / logp");
-    if (!pred_vb_) throw std::invalid_argument("the context holds no prediction (lc_model_predict)");
-    if (what == 2 && !pred_logp_) throw std::invalid_argument("the context's prediction has no log density");
-    col = what == 1 ? plogz_.p : plogp_.p;
-  }
+  const RankColumns rc = rank_columns(what, ncols, by_label);
+  const double* col = rc.col;
+  const int C = rc.C;
   const size_t n = (size_t)C * m;
   std::fill(count, count + C, 0);
   std::fill(group, group + n, -1);
