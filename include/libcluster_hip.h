@@ -230,8 +230,9 @@ int lc_ctx_set_speck_skip(lc_ctx* ctx, int on);
 int lc_ctx_speck_passes(lc_ctx* ctx, int64_t* skipping, int64_t* dense);
 /* How many of the skipping passes took the list route: at D <= 64 (a padded width of 64 columns), where the probe finds
  * that at least 58 of every 64 sampled rows keep values of exactly one cluster quad, the pass first writes, per row
- * chunk and quad, the list of the rows that keep a value of that quad, and then sums every list on its own.  Same records,
- * same bound; lc_ctx_set_speck_skip(ctx, 0) turns it off with the rest. */
+ * chunk and quad, the list of the rows that keep a value of that quad, and then sums every list on its own.  At
+ * 57 <= D <= 64 a listed row is summed into a cluster of the quad only where that cluster's own responsibility is not
+ * below 2^-300 (one wave per cluster).  Same records, same bound; lc_ctx_set_speck_skip(ctx, 0) turns it off with the rest. */
 int lc_ctx_speck_list_passes(lc_ctx* ctx, int64_t* lists);
 /* A Gauss-Wishart E-step at 49 <= D <= 64 (a padded width of 64 columns) whose statistics pass could take the list route
  * (the feature-GEMM kernel owns it: more than 16 clusters there) writes, next to the responsibilities,

@@ -224,7 +224,9 @@ bool speck_probe_says_lists(int64_t single, int64_t rows);
 // ---- the list route of a skipping pass (suffstat_list_kernel) -------------------------------------------
 // Every (row chunk, cluster quad) of the plan gets the ascending list of the chunk's rows that keep a value of the quad
 // ("not (q < SPECK_TAU)" in any of its clusters: a NaN is kept, pad rows are in no list, a soft row is in several), and one
-// block sums one list with the feature GEMM's arithmetic for a single quad.  Same partial records as launch_suffstat.
+// block sums one list: at DC = 56 with the feature GEMM's arithmetic for a single quad (all four q of a listed row), at
+// DC = 64 one wave per cluster on the VALU, a listed row going into a cluster only where speck_keeps(its own q)
+// (suffstat_owner_kernel).  Same partial records as launch_suffstat.
 // The buffer: [nchunks x nq] lengths (int), then [nchunks x nq] segments of chunk_rows chunk-local row offsets each -- a
 // segment can hold every row of its chunk, so no list overflows whatever qZ holds -- as 16-bit values while a chunk has at
 // most 65536 rows, 32-bit beyond.
@@ -241,6 +243,7 @@ inline SsListLayout ss_list_layout(int nchunks, int64_t chunk_rows, int K) {
   return l;
 }
 bool suffstat_list_instance(int DP, int DC);  // a suffstat_list_kernel exists for this width (DC = 0: DP)
+bool suffstat_owner_instance(int DP, int DC);  // its lists are summed by suffstat_owner_kernel (false with -DLC_FTL_OWNER=0)
 bool speck_lists_enabled();                   // false in a build with -DLC_FT_SPECK_LISTS=0 (tools/variants.py)
 // a (dense, SS_FEAT) launch as launch_suffstat takes it, with its plan; lists: ss_list_layout(...).bytes of device memory.
 // Both refuse (hipErrorInvalidValue, nothing launched) a launch that is not the plan's, a route other than the feature
@@ -412,6 +415,19 @@ __host__ __device__ constexpr int ftl_wi(int DC, int t) {
 }
 static_assert(!ftl_shared(64) || (ftl_tpw(64) == ftl_paired(64) + 2 && 16 * 2 * 8 >= ft_features(64) - 16 * ft_offdiag(64)),
               "shared deal: 8 waves of two stars and two free tiles");
+
+// The owner kernel (suffstat_owner_kernel, DC = DP = 64): one WAVE per cluster, lane w owns column w, and the
+// wave's accumulator t holds, in lane w,
+//   t = 0 ... 32 ("diagonals"): the product x_w x_((w + t) mod 64) -- every unordered pair once; at t = 32 lanes w and w + 32
+//     hold the same product (summed in the same order), and only the lower one is stored: the upper is FT_SPARE
+//   t = 33: the linear feature x_w,  t = 34: N_k (every lane holds it, lane 0 stores it)
+// fto_feature: THE map of that kernel's epilogue, (u, w) as in FtFeature with `one` = 64 for the column of ones.
+constexpr int FTO_DIAGS = 33, FTO_ACCS = 35;
+__host__ __device__ __attribute__((always_inline)) constexpr FtFeature fto_feature(int lane, int t) {
+  if (t < FTO_DIAGS) return {lane, (lane + t) & 63, t == 32 && lane >= 32 ? FT_SPARE : FT_PRODUCT};
+  if (t == FTO_DIAGS) return {lane, 64, FT_LINEAR};
+  return {64, 64, lane == 0 ? FT_COUNT : FT_SPARE};
+}
 
 // the smallest tile count of any wave (the 8-wave deal: ft_tpw or one fewer)
 __host__ __device__ constexpr int ft_nt_min(int DP, int DC, int NQ) {

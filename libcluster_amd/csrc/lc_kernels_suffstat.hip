@@ -1533,6 +1533,159 @@ __global__ void __launch_bounds__(512, 2) suffstat_list_kernel(SuffstatLaunch a,
   }
 }
 
+// ---- hard rows at DC = DP = 64: one wave per cluster, the products on the VALU -------------------------------
+// On a hard row one of a quad's four clusters holds a value and the MFMA's other three blocks multiply specks or zeros.  The
+// fp64 MFMA adds a step's four rows to an accumulator as a chain in row order, rounding after each row, so for ONE cluster
+// the accumulator of feature (u, w) receives, per kept row in ascending order, acc = fma(q, rnd(x_u x_w), acc): one
+// v_mul_f64 and one v_fma_f64 per 64 features, no matrix pipe.
+// One block = one (row chunk, cluster quad) as before, 4 waves, wave c = cluster 4 quad + c; the waves share nothing (no
+// __syncthreads).  A wave walks the quad's list 64 places at a time: lane l loads entry p0 + l and the wave's own q at that
+// row; a row is the wave's if speck_keeps(q) -- the rule is now per (listed row, cluster), DESIGN 4.4 -- and the kept rows of
+// the ballot are taken in ascending order, offset and q through readlane, lane w loading X[row][w] (one 512-byte load).
+// The deal is fto_feature's diagonals: the row goes to a wave-private LDS slot TWICE (128 doubles), so the rotated factor of
+// accumulator t is slot[w + t] with t as the read's immediate offset.  The entries of a window are fetched two windows
+// ahead and their q one ahead; the rows of LC_FTO_DEPTH kept places are in flight while the group before them is summed.
+// -DLC_FTL_OWNER=0 (tools/variants.py): the list kernel at DC = 64 too, as before.
+#ifndef LC_FTL_OWNER
+#define LC_FTL_OWNER 1
+#endif
+#ifndef LC_FTO_DEPTH
+#define LC_FTO_DEPTH 4  // rows of a group (two groups are in flight)
+#endif
+#ifndef LC_FTO_FUSED
+#define LC_FTO_FUSED 1  // 0: rnd(q p) + acc in place of fma(q, p, acc)
+#endif
+bool suffstat_owner_instance(int DP, int DC) { return LC_FTL_OWNER != 0 && DP == 64 && (DC == 0 || DC == 64); }
+template <int DP, int DC, typename IT>
+__global__ void __launch_bounds__(256, 4) suffstat_owner_kernel(SuffstatLaunch a, const int* __restrict__ lens, const IT* __restrict__ ent,
+                                                                 int nq) {
+  static_assert(DP == 64 && DC == 64, "lane w owns column w");
+  constexpr int G = LC_FTO_DEPTH, NSLOT = 2, ND = FTO_DIAGS;
+  static_assert(G >= 1 && G <= 8, "rows in flight");
+  __shared__ double slots[4][NSLOT][2 * DP];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int chunk = blockIdx.x / nq, quad = blockIdx.x % nq;
+  const int k = 4 * quad + wave;
+  if (k >= a.K) return;
+  const int64_t r0 = (int64_t)chunk * a.chunk_rows;
+  // (what the builders wrote: 0 <= len <= rows of the chunk, entries below that; clamped all the same, so that no
+  //  address leaves X or qZ whatever the buffer holds)
+  const int64_t rows64 = a.NP - r0 < a.chunk_rows ? a.NP - r0 : a.chunk_rows;
+  const int rows = rows64 > 0 ? (int)rows64 : 0;
+  int len = lens[blockIdx.x];
+  len = len < 0 ? 0 : len > rows ? rows : len;
+  const int nwin = (len + 63) / 64;
+  const IT* li = ent + (int64_t)blockIdx.x * a.chunk_rows;
+  const int64_t rb = rows > 0 ? r0 : 0;  // (a chunk behind the last row: nothing is summed, and nothing is read there)
+  const double* qcol = a.qZ + (int64_t)k * a.ldq + rb;
+  const double* xl = a.X + rb * DP + lane;
+  double* slot = &slots[wave][0][lane];
+
+  double acc[ND], lin = 0.0, cnt = 0.0;
+#pragma unroll
+  for (int t = 0; t < ND; ++t) acc[t] = 0.0;
+
+  // windows: `cur` is summed, n1 has its q on the way, n2 its entries (a place past the end: offset 0, masked out)
+  auto ld_off = [&](int w) {
+    const int p = 64 * w + lane;
+    const int o = p < len ? (int)li[p] : 0;
+    return o < rows ? o : 0;
+  };
+  int widx = -1;
+  unsigned long long mask = 0ull;
+  int cur_off = 0, n1_off = ld_off(0), n2_off = ld_off(1);
+  double cur_q = 0.0, n1_q = qcol[n1_off];
+  auto advance = [&]() {
+    ++widx;
+    cur_off = n1_off, cur_q = n1_q;
+    n1_off = n2_off;
+    n1_q = qcol[n1_off];
+    n2_off = ld_off(widx + 2);
+    mask = __ballot(64 * widx + lane < len && speck_keeps(cur_q));
+  };
+  // the next G kept places (fewer at a window's end: a group lies within one window): every load is issued, a missing
+  // place reads the chunk's first row and is not summed
+  auto fetch = [&](double(&gx)[G], double(&gq)[G], int& n) {
+    while (mask == 0ull && widx + 1 < nwin) advance();
+    n = 0;
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+      const bool has = mask != 0ull;
+      const int l = has ? __builtin_ctzll(mask) : 0;
+      mask &= mask - (has ? 1ull : 0ull);
+      const int off = has ? __builtin_amdgcn_readlane(cur_off, l) : 0;
+      gq[i] = readlane_f64(cur_q, l);
+      gx[i] = xl[(int64_t)off * DP];
+      n += has ? 1 : 0;
+    }
+  };
+  auto row = [&](double x, double q, int s) {
+    double* sl = slot + s * 2 * DP;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the slot's earlier reads stay in front of the stores)
+    __builtin_amdgcn_wave_barrier();
+    sl[0] = x;
+    sl[DP] = x;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    double y[ND];
+    y[0] = x;
+#pragma unroll
+    for (int t = 1; t < ND; ++t) {
+      y[t] = sl[t];
+      // (neighbouring reads would be joined into ds_read2_b64, which takes the LDS array twice as long as the two reads
+      //  it replaces: an empty statement that may touch memory stands between them)
+      asm volatile("" ::: "memory");
+    }
+#pragma unroll
+    for (int t = 0; t < ND; ++t) {
+      const double p = x * y[t];
+#if LC_FTO_FUSED
+      acc[t] = fma(q, p, acc[t]);
+#else
+      acc[t] = __dadd_rn(__dmul_rn(q, p), acc[t]);
+#endif
+    }
+#if LC_FTO_FUSED
+    lin = fma(q, x, lin);
+    cnt = fma(q, 1.0, cnt);
+#else
+    lin = __dadd_rn(__dmul_rn(q, x), lin);
+    cnt = __dadd_rn(q, cnt);
+#endif
+  };
+  auto sum = [&](const double(&gx)[G], const double(&gq)[G], int n) {
+#pragma unroll
+    for (int i = 0; i < G; ++i)
+      if (i < n) row(gx[i], gq[i], i % NSLOT);
+  };
+  double ax[G], aq[G], bx[G], bq[G];
+  int an = 0, bn = 0;
+  fetch(ax, aq, an);
+  while (an > 0) {
+    fetch(bx, bq, bn);
+    sum(ax, aq, an);
+    if (bn == 0) break;
+    fetch(ax, aq, an);
+    sum(bx, bq, bn);
+  }
+
+  // ---- the cluster's partial record (an empty list, a cluster without kept rows: exact zeros); S_k from ONE accumulator
+  // per pair, so it is exactly symmetric
+  const int64_t SS = 1 + (int64_t)DP + (int64_t)DP * DP;
+  double* out = a.partial + ((int64_t)chunk * a.KR + k) * SS;
+  double* S = out + 1 + DP;
+#pragma unroll
+  for (int t = 0; t < ND; ++t) {
+    const FtFeature f = fto_feature(lane, t);
+    if (f.kind == FT_PRODUCT) {
+      S[f.u * DP + f.w] = acc[t];
+      if (t != 0) S[f.w * DP + f.u] = acc[t];
+    }
+  }
+  out[1 + fto_feature(lane, ND).u] = lin;
+  if (fto_feature(lane, ND + 1).kind == FT_COUNT) out[0] = cnt;
+}
+
 // the checks both launchers share; *lay: the buffer's layout
 static hipError_t ss_list_check(const SuffstatLaunch& a, const SuffstatPlan& p, const void* lists, size_t bytes, SsListLayout* lay) {
   if (a.K <= 0 || p.nchunks <= 0 || !lists || !a.qZ || !a.X) return hipErrorInvalidValue;
@@ -1568,14 +1721,23 @@ static hipError_t launch_ss_list_i(const SuffstatLaunch& a, const SsListLayout& 
                      reinterpret_cast<const IT*>(static_cast<const char*>(lists) + lay.ent_off), lay.nq);
   return hipGetLastError();
 }
+template <typename IT>
+static hipError_t launch_ss_owner_i(const SuffstatLaunch& a, const SsListLayout& lay, const void* lists, hipStream_t stream) {
+  hipLaunchKernelGGL((suffstat_owner_kernel<64, 64, IT>), dim3((unsigned)(a.nchunks * lay.nq)), dim3(256), 0, stream, a,
+                     static_cast<const int*>(lists), reinterpret_cast<const IT*>(static_cast<const char*>(lists) + lay.ent_off), lay.nq);
+  return hipGetLastError();
+}
+// the sums over lists that exist: DC = 64 the owner kernel (unless built with -DLC_FTL_OWNER=0), DC = 56 the list kernel
+static hipError_t launch_ss_list_sums(const SuffstatLaunch& a, const SsListLayout& lay, const void* lists, hipStream_t stream) {
+  if (a.DC == 56) return lay.wide ? launch_ss_list_i<64, 56, unsigned>(a, lay, lists, stream) : launch_ss_list_i<64, 56, unsigned short>(a, lay, lists, stream);
+  if (suffstat_owner_instance(a.DP, a.DC)) return lay.wide ? launch_ss_owner_i<unsigned>(a, lay, lists, stream) : launch_ss_owner_i<unsigned short>(a, lay, lists, stream);
+  return lay.wide ? launch_ss_list_i<64, 64, unsigned>(a, lay, lists, stream) : launch_ss_list_i<64, 64, unsigned short>(a, lay, lists, stream);
+}
 hipError_t launch_suffstat_lists(const SuffstatLaunch& a, const SuffstatPlan& p, void* lists, size_t bytes, hipStream_t stream) {
   SsListLayout lay;
   if (hipError_t e = ss_list_check(a, p, lists, bytes, &lay); e != hipSuccess) return e;
   if (hipError_t e = launch_suffstat_list_build(a, p, lists, bytes, stream); e != hipSuccess) return e;
-  const bool narrow = a.DC == 56;
-  if (lay.wide) return narrow ? launch_ss_list_i<64, 56, unsigned>(a, lay, lists, stream) : launch_ss_list_i<64, 64, unsigned>(a, lay, lists, stream);
-  return narrow ? launch_ss_list_i<64, 56, unsigned short>(a, lay, lists, stream)
-                : launch_ss_list_i<64, 64, unsigned short>(a, lay, lists, stream);
+  return launch_ss_list_sums(a, lay, lists, stream);
 }
 
 // ---- the lists from the kept-quad masks of the E-step that wrote qZ (EstepLaunch::qmask) ------------------------------------
@@ -1676,10 +1838,7 @@ hipError_t launch_suffstat_lists_masks(const SuffstatLaunch& a, const SuffstatPl
   SsListLayout lay;
   if (hipError_t e = launch_suffstat_list_build_masks(a, p, qmask, nrg, lists, bytes, stream); e != hipSuccess) return e;
   if (hipError_t e = ss_list_check(a, p, lists, bytes, &lay); e != hipSuccess) return e;
-  const bool narrow = a.DC == 56;
-  if (lay.wide) return narrow ? launch_ss_list_i<64, 56, unsigned>(a, lay, lists, stream) : launch_ss_list_i<64, 64, unsigned>(a, lay, lists, stream);
-  return narrow ? launch_ss_list_i<64, 56, unsigned short>(a, lay, lists, stream)
-                : launch_ss_list_i<64, 64, unsigned short>(a, lay, lists, stream);
+  return launch_ss_list_sums(a, lay, lists, stream);
 }
 
 // ===========================================================================

@@ -856,14 +856,18 @@ LC_HOOK lcx_test_suffstat_speck(const double* X, int DP, int DC, i64 NP, const d
 // as lens_out (io) [nlens >= nchunks * quads] and ent_out (io) [nent >= nchunks * quads * chunk_rows]: segment (chunk, quad)
 // starts at (chunk * quads + quad) * chunk_rows and only its first lens entries are written; -2: a length outside its segment.
 // partial (io), fold / folded (io) as in lc_test_suffstat.  (lcx_: bound by its own test file, like the hook above.)
-LC_HOOK lcx_test_suffstat_lists(const double* X, int DP, int DC, i64 NP, const double* qZ, int K, i64 ldq, int sums, double* partial,
-                                i64 npartial, int fold, double* folded, i64 nfolded, i64* plan_out, int* lens_out, i64 nlens, int* ent_out,
-                                i64 nent) {
+static int test_suffstat_lists(const double* X, int DP, int DC, i64 NP, const double* qZ, int K, i64 ldq, int sums, double* partial,
+                               i64 npartial, int fold, double* folded, i64 nfolded, i64* plan_out, int* lens_out, i64 nlens, int* ent_out,
+                               i64 nent, i64 chunk_rows) {
   if (!X || !qZ || !partial || !plan_out || !lens_out || !ent_out || K < 1 || K > 4096 || !gw_width_ok(DP, DC)) return -1;
-  if (NP < RG || NP % RG || NP > HOT_MAX_NRG * RG || ldq < NP || ldq % 2) return -1;
+  if (NP < RG || NP % RG || NP > HOT_MAX_NRG * RG || ldq < NP || ldq % 2 || chunk_rows < 0 || chunk_rows % lck::SS_BR) return -1;
   const i64 SS = lck::stat_stride(DP);
   if (fold && (!sums || !folded || nfolded < (i64)K * SS)) return -1;
-  const lck::SuffstatPlan p = lck::suffstat_plan(DP, DC, NP, K, lck::SS_DENSE);
+  lck::SuffstatPlan p = lck::suffstat_plan(DP, DC, NP, K, lck::SS_DENSE);
+  if (chunk_rows > 0) {  // (the caller's chunking in place of the plan's: chunks of more than 65536 rows have 32-bit entries)
+    p.chunk_rows = chunk_rows;
+    p.nchunks = (int)((NP + chunk_rows - 1) / chunk_rows);
+  }
   plan_out[0] = p.route, plan_out[1] = p.nchunks, plan_out[2] = p.chunk_rows, plan_out[3] = p.extra, plan_out[4] = p.klast0;
   plan_out[5] = p.KR, plan_out[6] = p.clusters_per_block;
   if (p.nchunks < 1 || p.chunk_rows < lck::SS_BR || p.chunk_rows % lck::SS_BR || (i64)p.nchunks * p.chunk_rows < NP) return -1;
@@ -909,6 +913,22 @@ LC_HOOK lcx_test_suffstat_lists(const double* X, int DP, int DC, i64 NP, const d
     }
   }
   return 0;
+}
+
+LC_HOOK lcx_test_suffstat_lists(const double* X, int DP, int DC, i64 NP, const double* qZ, int K, i64 ldq, int sums, double* partial,
+                                i64 npartial, int fold, double* folded, i64 nfolded, i64* plan_out, int* lens_out, i64 nlens, int* ent_out,
+                                i64 nent) {
+  return test_suffstat_lists(X, DP, DC, NP, qZ, K, ldq, sums, partial, npartial, fold, folded, nfolded, plan_out, lens_out, nlens, ent_out,
+                             nent, 0);
+}
+// The same with the caller's rows per chunk (a multiple of the staging batch; as many chunks as cover NP) in place of the plan's:
+// plan_out [1], [2] report them.  (tests/test_gpu_stats_owner_lists.py: a chunk of more than 65536 rows has 32-bit entries.)
+LC_HOOK lcx_test_suffstat_lists_chunked(const double* X, int DP, int DC, i64 NP, const double* qZ, int K, i64 ldq, i64 chunk_rows,
+                                        double* partial, i64 npartial, double* folded, i64 nfolded, i64* plan_out, int* lens_out, i64 nlens,
+                                        int* ent_out, i64 nent) {
+  if (chunk_rows < 1) return -1;
+  return test_suffstat_lists(X, DP, DC, NP, qZ, K, ldq, 1, partial, npartial, 1, folded, nfolded, plan_out, lens_out, nlens, ent_out, nent,
+                             chunk_rows);
 }
 
 // ---- kept-quad masks (EstepLaunch::qmask; tests/test_gpu_estep_masks.py binds these) -------------------------------------------
@@ -1040,6 +1060,21 @@ LC_HOOK lcx_test_suffstat_list_deal(int DP, int DC, i64* info, int* feat, i64 nf
         int* o = feat + ((size_t)(v * tiles + t) * 16 + l) * 4;
         o[0] = f.u, o[1] = f.w, o[2] = f.kind, o[3] = f.shared;
       }
+  return 0;
+}
+
+// lcx_test_suffstat_owner_deal: the owner kernel's map (lck::fto_feature) evaluated on the host, no device involved.
+// info [3] = diagonals (FTO_DIAGS), accumulators of a lane (FTO_ACCS), 1 if this build routes DC = 64 lists to the owner
+// kernel; feat (io) [nfeat >= FTO_ACCS * 64 * 3]: u, w, kind (FtKind) of lane l of accumulator t at (t * 64 + l) * 3.
+LC_HOOK lcx_test_suffstat_owner_deal(i64* info, int* feat, i64 nfeat) {
+  if (!info || !feat || nfeat < (i64)lck::FTO_ACCS * 64 * 3) return -1;
+  info[0] = lck::FTO_DIAGS, info[1] = lck::FTO_ACCS, info[2] = lck::suffstat_owner_instance(64, 64) ? 1 : 0;
+  for (int t = 0; t < lck::FTO_ACCS; ++t)
+    for (int l = 0; l < 64; ++l) {
+      const lck::FtFeature f = lck::fto_feature(l, t);
+      int* o = feat + ((size_t)t * 64 + l) * 3;
+      o[0] = f.u, o[1] = f.w, o[2] = f.kind;
+    }
   return 0;
 }
 

@@ -171,15 +171,27 @@ def check(asm: str):
 
 
 def check_lists(asm: str):
-    """`--lists [file.s]`: every instance of the statistics pass's list route (suffstat_list_kernel, ss_list_build_kernel in
-    lc_kernels_suffstat.hip) is there and holds no scratch.  Not part of the default run: that file takes minutes to compile."""
+    """`--lists [file.s]`: every instance of the statistics pass's list route (suffstat_list_kernel, suffstat_owner_kernel,
+    ss_list_build_kernel in lc_kernels_suffstat.hip) is there and holds no scratch; the owner kernel keeps four waves per SIMD
+    (at most 128 VGPRs) and its LDS is the four waves' two doubled rows (8 KB), so that four blocks fit a compute unit.  Not
+    part of the default run: that file takes minutes to compile."""
     scratch = dict(re.findall(r"\.amdhsa_kernel\s+(\S+)\s+\.amdhsa_group_segment_fixed_size\s+\d+\s+"
                               r"\.amdhsa_private_segment_fixed_size\s+(\d+)", asm))
-    mine = {n: int(sz) for n, sz in scratch.items() if "suffstat_list_kernel" in n or "ss_list_build_kernel" in n}
+    names = ("suffstat_list_kernel", "suffstat_owner_kernel", "ss_list_build_kernel")
+    mine = {n: int(sz) for n, sz in scratch.items() if any(w in n for w in names)}
     problems = [f"{n}: {sz} bytes of scratch" for n, sz in mine.items() if sz]
-    for want in ("suffstat_list_kernelILi64ELi64E", "suffstat_list_kernelILi64ELi56E", "ss_list_build_kernel"):
+    for want in ("suffstat_list_kernelILi64ELi64E", "suffstat_list_kernelILi64ELi56E", "suffstat_owner_kernelILi64ELi64EtE",
+                 "suffstat_owner_kernelILi64ELi64EjE", "ss_list_build_kernel"):
         if not any(want in n for n in mine):
             problems.append(f"no instance {want} found")
+    lds = {n: int(v) for n, v in re.findall(r"\.amdhsa_kernel\s+(\S+)\s+\.amdhsa_group_segment_fixed_size\s+(\d+)", asm)}
+    vgprs = {n: int(v) for n, v in re.findall(r"\.amdhsa_kernel\s+(\S+)\n(?:[^\n]*\n)*?\s*\.amdhsa_next_free_vgpr\s+(\d+)", asm)}
+    for n in mine:
+        if "suffstat_owner_kernel" in n:
+            if vgprs.get(n, 999) > 128:
+                problems.append(f"{n}: {vgprs.get(n)} VGPRs cost the kernel a wave per SIMD")
+            if lds.get(n) != 4 * 2 * 128 * 8:
+                problems.append(f"{n}: {lds.get(n)} bytes of LDS where the four waves' slots take 8192")
     return problems, len(mine)
 
 

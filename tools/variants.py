@@ -6,7 +6,8 @@ them all in ONE GPU call.
     tools/variants.py run [--shape N,D,K] [--what estep,suffstat,diag] [NAME ...]   # on the GPU box
 
 Switches the device sources know: -DLC_FT_SPECK_LISTS=0, -DLC_FT_SPECK_SORT=0, -DLC_FT_LIST_SHARE64=n, -DLC_FTL_SPREAD=n,
--DLC_FTL_BR=n, -DLC_WIDE_FORCE_STREAM, -DLC_ESTEP_QMASK=0 (no E-step instance emits kept-quad masks: every statistics pass
+-DLC_FTL_BR=n, -DLC_FTL_OWNER=0 (hard rows at DC = 64 summed by the list kernel's MFMAs, as before the owner kernel; -DLC_FTO_DEPTH=n:
+the owner kernel's rows per group in flight), -DLC_WIDE_FORCE_STREAM, -DLC_ESTEP_QMASK=0 (no E-step instance emits kept-quad masks: every statistics pass
 probes and builds its lists from qZ, as before the masks).
 
 `run` starts one child process per variant (LC_LIB_PATH), which synthesises the north-star shape, runs three fixed
