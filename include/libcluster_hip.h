@@ -506,6 +506,35 @@ int lc_model_predict_incomplete_draws(lc_model* m, lc_ctx* ctx, const int* group
 int lc_ctx_get_completed_draws(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* draws, int32_t* label);
 /* ndraws of the last lc_model_predict_incomplete_draws on ctx, 0 when ctx holds no such prediction (never an error for that) */
 int lc_ctx_completed_draws(lc_ctx* ctx, int* ndraws);
+/* ---- leave-one-out conditionals (nothing in the reference corresponds): which value of a row is the odd one.
+ * Gauss-Wishart models only.  ctx holds COMPLETE rows at the model's full width D >= 2.  Block b of ctx is mixed with the
+ * weights of learned group groups[b] (NULL: group 0).  For every row and every column d, with b = {d} the single unknown
+ * column in the notation of lc_model_predict_incomplete above, y = x - m_k, P_k = nu_k iW_k^-1, v = P_k y, s_k, G_k(1), e_k(1)
+ * as in lc_gw_precision and g_k(1) as in lc_gw_precision_var:
+ *   d_a^2    = max(d^2 - v_d^2 / P_k,dd, 0),  t_k,d = log E[pi_jk] + G_k(1) - log(P_k,dd) / 2 - e_k(1) log1p(s_k d_a^2)
+ *   rest_d   = LSE_k t_k,d = log p(x_-d),     r_k,d = exp(t_k,d - rest_d),  M_k,d = x_d - v_d / P_k,dd
+ *   cond[d]  = logp - rest_d = log p(x_d | x_-d, training data)     (logp: lc_model_predict's, bit for bit)
+ *   mean[d]  = x_d + sum_k r_k,d (M_k,d - x_d) = E[x_d | x_-d]
+ *   var[d]   = sum_k r_k,d (g_k(1) nu_k (1 + s_k d_a^2) / P_k,dd + (M_k,d - x_d)^2) - (mean[d] - x_d)^2     (variance != 0)
+ *   worst    = the column with the smallest cond (the lowest column on ties; a NaN is never chosen)
+ * The sum of cond over d is the pseudo-log-likelihood of the row; (x_d - mean[d]) / sqrt(var[d]) a z-score per cell.  All K
+ * clusters take part, also for sparse models, and the prior component of StickBreak weights.  The observations keep every
+ * bit.  Replaces any prediction ctx held (lc_ctx_get_predictions, lc_ctx_get_conditional and lc_ctx_get_completed report
+ * none afterwards, and the ranking and threshold queries refuse it as they refuse an incomplete prediction); a call that
+ * fails leaves none.  The context's qZ holds intermediate values afterwards.  The same bits on every call and wherever a row
+ * sits in its block.
+ * An empty context is LC_OK.  LC_EINVAL: clusters that are not Gauss-Wishart, D mismatch ("Mismatched dims. of cluster
+ * params and obs.!"), D = 1 (no known column is left), a group index outside [0, J), a freed model, and a row that holds a
+ * NaN -- the message names block and row of the first such row in (block, row) order, nothing has been written then, and
+ * rows with unknown values go to lc_model_predict_incomplete.  LC_EDOMAIN (variance != 0 only), before any output: a
+ * component with positive weight in some block has nu - 2 <= 0 (the prior component of StickBreak weights at D = 2, or a
+ * cluster that ended up empty there); the message names the component, and the call without variance still works. */
+int lc_model_predict_leave_one_out(lc_model* m, lc_ctx* ctx, const int* groups /* [J of ctx] or NULL */, int variance);
+/* rows [row0, row0+n) of block j after the last lc_model_predict_leave_one_out on ctx: logp and worst are n values, cond,
+ * mean and var n x D with row_stride doubles between rows (>= D).  Any output may be NULL.  LC_EINVAL: no such prediction on
+ * ctx, var asked of a call made without variance, a row range out of bounds, row_stride < D with cond, mean or var given. */
+int lc_ctx_get_leave_one_out(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* logp, double* cond, double* mean,
+                             double* var, int64_t row_stride, int32_t* worst);
 /* ---- ranking on the device (nothing in the reference corresponds): the m best rows of each of C device-resident
  * columns, 1 <= m <= 64, without bringing the columns to the host.  Entry a is better than entry b when its score is larger
  * (largest != 0; smaller otherwise), or the scores compare equal (+0.0 and -0.0 do) and a comes first in the context (lower

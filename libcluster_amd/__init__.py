@@ -11,6 +11,7 @@ a CPU implementation of the data path.
 from . import capi  # noqa: F401
 from .capi import ConditionalDraws, Sample  # noqa: F401  (what Model.predict_conditional(draws=) and Model.sample return)
 from .capi import CompletionDraws  # noqa: F401  (what Model.predict_incomplete(draws=) returns)
+from .capi import LeaveOneOut, LeaveOneOutVar  # noqa: F401  (what Model.explain returns)
 from .capi import FlaggedRows, ScoreCounts, ScoreQuantiles  # noqa: F401  (what the order and threshold queries return)
 from .api import (learnBEMM, learnBGMM, learnDGMC, learnDGMM, learnEGMC, learnGMC, learnMCM,  # noqa: F401
                   learnSCM, learnSGMC, learnVDP)

@@ -126,6 +126,29 @@ class CompletionDraws(NamedTuple):
 HOLES_MAX = 8  # LC_HOLES_MAX: the NaNs one row may hold
 
 
+class LeaveOneOut(NamedTuple):
+    """Per-row outputs of Model.explain (lc_model_predict_leave_one_out): logp (N,) = log p(x | training data), the bits of
+    Model.predict's; cond_logp (N, D) = log p(x_d | x_-d, training data); mean (N, D) = E[x_d | x_-d]; worst (N,) int32 =
+    the column with the smallest cond_logp (the lowest on ties)."""
+    logp: np.ndarray
+    cond_logp: np.ndarray
+    mean: np.ndarray
+    worst: np.ndarray
+
+    @property
+    def var(self):
+        return None
+
+
+class LeaveOneOutVar(NamedTuple):
+    """LeaveOneOut with var (N, D) = Var[x_d | x_-d]: (x - mean) / sqrt(var) is a z-score per cell."""
+    logp: np.ndarray
+    cond_logp: np.ndarray
+    mean: np.ndarray
+    var: np.ndarray
+    worst: np.ndarray
+
+
 class TopRows(NamedTuple):
     """The m best rows of each of C columns (lc_ctx_top_rows, lc_model_exemplars), best first: count (C,) int32, group
     (C, m) int32 (block of the context / of X), row (C, m) int64 (row of that block), score (C, m); the entries past
@@ -403,6 +426,9 @@ def lib() -> C.CDLL:
     L.lc_model_predict_incomplete_draws.argtypes = [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_uint64]
     L.lc_ctx_get_completed_draws.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, c_int32_p]
     L.lc_ctx_completed_draws.argtypes = [C.c_void_p, c_int_p]
+    L.lc_model_predict_leave_one_out.argtypes = [C.c_void_p, C.c_void_p, c_int_p, C.c_int]
+    L.lc_ctx_get_leave_one_out.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                           c_double_p, C.c_int64, c_int32_p]
     L.lc_model_predict_conditional_draws.argtypes = [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, c_int_p, C.c_int,
                                                      C.c_int, C.c_uint64]
     L.lc_ctx_get_conditional_draws.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, c_int32_p]
@@ -842,6 +868,18 @@ class Context:
         check(lib().lc_ctx_get_completed_var(self._h, j, row0, n, dptr(var), HOLES_MAX))
         return CompletionVar(rows, logp, count, cols, var)
 
+    def get_leave_one_out(self, j, row0, n, variance=False):
+        """Rows [row0, row0+n) of block j after the last Model.explain_context on this context -> LeaveOneOut(logp (n,),
+        cond_logp (n, D), mean (n, D), worst (n,)) (lc_ctx_get_leave_one_out).  variance: LeaveOneOutVar, with var (n, D)
+        (ValueError when that call was made without variance=True)."""
+        D = self.dims()[1]
+        logp, cond, mean = np.zeros(n), np.zeros((n, D)), np.zeros((n, D))
+        var = np.zeros((n, D)) if variance else None
+        worst = np.zeros(n, dtype=np.int32)
+        check(lib().lc_ctx_get_leave_one_out(self._h, j, row0, n, dptr(logp), dptr(cond), dptr(mean),
+                                             dptr(var) if variance else None, D, worst.ctypes.data_as(C.POINTER(C.c_int32))))
+        return LeaveOneOutVar(logp, cond, mean, var, worst) if variance else LeaveOneOut(logp, cond, mean, worst)
+
     def top_rows(self, m, by="qz", largest=True, ncols=None, by_label=False):
         """TopRows of the m best rows (1 ... 64) of each column, ranked on the device (lc_ctx_top_rows): by="qz" the first
         ncols columns of qZ (None: all), by="logz" / "logp" the per-row outputs of the last prediction on this context
@@ -1245,6 +1283,34 @@ class Model:
             self.predict_incomplete_context(ctx, groups, variance, draws, seed)
             out = [ctx.get_completed(j, 0, x.shape[0], variance, draws if draws is not None else False)
                    for j, x in enumerate(Xs)]
+        return out if blocks else out[0]
+
+    # -- leave-one-out conditionals -------------------------------------------------------------------
+    def explain_context(self, ctx, groups=None, variance=False):
+        """Score every column of the complete full-width rows resident in ctx given the row's other columns
+        (lc_model_predict_leave_one_out).  Nothing is downloaded and the rows keep every bit: read the results with
+        ctx.get_leave_one_out.  ValueError for a row that holds a NaN (predict_incomplete takes those).  variance: also
+        Var[x_d | x_-d] (DomainError where a component with weight has nu <= 2)."""
+        g = None
+        if groups is not None:
+            garr = np.ascontiguousarray(groups, dtype=np.int32)
+            if garr.shape != (ctx.dims()[0],):
+                raise ValueError("groups needs one learned group index per block of the context")
+            g = garr.ctypes.data_as(c_int_p)
+        check(lib().lc_model_predict_leave_one_out(self._h, ctx._h, g, 1 if variance else 0))
+
+    def explain(self, X, groups=None, device=0, variance=False):
+        """LeaveOneOut(logp, cond_logp, mean, worst) for the complete host rows X ((N, D) array), or a list of them for a
+        list of blocks (block b mixed with learned group groups[b], default 0): which value of a row disagrees with the
+        row's other values.  variance: LeaveOneOutVar, with var (N, D)."""
+        blocks = isinstance(X, (list, tuple))
+        Xs = self._blocks(X)
+        if not Xs:
+            return []
+        with Context(device) as ctx:
+            ctx.set_data(Xs)
+            self.explain_context(ctx, groups, variance)
+            out = [ctx.get_leave_one_out(j, 0, x.shape[0], variance) for j, x in enumerate(Xs)]
         return out if blocks else out[0]
 
     # -- ranking (DESIGN 4.13) -------------------------------------------------------------------------------------

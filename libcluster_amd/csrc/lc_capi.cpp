@@ -1299,6 +1299,25 @@ int lc_ctx_completed_draws(lc_ctx* ctx, int* ndraws) {
   });
 }
 
+// ---- leave-one-out conditionals -------------------------------------------
+int lc_model_predict_leave_one_out(lc_model* m, lc_ctx* ctx, const int* groups, int variance) {
+  return guarded([&] {
+    need(m, "model");
+    need(ctx, "ctx");
+    ctx->impl.predict_clear();  // (a failure leaves no prediction behind)
+    if (!model_alive(m)) throw std::invalid_argument("the model was freed");
+    lcp::predict_leave_one_out(ctx->impl, m->model, groups, variance != 0);
+  });
+}
+
+int lc_ctx_get_leave_one_out(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* logp, double* cond, double* mean,
+                             double* var, int64_t row_stride, int32_t* worst) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.get_leave_one_out(j, row0, n, logp, cond, mean, var, row_stride, worst);
+  });
+}
+
 // ---- ranking -----------------------------------------------------
 int lc_ctx_top_rows(lc_ctx* ctx, int what, int ncols, int m, int largest, int by_label, int32_t* count, int32_t* group,
                     int64_t* row, double* score) {

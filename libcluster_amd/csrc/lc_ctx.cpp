@@ -270,6 +270,8 @@ void Context::build_layout(int J, const int64_t* Nj, int D) {
   pred_holes_var_ = false;
   pred_holes_draws_ = 0;
   pred_cond_draws_ = 0;
+  pred_loo_ = false;
+  pred_loo_var_ = false;
   sampled_ = false;               // (the rows no longer come from sample(): it sets the flag after its launch)
   pred_docs_T_ = 0;               // (... and the per-document ones to the old documents)
   LC_HIP(hipSetDevice(device_));

@@ -294,6 +294,8 @@ class Context {
     pred_holes_var_ = false;
     pred_holes_draws_ = 0;
     pred_cond_draws_ = 0;
+    pred_loo_ = false;
+    pred_loo_var_ = false;
   }
   // Conditional prediction: after a raw E-step with zero constants over the context's (given) columns left
   // Kp columns in qZ, per row E[x_target | x_given] (Db columns) and log p(x_given) into the context's conditional outputs
@@ -337,6 +339,8 @@ class Context {
   // (lck::HolesDrawsLaunch), in buffers that only such a call reserves; qZ then holds t_k for the rows with holes.
   void holes_scan(int64_t* holed_rows, int* max_count, int* bad_block, int64_t* bad_row, int* bad_count);
   void holes_fill(const double* fill);
+  // after holes_scan: the first row (in block, row order) with at least one hole (*block = -1: none)
+  void first_holed_row(int* block, int64_t* row) const;
   void predict_holes(int Kp, const double* tt, const double* ps, const double* pe, const double* mean, const double* P,
                      const double* gnu = nullptr, const double* cqnu = nullptr, int ndraws = 0, uint64_t seed = 0);
   // rows [row0, row0+n) of group j after the last predict_holes (any output may be null): the completed rows (row_stride
@@ -350,6 +354,17 @@ class Context {
   // every draw [n x ndraws] (-1 in a row without holes); either may be null: throws when the last predict_holes drew none
   void get_completed_draws(int j, int64_t row0, int64_t n, double* draws, int32_t* label) const;
   int completed_draws() const { return pred_holes_ ? pred_holes_draws_ : 0; }  // draws per row held (0: none)
+  // Leave-one-out conditionals, after holes_scan found no hole and a raw E-step with zero constants over the
+  // complete rows left Kp columns in qZ: log p(x) per row (predict_rows_kernel over the nb = 0 tables pc J x Kp, ps Kp, pe0
+  // Kp), then per row and column the conditional log density, mean and -- gnu1 not null -- variance (lck::LooRowsLaunch for
+  // the tables: tt1 J x Kp, pe1 Kp, gnu1 Kp, mean Kp x D, P Kp x D x D host arrays; log(P_dd) / 2 and 1 / P_dd are formed
+  // here), then the worst column per row.  qZ is left holding the raw columns; X is only read.
+  void predict_loo(int Kp, const double* pc, const double* ps, const double* pe0, const double* tt1, const double* pe1,
+                   const double* gnu1, const double* mean, const double* P);
+  // rows [row0, row0+n) of group j of the last predict_loo (any output may be null): logp and worst [n]; cond, mean and var
+  // [n x D], row_stride >= D doubles apart; throws for var when the last predict_loo had no gnu1
+  void get_leave_one_out(int j, int64_t row0, int64_t n, double* logp, double* cond, double* mean, double* var,
+                         int64_t row_stride, int32_t* worst) const;
   // ---- ranking ----------------------------------------------------------------------------------------------
   // The m best rows of each column (lck::TopRowsLaunch for the order): what = 0 the first ncols columns of qZ, 1 / 2 the
   // logZ / logp of the last prediction (one column; ncols is not looked at).  by_label: column c only sees the rows the
@@ -578,6 +593,12 @@ class Context {
   DevBuf<double> hdraws_;
   DevBuf<int> hdlabel_;
   int pred_holes_draws_ = 0;
+  // ... of the last leave-one-out prediction: log p(x) [NP], cond and mean [NP x DP], the worst column and its value [NP]
+  // and, when pred_loo_var_, the variance [NP x DP]
+  DevBuf<double> llogp_, lcond_, lmean_, lvar_, lworstv_;
+  DevBuf<int> lworst_;
+  bool pred_loo_ = false;
+  bool pred_loo_var_ = false;
   // top_rows: the first stage's partial lists and the result [C x m scores | C x m positions]; the order and threshold
   // queries keep their integer scratch and results in toppos_ and the flagged rows' scores in topkey_
   DevBuf<double> topkey_, topout_;

@@ -398,6 +398,24 @@ void Context::holes_scan(int64_t* holed_rows, int* max_count, int* bad_block, in
   *bad_count = cnt;
 }
 
+void Context::first_holed_row(int* block, int64_t* row) const {
+  use_device();
+  *block = -1;
+  *row = -1;
+  if (NP_ == 0) return;
+  if (!hcount_.p) throw std::logic_error("first_holed_row: no hole records");
+  std::vector<int> cnt((size_t)NP_);  // (an error path: the counts come to the host whole)
+  LC_HIP(hipMemcpyAsync(cnt.data(), hcount_.p, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+  for (int j = 0; j < J_; ++j)
+    for (int64_t r = 0; r < Nj_[(size_t)j]; ++r)  // (the counts of pad rows are not written: valid rows only)
+      if (cnt[(size_t)(goff_[(size_t)j] + r)] > 0) {
+        *block = j;
+        *row = r;
+        return;
+      }
+}
+
 void Context::holes_fill(const double* fill) {
   use_device();
   if (NP_ == 0) return;
@@ -561,6 +579,134 @@ void Context::get_completed(int j, int64_t row0, int64_t n, double* rows, int64_
   if (cols)
     LC_HIP(hipMemcpyAsync(cols, hcols_.p + at * lck::HOLES_MAX, (size_t)n * lck::HOLES_MAX * sizeof(int),
                           hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+}
+
+void Context::predict_loo(int Kp, const double* pc, const double* ps, const double* pe0, const double* tt1, const double* pe1,
+                          const double* gnu1, const double* mean, const double* P) {
+  use_device();
+  if (Kp < 1) throw std::invalid_argument("K must be >= 1");
+  pred_loo_ = false;
+  pred_loo_var_ = false;
+  if (NP_ == 0) {
+    pred_loo_ = true;
+    pred_loo_var_ = gnu1 != nullptr;
+    return;
+  }
+  if (qz_[cur_].cap < Kp || !qz_[cur_].buf.p) throw std::logic_error("predict_loo: no raw E-step columns");
+  const int D = D_, DP = DP_;
+  const size_t NP = (size_t)NP_;
+  llogp_.reserve(NP);
+  lcond_.reserve(NP * DP);
+  lmean_.reserve(NP * DP);
+  if (gnu1) lvar_.reserve(NP * DP);
+  lworst_.reserve(NP);
+  lworstv_.reserve(NP);
+  // tables: [pc J x Kp | ps Kp | pe0 Kp | tt1 J x Kp | pe1 Kp | gnu1 Kp | mean Kp x DP | hlogp Kp x DP | ipd Kp x DP |
+  // P Kp x DP x DP], the pads zero
+  const size_t nt = (size_t)J_ * Kp, nm = (size_t)Kp * DP, nP = nm * DP;
+  hpack_.assign(2 * nt + 4 * (size_t)Kp + 3 * nm + nP, 0.0);
+  double* h = hpack_.data();
+  std::copy(pc, pc + nt, h);
+  std::copy(ps, ps + Kp, h + nt);
+  std::copy(pe0, pe0 + Kp, h + nt + Kp);
+  double* ht1 = h + nt + 2 * (size_t)Kp;
+  std::copy(tt1, tt1 + nt, ht1);
+  std::copy(pe1, pe1 + Kp, ht1 + nt);
+  if (gnu1) std::copy(gnu1, gnu1 + Kp, ht1 + nt + Kp);
+  double* hm = ht1 + nt + 2 * (size_t)Kp;
+  double *hl = hm + nm, *hi = hl + nm, *hP = hi + nm;
+  for (int k = 0; k < Kp; ++k) {
+    std::copy(mean + (size_t)k * D, mean + (size_t)(k + 1) * D, hm + (size_t)k * DP);
+    for (int r = 0; r < D; ++r) {
+      std::copy(P + ((size_t)k * D + r) * D, P + ((size_t)k * D + r + 1) * D, hP + ((size_t)k * DP + r) * DP);
+      const double pdd = P[((size_t)k * D + r) * D + r];  // (> 0: the diagonal of a positive definite matrix)
+      hl[(size_t)k * DP + r] = 0.5 * std::log(pdd);
+      hi[(size_t)k * DP + r] = 1.0 / pdd;
+    }
+  }
+  ptab_.reserve(hpack_.size());
+  LC_HIP(hipMemcpyAsync(ptab_.p, hpack_.data(), hpack_.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+  const double* d1 = ptab_.p + nt + 2 * (size_t)Kp;
+  // log p(x): predict_rows_kernel over the nb = 0 tables with no VB column (its label and logZ outputs go to the buffers
+  // the worst column and its value overwrite below)
+  lck::PredictRowsLaunch r;
+  r.col = qz_[cur_].buf.p;
+  r.qcol = qz_[cur_].buf.p;
+  r.ldq = NP_;
+  r.K = 0;
+  r.Kp = Kp;
+  r.nrg = NP_ / lck::RG;
+  r.rginfo = J_ > 1 ? rginfo_.p : nullptr;
+  r.nrows = Nj_[0];
+  r.ctab = ptab_.p;
+  r.ptab = ptab_.p;
+  r.pscale = ptab_.p + nt;
+  r.pexp = ptab_.p + nt + Kp;
+  r.keep_q = 0;
+  r.label = lworst_.p;
+  r.logZ = lworstv_.p;
+  r.logp = llogp_.p;
+  LC_HIP(lck::launch_predict_rows(r, stream_));
+  lck::LooRowsLaunch a;
+  a.X = X_.p;
+  a.DP = DP;
+  a.D = D;
+  a.Kp = Kp;
+  a.col = qz_[cur_].buf.p;
+  a.ldq = NP_;
+  a.nrg = r.nrg;
+  a.rginfo = r.rginfo;
+  a.nrows = r.nrows;
+  a.ttab = d1;
+  a.pscale = r.pscale;
+  a.pexp = d1 + nt;
+  a.gnu = gnu1 ? d1 + nt + Kp : nullptr;
+  a.mean = d1 + nt + 2 * (size_t)Kp;
+  a.hlogp = a.mean + nm;
+  a.ipd = a.hlogp + nm;
+  a.P = a.ipd + nm;
+  a.logp = llogp_.p;
+  a.cond = lcond_.p;
+  a.cmean = lmean_.p;
+  a.var = gnu1 ? lvar_.p : nullptr;
+  LC_HIP(lck::launch_loo_rows(a, stream_));
+  lck::LooWorstLaunch w;
+  w.cond = lcond_.p;
+  w.DP = DP;
+  w.D = D;
+  w.nrg = r.nrg;
+  w.rginfo = r.rginfo;
+  w.nrows = r.nrows;
+  w.worst = lworst_.p;
+  w.value = lworstv_.p;
+  LC_HIP(lck::launch_loo_worst(w, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ and ptab_ are free again)
+  qz_[cur_].K = Kp;
+  qz_[cur_].hash_ok = false;
+  qz_written(qz_[cur_]);
+  pred_loo_ = true;
+  pred_loo_var_ = gnu1 != nullptr;
+}
+
+void Context::get_leave_one_out(int j, int64_t row0, int64_t n, double* logp, double* cond, double* mean, double* var,
+                                int64_t row_stride, int32_t* worst) const {
+  use_device();
+  if (!pred_loo_) throw std::invalid_argument("the context holds no leave-one-out prediction (lc_model_predict_leave_one_out)");
+  if (var && !pred_loo_var_)
+    throw std::invalid_argument("the context's leave-one-out prediction has no variance (lc_model_predict_leave_one_out "
+                                "with variance != 0)");
+  if (j < 0 || j >= J_ || row0 < 0 || n < 0 || row0 + n > Nj_[j]) throw std::invalid_argument("row range out of bounds");
+  if ((cond || mean || var) && row_stride < D_) throw std::invalid_argument("row_stride is smaller than the number of columns");
+  if (n == 0) return;
+  const size_t at = (size_t)(goff_[j] + row0);
+  static_assert(sizeof(int) == sizeof(int32_t), "the worst columns are int32");
+  const size_t dpitch = (size_t)row_stride * sizeof(double), spitch = (size_t)DP_ * sizeof(double), w = (size_t)D_ * sizeof(double);
+  if (cond) LC_HIP(hipMemcpy2DAsync(cond, dpitch, lcond_.p + at * DP_, spitch, w, (size_t)n, hipMemcpyDeviceToHost, stream_));
+  if (mean) LC_HIP(hipMemcpy2DAsync(mean, dpitch, lmean_.p + at * DP_, spitch, w, (size_t)n, hipMemcpyDeviceToHost, stream_));
+  if (var) LC_HIP(hipMemcpy2DAsync(var, dpitch, lvar_.p + at * DP_, spitch, w, (size_t)n, hipMemcpyDeviceToHost, stream_));
+  if (logp) LC_HIP(hipMemcpyAsync(logp, llogp_.p + at, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  if (worst) LC_HIP(hipMemcpyAsync(worst, lworst_.p + at, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, stream_));
   LC_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -1333,6 +1479,97 @@ void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* g
   }
   ctx.predict_holes(Kp, tt.data(), ps.data(), pe.data(), m.data(), P.data(), want_var ? gnu.data() : nullptr,
                     ndraws > 0 ? cqnu.data() : nullptr, ndraws, seed);
+}
+
+void predict_leave_one_out(lcc::Context& ctx, const lce::Model& model, const int* groups, bool want_var) {
+  ctx.predict_clear();  // (whatever an earlier prediction left must not outlive a failure of this one)
+  constexpr int NH = lck::HOLES_MAX + 1;
+  const int K = (int)model.clusters.size(), J = (int)model.weights.size(), Jc = ctx.J();
+  if (K < 1) throw std::invalid_argument("the model has no clusters");
+  if (model.ckind != lch::C_GAUSSWISH)
+    throw std::invalid_argument("leave-one-out conditionals need Gauss-Wishart clusters: the columns of NormGamma / ExpGamma "
+                                "clusters are independent within a cluster (not supported)");
+  const int D = model.clusters[0].gw.D;
+  if (Jc > 0 && ctx.D() != D) throw std::invalid_argument("Mismatched dims. of cluster params and obs.!");
+  if (D < 2) throw std::invalid_argument("leave-one-out conditionals need D >= 2: with one column no known column is left");
+  for (int b = 0; b < Jc; ++b) {
+    const int j = groups ? groups[b] : 0;
+    if (j < 0 || j >= J) throw std::invalid_argument("group index out of range");
+  }
+  if (Jc < 1) return;  // (a context without observations: nothing to score)
+  if (ctx.DP() > lck::GW_MAX_DP)
+    throw std::invalid_argument("D > 1024 is not supported by the Gauss-Wishart kernels (the diagonal and exponential "
+                                "families take any D)");
+  std::vector<double> Epi((size_t)J * K), Erest((size_t)J);
+  bool rest = false;
+  for (int j = 0; j < J; ++j) {
+    if ((int)model.weights[(size_t)j].alpha1.size() != K) throw std::invalid_argument("weights and clusters disagree");
+    weights_predictive(model.weights[(size_t)j], Epi.data() + (size_t)j * K, &Erest[(size_t)j]);
+    rest = rest || Erest[(size_t)j] > 0.0;
+  }
+  const int Kp = K + (rest ? 1 : 0);
+  const lch::ClusterAny prior(model.ckind, model.clusters[0].prior(), D);  // clearobs state: a cluster that saw no data
+  // nb = 0: predict()'s own constants, so that logp is its logp to the bit; nb = 1: the row of predict_incomplete's tables
+  std::vector<double> P((size_t)Kp * D * D), ps((size_t)Kp), pe0((size_t)Kp), pe1((size_t)Kp), lc0((size_t)Kp), G1((size_t)Kp);
+  std::vector<double> A((size_t)Kp * D * D), m((size_t)Kp * D), gnu1;
+  if (want_var) gnu1.assign((size_t)Kp, 0.0);
+  for (int k = 0; k < Kp; ++k) {
+    const lch::GaussWishState& g = k < K ? model.clusters[(size_t)k].gw : prior.gw;
+    double G[NH], e[NH], s;
+    gw_precision(D, g.nu, g.beta, g.iW.data(), P.data() + (size_t)k * D * D, G, &s, e);
+    const Predictive p0 = gw_predictive(g);
+    lc0[(size_t)k] = p0.lc;
+    ps[(size_t)k] = p0.s;
+    pe0[(size_t)k] = p0.e;
+    G1[(size_t)k] = G[1];
+    pe1[(size_t)k] = e[1];
+    const std::vector<double> Ak = g.whitener();
+    std::copy(Ak.begin(), Ak.end(), A.begin() + (size_t)k * D * D);
+    std::copy(g.m.begin(), g.m.end(), m.begin() + (size_t)k * D);
+    if (want_var) {
+      // the check of DESIGN 4.15.1 with cmax = 1: g_k(1) = (1 + beta) / (beta (nu - 2)) has to exist wherever a row can meet it
+      if (!(g.nu - 2 > 0.0)) {
+        bool weighted = false;
+        for (int b = 0; b < Jc; ++b) {
+          const int j = groups ? groups[b] : 0;
+          weighted = weighted || (k < K ? Epi[(size_t)j * K + k] : Erest[(size_t)j]) > 0.0;
+        }
+        if (weighted)
+          throw std::domain_error("the leave-one-out variance does not exist: " +
+                                  (k < K ? "cluster " + std::to_string(k) : std::string("the prior component")) +
+                                  " has nu - 2 = " + std::to_string(g.nu - 2) +
+                                  ", which is not above 0 (lc_model_predict_leave_one_out without variance does exist)");
+      } else {
+        double gk[NH];
+        gw_precision_var(D, g.nu, g.beta, gk);
+        gnu1[(size_t)k] = gk[1] * g.nu;
+      }
+    }
+  }
+  std::vector<double> pc((size_t)Jc * Kp), tt1((size_t)Jc * Kp), zero((size_t)Jc * Kp, 0.0);
+  for (int b = 0; b < Jc; ++b) {
+    const int j = groups ? groups[b] : 0;
+    for (int k = 0; k < Kp; ++k) {
+      const double lw = std::log(k < K ? Epi[(size_t)j * K + k] : Erest[(size_t)j]);
+      pc[(size_t)b * Kp + k] = lw + lc0[(size_t)k];
+      tt1[(size_t)b * Kp + k] = lw + G1[(size_t)k];
+    }
+  }
+  int64_t holed = 0, bad_row = -1;
+  int max_count = 0, bad_block = -1, bad_count = 0;
+  ctx.holes_scan(&holed, &max_count, &bad_block, &bad_row, &bad_count);
+  if (holed > 0) {  // (nothing was written so far)
+    int64_t row = -1;
+    int block = -1;
+    ctx.first_holed_row(&block, &row);
+    throw std::invalid_argument("row " + std::to_string(row) + " of block " + std::to_string(block) +
+                                " holds an unknown value (NaN): leave-one-out conditionals need complete rows "
+                                "(lc_model_predict_incomplete takes rows with unknown values)");
+  }
+  // one raw E-step at full width over the K clusters (+ the prior's whitener), as predict() runs it: -d^2 / 2 per column
+  ctx.estep(Kp, A.data(), m.data(), zero.data(), nullptr, nullptr, /*raw=*/true);
+  ctx.predict_loo(Kp, pc.data(), ps.data(), pe0.data(), tt1.data(), pe1.data(), want_var ? gnu1.data() : nullptr, m.data(),
+                  P.data());
 }
 
 void exemplars(lcc::Context& ctx, const lce::Model& model, bool sparse, const int* groups, int mtop, int32_t* count,

@@ -268,6 +268,59 @@ struct HolesDrawsLaunch {
 };
 hipError_t launch_holes_draws(const HolesDrawsLaunch& a, hipStream_t stream);
 
+// ---- leave-one-out conditionals (lc_kernels_loo.hip) ----------------------------------------------------------------
+// loo_rows_kernel<VAR>: after a raw E-step over COMPLETE rows left -d^2 / 2 in column k and predict_rows_kernel left logp, per
+// valid row and column d < D, with y = x - m_k, v = P_k y (one GEMM per cluster on the matrix pipe, the full contraction):
+//   d_a^2 = max(d^2 - v_d^2 / P_k,dd, 0),  t_k,d = ttab[j][k] - hlogp[k][d] - pexp[k] log1p(s_k d_a^2),  delta_k,d = -v_d / P_k,dd
+//   rest_d = LSE_k t_k,d,  r_k,d = exp(t_k,d - rest_d),  cond[row][d] = logp[row] - rest_d
+//   cmean[row][d] = x_d + sum_k r_k,d delta_k,d
+//   var[row][d] = sum_k r_k,d (gnu[k] (1 + s_k d_a^2) / P_k,dd + delta_k,d^2) - (cmean[row][d] - x_d)^2          (VAR: var != null)
+// A wave owns LOO_WAVE_ROWS rows and a panel of LOO_PANEL output columns (grid y: the panels) and folds the clusters in
+// ascending order into a running (max, sum e, sum e delta, sum e (Cov + delta^2)) per element.  No atomics, no scratch, the
+// order of every sum fixed: the same bits on every call and wherever a row sits.  Pad rows and pad columns are not written.
+constexpr int LOO_THREADS = 256;    // four waves, each on its own rows
+constexpr int LOO_WAVE_ROWS = 32;   // two row groups of 16
+constexpr int LOO_PANEL = 16;       // output columns whose running state is resident: 4 quads
+struct LooRowsLaunch {
+  const double* X = nullptr;  // [NP x DP] complete rows
+  int DP = 0;
+  int D = 0;
+  int Kp = 0;
+  const double* col = nullptr;  // [Kp columns x ldq] raw E-step
+  int64_t ldq = 0;
+  int64_t nrg = 0;
+  const int* rginfo = nullptr;
+  int64_t nrows = 0;
+  const double* ttab = nullptr;    // [J x Kp] log E[pi_jk] + G_k(1)
+  const double* pscale = nullptr;  // [Kp] s_k
+  const double* pexp = nullptr;    // [Kp] e_k(1)
+  const double* gnu = nullptr;     // [Kp] g_k(1) nu_k; 0 for a component without weight whose variance does not exist (VAR)
+  const double* mean = nullptr;    // [Kp x DP] m_k, pad columns zero
+  const double* P = nullptr;       // [Kp x DP x DP] P_k, pad rows and columns zero
+  const double* hlogp = nullptr;   // [Kp x DP] log(P_k,dd) / 2, pad columns zero
+  const double* ipd = nullptr;     // [Kp x DP] 1 / P_k,dd, pad columns zero (no division on the device)
+  const double* logp = nullptr;    // [NP] log p(x), predict_rows_kernel's
+  double* cond = nullptr;          // [NP x DP]
+  double* cmean = nullptr;         // [NP x DP]
+  double* var = nullptr;           // [NP x DP] or null
+};
+hipError_t launch_loo_rows(const LooRowsLaunch& a, hipStream_t stream);
+
+// loo_worst_kernel: per valid row worst[row] = the column d < D with the smallest cond[row][d] (the lowest column on ties; a
+// NaN is never chosen; -1 when every entry is NaN) and value[row] = that entry (NaN with -1).  16 / 32 / 64 lanes read one row,
+// as in holes_scan_kernel.
+struct LooWorstLaunch {
+  const double* cond = nullptr;  // [NP x DP]
+  int DP = 0;
+  int D = 0;
+  int64_t nrg = 0;
+  const int* rginfo = nullptr;
+  int64_t nrows = 0;
+  int* worst = nullptr;     // [NP]
+  double* value = nullptr;  // [NP]
+};
+hipError_t launch_loo_worst(const LooWorstLaunch& a, hipStream_t stream);
+
 }  // namespace lck
 
 namespace lch {
@@ -348,6 +401,14 @@ void predict_incomplete(lcc::Context& ctx, const lce::Model& model, const int* g
 // lck::HOLES_MAX holes, so that cluster k's conditional covariance is g[nb] (1 + s d_a^2) nu (P_bb)^-1; NaN where nb >= D or
 // nu - 1 - nb <= 0.  Throws std::invalid_argument for nu <= D - 1, beta <= 0.
 void gw_precision_var(int D, double nu, double beta, double* g);
+// Leave-one-out conditionals of the COMPLETE rows in ctx (the model's full width): per row n and column d
+// log p(x_d | x_-d, training data), E[x_d | x_-d] and, with want_var, Var[x_d | x_-d]; log p(x) per row (the bits of
+// predict()'s logp) and the column with the smallest conditional log density (Context::get_leave_one_out).  Gauss-Wishart
+// models only; all K clusters take part (and the prior component of StickBreak weights).  The observations keep every bit.
+// Throws std::invalid_argument, with nothing written, for a row that holds a NaN (naming block and row), D = 1, and the
+// argument cases of predict_incomplete; std::domain_error, before any output, when want_var meets a component with weight
+// in some block whose nu - 2 <= 0 (the check of DESIGN 4.15.1 with cmax = 1).
+void predict_leave_one_out(lcc::Context& ctx, const lce::Model& model, const int* groups, bool want_var = false);
 // E[pi_k] (K values) and the mass beyond the truncation E[pi_rest] of a weight distribution in its updated state:
 //   Dirichlet:  alpha_k / sum(alpha), no rest
 //   StickBreak: E[v_k] prod_{i before k} E[1 - v_i] in ordvec order (distributions.cpp:139-165), rest prod_i E[1 - v_i]

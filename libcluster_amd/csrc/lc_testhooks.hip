@@ -563,6 +563,66 @@ LC_HOOK lc_test_predict_cond(const double* X, int DP, int Da, int Dae, int Db, i
   return s.finish(lck::launch_predict_cond(a, nullptr));
 }
 
+// (lcx_: tests/aux_hooks.py declares every lc_test_* export, and this one is bound by its own test file.)
+// launch_loo_rows, then (worst and value given) launch_loo_worst on what it left (lc_kernels_loo.hip; tests/test_gpu_loo_kernels.py).
+// X [nrg * 16 x DP]; col [Kp x ldq]; ttab [J x Kp]; pscale / pexp [Kp]; gnu [Kp] or null (no variance: var has to be null
+// too); mean / hlogp / ipd [Kp x DP]; P [Kp x DP x DP]; logp [nrg * 16].  cond, cmean and var (io) are guard + nrg * 16 * DP +
+// guard doubles, worst (io) guard + nrg * 16 + guard ints and value (io) as many doubles: the kernels see the middle part, the
+// guards come back as they went in.
+LC_HOOK lcx_test_loo_rows(const double* X, int DP, int D, int Kp, const double* col, i64 ldq, i64 nrg, const int* rginfo, i64 nrows,
+                          int J, const double* ttab, const double* pscale, const double* pexp, const double* gnu,
+                          const double* mean, const double* P, const double* hlogp, const double* ipd, const double* logp,
+                          i64 guard, double* cond, double* cmean, double* var, int* worst, double* value) {
+  if (!X || !col || !ttab || !pscale || !pexp || !mean || !P || !hlogp || !ipd || !logp || !cond || !cmean) return -1;
+  if ((var != nullptr) != (gnu != nullptr) || (worst != nullptr) != (value != nullptr)) return -1;
+  if (!pred_rows_ok(nrg, ldq, rginfo, nrows, J) || (!rginfo && J != 1)) return -1;
+  if (Kp < 1 || Kp > 4096 || D < 1 || DP < D || DP > 4096 || DP % 16 != 0 || guard < 0 || guard > (1 << 20)) return -1;
+  const size_t NP = (size_t)(nrg * RG), G = (size_t)guard;
+  Scope s;
+  lck::LooRowsLaunch a;
+  a.X = s.in(X, NP * DP);
+  a.DP = DP;
+  a.D = D;
+  a.Kp = Kp;
+  a.col = s.in(col, (size_t)Kp * (size_t)ldq);
+  a.ldq = ldq;
+  a.nrg = nrg;
+  a.rginfo = rginfo ? s.in(rginfo, (size_t)nrg) : nullptr;
+  a.nrows = nrows;
+  a.ttab = s.in(ttab, (size_t)J * Kp);
+  a.pscale = s.in(pscale, (size_t)Kp);
+  a.pexp = s.in(pexp, (size_t)Kp);
+  a.gnu = gnu ? s.in(gnu, (size_t)Kp) : nullptr;
+  a.mean = s.in(mean, (size_t)Kp * DP);
+  a.P = s.in(P, (size_t)Kp * DP * DP);
+  a.hlogp = s.in(hlogp, (size_t)Kp * DP);
+  a.ipd = s.in(ipd, (size_t)Kp * DP);
+  a.logp = s.in(logp, NP);
+  double* dcond = s.io(cond, NP * DP + 2 * G);
+  double* dmean = s.io(cmean, NP * DP + 2 * G);
+  double* dvar = var ? s.io(var, NP * DP + 2 * G) : nullptr;
+  int* dworst = worst ? s.io(worst, NP + 2 * G) : nullptr;
+  double* dvalue = value ? s.io(value, NP + 2 * G) : nullptr;
+  if (!s.ok()) return s.finish(hipSuccess);
+  a.cond = dcond + G;
+  a.cmean = dmean + G;
+  a.var = dvar ? dvar + G : nullptr;
+  hipError_t e = lck::launch_loo_rows(a, nullptr);
+  if (e == hipSuccess && worst) {
+    lck::LooWorstLaunch w;
+    w.cond = a.cond;
+    w.DP = DP;
+    w.D = D;
+    w.nrg = nrg;
+    w.rginfo = a.rginfo;
+    w.nrows = nrows;
+    w.worst = dworst + G;
+    w.value = dvalue + G;
+    e = lck::launch_loo_worst(w, nullptr);
+  }
+  return s.finish(e);
+}
+
 // ---- document inference (lc_kernels_topic.hip) ----------------------------------------------------------------------------------
 // topic_infer_lds itself: the bytes of dynamic LDS (0: K and T do not fit; *tile_cap and *e_lds are then untouched)
 LC_HOOK lc_test_topic_plan(int K, int T, int threads, const i64* nrows, int docs, i64* tile_cap, int* e_lds) {
