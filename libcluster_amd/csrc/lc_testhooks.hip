@@ -7,7 +7,12 @@
 // Python side: tests/aux_hooks.py; cases: tests/test_gpu_aux_kernels.py, tests/test_gpu_predict_kernels.py for the
 // launchers of lc_kernels_predict.hip and lc_kernels_topic.hip, tests/test_gpu_launch_plans.py for the two launch plans, and
 // tests/test_gpu_hot_kernels.py for launch_estep, launch_suffstat (with launch_fold_extra) and launch_fused, and
-// tests/test_gpu_diag_kernels.py for launch_estep_diag, launch_suffstat_diag and the host packer at the end of this file.
+// tests/test_gpu_diag_kernels.py for launch_estep_diag, launch_suffstat_diag and the host packer.  Hooks named lcx_test_* are
+// bound by their own test files: lcx_test_loo_rows (tests/test_gpu_loo_kernels.py), the statistics list hooks
+// (tests/test_gpu_stats_lists.py and its neighbours) and, at the end of this file, the six launchers of lc_kernels_holes.hip:
+// lcx_test_holes_scan (launch_holes_scan, launch_holes_fill), lcx_test_predict_holes (launch_predict_holes / _var / _keep) and
+// lcx_test_holes_draws (launch_predict_holes_keep, launch_holes_draws), cases in tests/test_gpu_holes_kernels.py (inputs:
+// tests/holes_kernel_cases.py, held to their conditions without a device by tests/test_holes_kernels_refs_host.py).
 #include <algorithm>
 #include <cstdio>
 #include <vector>
@@ -1331,3 +1336,173 @@ LC_HOOK lc_test_diag_pack(int D, int DP, int K, int mode, const double* a_, cons
 
 // estep_diag_mfma_weights itself (no device)
 LC_HOOK lc_test_diag_weights(int DP, int K, int mode) { return (int)lck::estep_diag_mfma_weights(DP, K, mode); }
+
+// ---- rows with holes (lc_kernels_holes.hip; tests/test_gpu_holes_kernels.py binds these) -----------------------------------------
+namespace {
+
+// row_valid (lc_device.hpp) on the host
+bool host_row_valid(i64 row, const int* rginfo, i64 nrows, int& j) {
+  const i64 g = row / RG;
+  const int r = (int)(row - g * RG);
+  j = rginfo ? rginfo[g] >> 5 : 0;
+  const i64 rem = nrows - g * RG;
+  const int nv = rginfo ? rginfo[g] & 31 : rem >= RG ? RG : rem > 0 ? (int)rem : 0;
+  return r < nv;
+}
+
+// the hole records as predict_holes_kernel and holes_draws_kernel address X, P and their tables with them: per valid row
+// 0 <= count <= HOLES_MAX and count < D, cols[0 .. count) ascending inside [0, D)
+bool hole_records_ok(const int* count, const int* cols, i64 nrg, const int* rginfo, i64 nrows, int D) {
+  for (i64 row = 0; row < nrg * RG; ++row) {
+    int j;
+    if (!host_row_valid(row, rginfo, nrows, j)) continue;
+    const int cnt = count[row];
+    if (cnt < 0 || cnt > lck::HOLES_MAX || cnt >= D) return false;
+    for (int i = 0; i < cnt; ++i) {
+      const int c = cols[row * lck::HOLES_MAX + i];
+      if (c < 0 || c >= D || (i > 0 && c <= cols[row * lck::HOLES_MAX + i - 1])) return false;
+    }
+  }
+  return true;
+}
+
+// what the three prediction hooks share: the numbers of a launch over filled rows
+bool holes_launch_ok(int DP, int D, int Kp, i64 ldq, i64 nrg, const int* rginfo, i64 nrows, int J, i64 guard) {
+  if (!pred_rows_ok(nrg, ldq, rginfo, nrows, J) || (!rginfo && J != 1)) return false;
+  return Kp >= 1 && Kp <= 4096 && D >= 1 && DP >= D && DP <= 4096 && DP % 16 == 0 && guard >= 0 && guard <= (1 << 20);
+}
+
+// the arguments predict_holes_kernel reads, uploaded; X, col and logp (io) are guard + payload + guard
+void holes_upload(Scope& s, lck::PredictHolesLaunch& a, double* X, int DP, int Kp, double* col, i64 ldq, i64 nrg, const int* rginfo,
+                  i64 nrows, int J, const int* count, const int* cols, const double* ttab, const double* pscale,
+                  const double* pexp, const double* mean, const double* P, size_t G, double* logp) {
+  const size_t NP = (size_t)(nrg * RG), NH = lck::HOLES_MAX + 1;
+  a.X = s.io(X, NP * DP + 2 * G) + G;
+  a.DP = DP;
+  a.Kp = Kp;
+  a.col = s.io(col, (size_t)Kp * (size_t)ldq + 2 * G) + G;
+  a.ldq = ldq;
+  a.nrg = nrg;
+  a.rginfo = rginfo ? s.in(rginfo, (size_t)nrg) : nullptr;
+  a.nrows = nrows;
+  a.count = s.in(count, NP);
+  a.cols = s.in(cols, NP * lck::HOLES_MAX);
+  a.ttab = s.in(ttab, (size_t)J * NH * Kp);
+  a.pscale = s.in(pscale, (size_t)Kp);
+  a.pexp = s.in(pexp, NH * Kp);
+  a.mean = s.in(mean, (size_t)Kp * DP);
+  a.P = s.in(P, (size_t)Kp * DP * DP);
+  a.logp = s.io(logp, NP + 2 * G) + G;
+}
+
+}  // namespace
+
+// launch_holes_scan, then (fill given) launch_holes_fill on what it left.  X (io) is guard + nrg * 16 * DP + guard doubles,
+// count (io) guard + nrg * 16 + guard ints, cols (io) guard + nrg * 16 * HOLES_MAX + guard ints: the kernels see the middle
+// part.  rginfo [nrg] or null (then nrows, J = 1); fill [D] or null; out (io) [3].
+LC_HOOK lcx_test_holes_scan(double* X, int DP, int D, i64 nrg, const int* rginfo, i64 nrows, int J, const double* fill, i64 guard,
+                            int* count, int* cols, unsigned long long* out) {
+  if (!X || !count || !cols || !out) return -1;
+  if (nrg < 1 || nrg > ((i64)1 << 30) / RG || J < 1 || (!rginfo && J != 1)) return -1;
+  if (rginfo ? !rginfo_ok(rginfo, nrg, J) : (nrows < 0 || nrows > nrg * RG)) return -1;
+  if (D < 1 || DP < D || DP > 4096 || DP % 16 != 0 || guard < 0 || guard > (1 << 20)) return -1;
+  const size_t NP = (size_t)(nrg * RG), G = (size_t)guard;
+  Scope s;
+  double* dX = s.io(X, NP * DP + 2 * G);
+  int* dcount = s.io(count, NP + 2 * G);
+  int* dcols = s.io(cols, NP * lck::HOLES_MAX + 2 * G);
+  const int* drg = rginfo ? s.in(rginfo, (size_t)nrg) : nullptr;
+  const double* dfill = fill ? s.in(fill, (size_t)D) : nullptr;
+  unsigned long long* dout = s.io(out, 3);
+  if (!s.ok()) return s.finish(hipSuccess);
+  lck::HolesScanLaunch a;
+  a.X = dX + G;
+  a.DP = DP;
+  a.D = D;
+  a.nrg = nrg;
+  a.rginfo = drg;
+  a.nrows = nrows;
+  a.count = dcount + G;
+  a.cols = dcols + G;
+  a.out = dout;
+  hipError_t e = lck::launch_holes_scan(a, nullptr);
+  if (e == hipSuccess && fill) {  // (the scan's own records: every recorded column is below D)
+    lck::HolesFillLaunch f;
+    f.X = dX + G;
+    f.DP = DP;
+    f.nrg = nrg;
+    f.rginfo = drg;
+    f.nrows = nrows;
+    f.count = a.count;
+    f.cols = a.cols;
+    f.fill = dfill;
+    e = lck::launch_holes_fill(f, nullptr);
+  }
+  return s.finish(e);
+}
+
+// mode 0 / 1 / 2: launch_predict_holes / launch_predict_holes_var / launch_predict_holes_keep.  X [nrg * 16 x DP] filled, col
+// [Kp x ldq] (read in all modes, written in mode 2) and logp [nrg * 16] are io, guard + payload + guard doubles; count
+// [nrg * 16], cols [nrg * 16 x HOLES_MAX]; ttab [J x (HOLES_MAX + 1) x Kp]; pscale [Kp]; pexp [(HOLES_MAX + 1) x Kp]; mean
+// [Kp x DP]; P [Kp x DP x DP]; mode 1 only: gnu [(HOLES_MAX + 1) x Kp] and var (io) guard + nrg * 16 * HOLES_MAX + guard.
+LC_HOOK lcx_test_predict_holes(int mode, double* X, int DP, int D, int Kp, double* col, i64 ldq, i64 nrg, const int* rginfo,
+                               i64 nrows, int J, const int* count, const int* cols, const double* ttab, const double* pscale,
+                               const double* pexp, const double* mean, const double* P, const double* gnu, i64 guard,
+                               double* logp, double* var) {
+  if (mode < 0 || mode > 2 || !X || !col || !count || !cols || !ttab || !pscale || !pexp || !mean || !P || !logp) return -1;
+  if ((gnu != nullptr) != (mode == 1) || (var != nullptr) != (mode == 1)) return -1;
+  if (!holes_launch_ok(DP, D, Kp, ldq, nrg, rginfo, nrows, J, guard)) return -1;
+  if (!hole_records_ok(count, cols, nrg, rginfo, nrows, D)) return -1;
+  const size_t NP = (size_t)(nrg * RG), G = (size_t)guard;
+  Scope s;
+  lck::PredictHolesLaunch a;
+  holes_upload(s, a, X, DP, Kp, col, ldq, nrg, rginfo, nrows, J, count, cols, ttab, pscale, pexp, mean, P, G, logp);
+  const double* dgnu = gnu ? s.in(gnu, (size_t)(lck::HOLES_MAX + 1) * Kp) : nullptr;
+  double* dvar = var ? s.io(var, NP * lck::HOLES_MAX + 2 * G) : nullptr;
+  if (!s.ok()) return s.finish(hipSuccess);
+  if (mode == 0) return s.finish(lck::launch_predict_holes(a, nullptr));
+  if (mode == 1) {
+    lck::PredictHolesVarLaunch v;
+    v.h = a;
+    v.gnu = dgnu;
+    v.var = dvar + G;
+    return s.finish(lck::launch_predict_holes_var(v, nullptr));
+  }
+  lck::PredictHolesKeepLaunch k;
+  k.h = a;
+  k.tcol = const_cast<double*>(a.col);
+  return s.finish(lck::launch_predict_holes_keep(k, nullptr));
+}
+
+// launch_predict_holes_keep, then launch_holes_draws on what it left.  The arguments of lcx_test_predict_holes (mode 2), goff
+// [J + 1] or null, cqnu [Kp], ndraws, seed; draws (io) guard + nrg * 16 * max(ndraws, 1) * HOLES_MAX + guard doubles and label
+// (io) guard + nrg * 16 * max(ndraws, 1) + guard ints, pre-filled by the caller with 0 / -1.  An ndraws outside 1 ...
+// DRAWS_MAX (at most 128) goes to launch_holes_draws alone, with all buffers: its refusal is what a test asks for.
+LC_HOOK lcx_test_holes_draws(double* X, int DP, int D, int Kp, double* col, i64 ldq, i64 nrg, const int* rginfo, i64 nrows, int J,
+                             const int* count, const int* cols, const double* ttab, const double* pscale, const double* pexp,
+                             const double* mean, const double* P, const i64* goff, const double* cqnu, int ndraws,
+                             unsigned long long seed, i64 guard, double* logp, double* draws, int* label) {
+  if (!X || !col || !count || !cols || !ttab || !pscale || !pexp || !mean || !P || !logp || !cqnu || !draws || !label) return -1;
+  if (!holes_launch_ok(DP, D, Kp, ldq, nrg, rginfo, nrows, J, guard) || ndraws < 0 || ndraws > 128) return -1;
+  if (!hole_records_ok(count, cols, nrg, rginfo, nrows, D)) return -1;
+  const size_t NP = (size_t)(nrg * RG), G = (size_t)guard, nd = (size_t)(ndraws > 1 ? ndraws : 1);
+  Scope s;
+  lck::HolesDrawsLaunch v;
+  holes_upload(s, v.h, X, DP, Kp, col, ldq, nrg, rginfo, nrows, J, count, cols, ttab, pscale, pexp, mean, P, G, logp);
+  v.goff = goff ? reinterpret_cast<const int64_t*>(s.in(goff, (size_t)J + 1)) : nullptr;
+  v.cqnu = s.in(cqnu, (size_t)Kp);
+  v.ndraws = ndraws;
+  v.seed = seed;
+  v.draws = s.io(draws, NP * nd * lck::HOLES_MAX + 2 * G) + G;
+  v.label = s.io(label, NP * nd + 2 * G) + G;
+  if (!s.ok()) return s.finish(hipSuccess);
+  hipError_t e = hipSuccess;
+  if (ndraws >= 1 && ndraws <= lck::DRAWS_MAX) {
+    lck::PredictHolesKeepLaunch k;
+    k.h = v.h;
+    k.tcol = const_cast<double*>(v.h.col);
+    e = lck::launch_predict_holes_keep(k, nullptr);
+  }
+  if (e == hipSuccess) e = lck::launch_holes_draws(v, nullptr);
+  return s.finish(e);
+}
