@@ -105,6 +105,22 @@ int lc_ctx_dims(lc_ctx* ctx, int* J, int* D, int64_t* Ntotal, int* K);
  * Any D for the diagonal / exponential families; the Gauss-Wishart entry points return LC_EINVAL beyond D = 1024. */
 int lc_ctx_set_data(lc_ctx* ctx, int J, const double* const* Xj, const int64_t* Nj, int D, int64_t row_stride,
                     int64_t col_stride);
+/* The same for observations that already live in device memory: Xj_dev is a HOST array of J DEVICE
+ * pointers to float64 data, the strides (in doubles) are positive; row-major (col_stride = 1) and column-major
+ * (row_stride = 1) sources are read coalesced, any other strides are gathered.  One kernel launch packs all groups on the
+ * context's stream, which is synchronised before the call returns.  The context holds a COPY: the sources may be
+ * overwritten or freed afterwards.  Work that produced the sources must be ordered before the context's stream (the same
+ * stream, or the caller synchronises).
+ * LC_EINVAL, before anything is launched and with the context unchanged: a pointer of a group with rows that is NULL,
+ * host memory, managed memory or memory of another device than the context's (the message names the group), a
+ * non-positive stride, J < 1, D < 1, a negative group size. */
+int lc_ctx_set_data_device(lc_ctx* ctx, int J, const double* const* Xj_dev, const int64_t* Nj, int D, int64_t row_stride,
+                           int64_t col_stride);
+/* The smallest observation that is a number (+inf when there is none) and how many observations are NaN (unknown values,
+ * lc_model_predict_incomplete).  After lc_ctx_set_data_device these are what its pass over the data left behind; after
+ * anything else filled or changed the observations, one reduction pass over them.  The same bits on every call.  Either
+ * pointer may be NULL. */
+int lc_ctx_data_range(lc_ctx* ctx, double* min, int64_t* n_nan);
 /* Synthetic K-component full-covariance Gaussian mixture generated on the
  * device (bench workload): x = mu_z + L_z eps, z uniform,
  * Philox-4x32-10 keyed by `seed`, counter = row_offset + row.  Also writes the
@@ -125,6 +141,12 @@ int lc_ctx_set_qz(lc_ctx* ctx, int j, const double* q, int K, int64_t row_stride
 int lc_ctx_get_qz(lc_ctx* ctx, int j, double* q, int64_t row_stride, int64_t col_stride);
 /* rows [row0,row0+n) of group j only (qZ[j].block(row0,0,n,K)) */
 int lc_ctx_get_qz_rows(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* q, int64_t row_stride, int64_t col_stride);
+/* ... into DEVICE memory of the context's device: q_dev[r*row_stride + k*col_stride], positive strides (row-major
+ * destinations go through an LDS tile, column-major ones are K contiguous copies).  Enqueued on the context's stream and
+ * NOT synchronised (lc_ctx_synchronize).  LC_EINVAL as lc_ctx_get_qz_rows, and for a q_dev that is not plain device
+ * memory of that device or a non-positive stride, before anything is launched. */
+int lc_ctx_get_qz_rows_device(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* q_dev, int64_t row_stride,
+                              int64_t col_stride);
 /* every group at once: q is [sum_j N_j x K] row-major, the groups' rows concatenated (one transfer) */
 int lc_ctx_get_qz_all(lc_ctx* ctx, double* q);
 /* every group at once, q[j] = the N_j x K matrix of group j in column-major order (Eigen's default: the `vMatrixXd& qZ`
@@ -309,6 +331,12 @@ int lc_learn(int algo, int J, const double* const* Xj, const int64_t* Nj, int D,
 int lc_learn_w(int algo, int J, const double* const* Xj, const int64_t* Nj, int D, int64_t row_stride,
                int64_t col_stride, double wprior, const double* wprior_j, double clusterprior, int maxclusters,
                int sparse, int verbose, unsigned nthreads, int device, lc_model** out, double* F);
+/* lc_learn_w on observations that already live in ctx (lc_ctx_set_data_device, lc_ctx_set_data, lc_ctx_synth): the same
+ * algorithms, priors, messages and results as the one-device path of lc_learn_w on the same rows.  The data lives on one
+ * device: LIBCLUSTER_GPUS is not consulted.  The ExpGamma learners take "X has to be in the range [0, inf)!" from
+ * lc_ctx_data_range's minimum, before anything is printed or learned.  The returned model borrows ctx, as lc_cluster's. */
+int lc_learn_ctx(int algo, lc_ctx* ctx, double wprior, const double* wprior_j, double clusterprior, int maxclusters,
+                 int sparse, int verbose, unsigned nthreads, lc_model** out, double* F);
 
 /* The same model-selection loop (cluster(), cluster.cpp:564-629) on observations that already live in
  * a context (lc_ctx_set_data or lc_ctx_synth): nothing but the M-step statistics crosses PCIe, the
@@ -357,6 +385,11 @@ int lc_model_fenergy(lc_model* m, double* Fw /*[J]*/, double* Fc /*[K]*/);
 int lc_model_predict(lc_model* m, lc_ctx* ctx, const int* groups /* [J of ctx] or NULL */, int keep_qz);
 /* rows [row0, row0+n) of block j of the last prediction on ctx (like lc_ctx_get_qz_rows); any output may be NULL */
 int lc_ctx_get_predictions(lc_ctx* ctx, int j, int64_t row0, int64_t n, int32_t* label, double* logZ, double* logp);
+/* ... into DEVICE arrays of the context's device (any may be NULL): device-to-device copies enqueued on the context's
+ * stream and NOT synchronised (lc_ctx_synchronize).  LC_EINVAL as lc_ctx_get_predictions, and for an output that is not
+ * plain device memory of that device, before anything is enqueued. */
+int lc_ctx_get_predictions_device(lc_ctx* ctx, int j, int64_t row0, int64_t n, int32_t* label_dev, double* logZ_dev,
+                                  double* logp_dev);
 /* ---- conditional prediction (nothing in the reference corresponds): some columns of a new row are known,
  * the others are wanted.  Gauss-Wishart models only.  ctx holds the KNOWN columns only: its width is ngiven and its column
  * i is model column given[i]; target lists the wanted model columns (NULL: every column that is not given, ascending;

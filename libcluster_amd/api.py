@@ -10,7 +10,10 @@ precision, libclusterpy.h:74-135).
 Additive keyword-only extras: ``return_info=True`` appends a dict (rounds with every free energy, cluster
 posteriors, E[log weights]), ``device`` picks the GPU, ``concentration`` / ``alpha`` set the weight prior the C++ API
 takes through its ``weights`` argument, ``qY0`` gives learnSCM / learnMCM a reproducible start, ``nthreads`` is an
-alias of ``threads``, ``return_model=True`` (the eight flat and grouped learners) appends the open ``capi.Model`` as
+alias of ``threads``, X may be a 2-D CUDA ``torch.float64`` tensor (a list of them for the grouped learners) instead of
+host arrays -- the rows are read where they are, on torch's current stream, and ``qZ`` comes back as torch tensors on that
+device while everything else stays numpy (``device`` then has to agree with the tensors' device; learnSCM / learnMCM take
+host data only) --, ``return_model=True`` (the eight flat and grouped learners) appends the open ``capi.Model`` as
 the last element, whose ``predict(Xnew)`` scores new observations (labels, responsibilities, log density),
 ``sample(n, seed)`` draws new rows from the learned density, and ``predict_conditional(..., draws=m, seed=s)`` /
 ``impute(X, missing, draws=m)`` draw the unknown columns of rows (multiple imputation).
@@ -39,7 +42,8 @@ def _threads(threads, nthreads):
 
 def _result(F, model, rows, grouped, return_info, return_model=False):
     J, K, D = model.dims()
-    qZ = model.qz_all(rows)
+    # (a model learned from device tensors hands qZ out where the tensors live; everything else is small and on the host)
+    qZ = model.qz_all_device(rows) if model._torch_device is not None else model.qz_all(rows)
     w = [np.exp(model.weights(j)[0]).reshape(-1, 1) for j in range(J)]  # ArrayXd -> (K, 1)
     cl = [model.cluster(k) for k in range(K)]
     # ExpGamma has no mean / covariance: its slot carries getrate(), covs is None per cluster
@@ -55,32 +59,33 @@ def _result(F, model, rows, grouped, return_info, return_model=False):
 
 
 def _flat(algo, X, wprior, prior, maxclusters, verbose, threads, nthreads, device, return_info, return_model):
-    F, m, rows = capi.learn(algo, np.asarray(X, dtype=np.float64), wprior, _f32(prior), maxclusters, False, verbose,
-                            _threads(threads, nthreads), device)
+    X = X if capi.device_blocks(X) is not None else np.asarray(X, dtype=np.float64)
+    F, m, rows = capi.learn(algo, X, wprior, _f32(prior), maxclusters, False, verbose, _threads(threads, nthreads), device)
     return _result(F, m, rows, False, return_info, return_model)
 
 
 def _grouped(algo, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info, return_model):
-    F, m, rows = capi.learn(algo, [np.asarray(x, dtype=np.float64) for x in X], 1.0, _f32(prior), maxclusters,
-                            sparse, verbose, _threads(threads, nthreads), device)
+    X = list(X)
+    X = X if capi.device_blocks(X) is not None else [np.asarray(x, dtype=np.float64) for x in X]
+    F, m, rows = capi.learn(algo, X, 1.0, _f32(prior), maxclusters, sparse, verbose, _threads(threads, nthreads), device)
     return _result(F, m, rows, True, return_info, return_model)
 
 
 def learnVDP(X, prior=1.0, maxclusters=-1, verbose=False, threads=None, *, nthreads=None, concentration=1.0,
-             device=0, return_info=False, return_model=False):
+             device=None, return_info=False, return_model=False):
     """libclusterpy.h:300-320 / include/libcluster.h:177-186.  Returns (f, qZ, w, mu, cov)."""
     return _flat(capi.ALGO_VDP, X, concentration, prior, maxclusters, verbose, threads, nthreads, device, return_info,
                  return_model)
 
 
-def learnBGMM(X, prior=1.0, maxclusters=-1, verbose=False, threads=None, *, nthreads=None, alpha=1.0, device=0,
+def learnBGMM(X, prior=1.0, maxclusters=-1, verbose=False, threads=None, *, nthreads=None, alpha=1.0, device=None,
               return_info=False, return_model=False):
     """libclusterpy.h:322-342 / include/libcluster.h:218-227.  Returns (f, qZ, w, mu, cov)."""
     return _flat(capi.ALGO_BGMM, X, alpha, prior, maxclusters, verbose, threads, nthreads, device, return_info,
                  return_model)
 
 
-def learnGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads=None, *, nthreads=None, device=0,
+def learnGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads=None, *, nthreads=None, device=None,
              return_info=False, return_model=False):
     """libclusterpy.h:344-368 / include/libcluster.h:356-366.  X: list of (N_j, D) arrays.
     Returns (f, qZ, w, mu, cov) with qZ and w lists over the groups."""
@@ -88,21 +93,21 @@ def learnGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads=
                     return_model)
 
 
-def learnSGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads=None, *, nthreads=None, device=0,
+def learnSGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads=None, *, nthreads=None, device=None,
               return_info=False, return_model=False):
     """libclusterpy.h:370-395 / include/libcluster.h:409-419 (one Dirichlet per group)."""
     return _grouped(capi.ALGO_SGMC, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info,
                     return_model)
 
 
-def learnDGMM(X, prior=1.0, maxclusters=-1, verbose=False, threads=None, *, nthreads=None, alpha=1.0, device=0,
+def learnDGMM(X, prior=1.0, maxclusters=-1, verbose=False, threads=None, *, nthreads=None, alpha=1.0, device=None,
               return_info=False, return_model=False):
     """include/libcluster.h:262-271 (diagonal Gaussians, NormGamma).  cov holds the (1, D) vectors getcov() returns."""
     return _flat(capi.ALGO_DGMM, X, alpha, prior, maxclusters, verbose, threads, nthreads, device, return_info,
                  return_model)
 
 
-def learnBEMM(X, prior=1.0, maxclusters=-1, verbose=False, threads=None, *, nthreads=None, alpha=1.0, device=0,
+def learnBEMM(X, prior=1.0, maxclusters=-1, verbose=False, threads=None, *, nthreads=None, alpha=1.0, device=None,
               return_info=False, return_model=False):
     """include/libcluster.h:306-315 (exponential mixture).  ValueError if X has a negative entry; mu holds the
     clusters' getrate(), cov is a list of None."""
@@ -110,14 +115,14 @@ def learnBEMM(X, prior=1.0, maxclusters=-1, verbose=False, threads=None, *, nthr
                  return_model)
 
 
-def learnDGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads=None, *, nthreads=None, device=0,
+def learnDGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads=None, *, nthreads=None, device=None,
               return_info=False, return_model=False):
     """include/libcluster.h:462-472.  X is a list of (N_j, D) arrays."""
     return _grouped(capi.ALGO_DGMC, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info,
                     return_model)
 
 
-def learnEGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads=None, *, nthreads=None, device=0,
+def learnEGMC(X, prior=1.0, maxclusters=-1, sparse=False, verbose=False, threads=None, *, nthreads=None, device=None,
               return_info=False, return_model=False):
     """include/libcluster.h:513-523.  X is a list of non-negative (N_j, D) arrays."""
     return _grouped(capi.ALGO_EGMC, X, prior, maxclusters, sparse, verbose, threads, nthreads, device, return_info,

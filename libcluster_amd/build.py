@@ -32,7 +32,7 @@ ARCH = "gfx950"
 DEVICE_FLAGS = ["-mllvm", "-amdgpu-use-amdgpu-trackers=1", "-mllvm", "-amdgpu-disable-unclustered-high-rp-reschedule=1"]
 
 SOURCES = ["lc_kernels_estep.hip", "lc_kernels_suffstat.hip", "lc_kernels_diag.hip", "lc_kernels_aux.hip", "lc_kernels_fused.hip",
-           "lc_kernels_predict.hip", "lc_kernels_sample.hip", "lc_kernels_holes.hip", "lc_kernels_loo.hip", "lc_kernels_topic.hip", "lc_kernels_rank.hip", "lc_kernels_select.hip", "lc_ctx.cpp", "lc_predict.cpp", "lc_topic_predict.cpp",
+           "lc_kernels_predict.hip", "lc_kernels_sample.hip", "lc_kernels_holes.hip", "lc_kernels_loo.hip", "lc_kernels_topic.hip", "lc_kernels_rank.hip", "lc_kernels_select.hip", "lc_kernels_ingest.hip", "lc_ctx.cpp", "lc_predict.cpp", "lc_topic_predict.cpp",
            "lc_comm.cpp", "lc_engine.cpp", "lc_topic.cpp", "lc_capi.cpp"]
 HEADERS = ["lc_kernels.h", "lc_device.hpp", "lc_ctx.hpp", "lc_comm.hpp", "lc_engine.hpp", "lc_topic.hpp", "lc_host.hpp",
            "lc_predict.hpp", "lc_philox.hpp", "../../include/libcluster_hip.h"]

@@ -437,6 +437,13 @@ def lib() -> C.CDLL:
     L.lc_ctx_get_sample_labels.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_int32_p]
     L.lc_gw_conditional_cov.argtypes = [C.c_int, C.c_double, C.c_double, c_double_p, c_int_p, C.c_int, c_int_p, C.c_int,
                                         c_double_p, c_double_p]
+    # device-resident data in, row results out: device addresses travel as plain integers
+    L.lc_ctx_set_data_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_int64_p, C.c_int, C.c_int64, C.c_int64]
+    L.lc_ctx_data_range.argtypes = [C.c_void_p, c_double_p, c_int64_p]
+    L.lc_learn_ctx.argtypes = [C.c_int, C.c_void_p, C.c_double, c_double_p, C.c_double, C.c_int, C.c_int, C.c_int, C.c_uint,
+                               C.POINTER(C.c_void_p), c_double_p]
+    L.lc_ctx_get_qz_rows_device.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64]
+    L.lc_ctx_get_predictions_device.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -467,6 +474,48 @@ def _strides(a: np.ndarray):
     return a.strides[0] // 8, a.strides[1] // 8
 
 
+def is_device_tensor(x) -> bool:
+    """True for a torch tensor that lives on a GPU.  torch is only imported once an object of a torch type shows up: numpy
+    callers never load it through this module (a CPU tensor is host data and goes through np.asarray as ever)."""
+    if not type(x).__module__.startswith("torch"):
+        return False
+    import torch
+
+    return isinstance(x, torch.Tensor) and bool(x.is_cuda)
+
+
+def device_blocks(X):
+    """How the data entry points read X: None for host data (numpy arrays, CPU tensors, lists of them), or the
+    list of blocks when X is a 2-D CUDA torch.float64 tensor or a list of them on one device.  TypeError for another dtype
+    (nothing is converted silently), ValueError for a list that mixes host and device blocks, a block that is not 2-D,
+    blocks of different widths or on different devices.  Nothing is launched or copied here."""
+    Xs = list(X) if isinstance(X, (list, tuple)) else [X]
+    on_device = [is_device_tensor(x) for x in Xs]
+    if not any(on_device):
+        return None
+    if not all(on_device):
+        raise ValueError("X mixes host arrays and device tensors: move every block to one side first")
+    import torch
+
+    for x in Xs:
+        if x.dtype != torch.float64:
+            raise TypeError(f"device tensors must be float64, not {x.dtype}: convert with X.double() (nothing is converted "
+                            "silently)")
+        if x.ndim != 2:
+            raise ValueError(f"a device tensor of observations must be 2-D (N, D), not {x.ndim}-D")
+    if any(x.shape[1] != Xs[0].shape[1] for x in Xs):
+        raise ValueError("X dimensions are inconsistent between groups!")
+    if any(x.device != Xs[0].device for x in Xs):
+        raise ValueError("the blocks of X live on different devices")
+    return Xs
+
+
+def _torch_stream(tdev) -> int:
+    import torch
+
+    return int(torch.cuda.current_stream(tdev).cuda_stream)
+
+
 def _top_rows_call(call, C_, m):
     """the output arrays of lc_ctx_top_rows / lc_model_exemplars for C_ columns of m entries -> TopRows"""
     shape = (max(C_, 0), max(min(m, 64), 0))  # (out-of-range arguments are the library's to refuse: nothing is written)
@@ -484,6 +533,7 @@ class Context:
     def __init__(self, device: int = 0, stream: int | None = None):
         self._h = C.c_void_p()
         self._cb = None
+        self._device, self._stream = int(device), int(stream or 0)
         check(lib().lc_ctx_create(device, C.c_void_p(stream or 0), C.byref(self._h)))
 
     def close(self):
@@ -505,7 +555,12 @@ class Context:
 
     # -- data ---------------------------------------------------------------
     def set_data(self, X):
-        """X: (N, D) array or list of (N_j, D) arrays, any strides (no copy)."""
+        """X: (N, D) array or list of (N_j, D) arrays, any strides (no copy).  Also a 2-D CUDA torch.float64 tensor or a list
+        of them on this context's device, any strides (device_blocks for what is refused): one kernel packs them into the
+        context's own image, so the tensors may be overwritten or freed afterwards and are not kept alive."""
+        blocks = device_blocks(X)
+        if blocks is not None:
+            return self._set_data_device(blocks)
         Xs = [X] if isinstance(X, np.ndarray) else list(X)
         Xs = [np.asarray(x, dtype=np.float64) for x in Xs]
         D = Xs[0].shape[1]
@@ -523,6 +578,66 @@ class Context:
         Nj = (C.c_int64 * J)(*[x.shape[0] for x in Xs])
         check(lib().lc_ctx_set_data(self._h, J, ptrs, Nj, D, rs, cs))
         self._X = Xs  # keep alive
+
+    def _after_torch(self, tdev):
+        """Order the context's stream behind torch's current stream of tdev: nothing to do when they are one stream (the
+        wrappers that create the context see to that), a host wait for torch's stream otherwise."""
+        if _torch_stream(tdev) != self._stream:
+            import torch
+
+            torch.cuda.current_stream(tdev).synchronize()
+
+    def _set_data_device(self, Xs):
+        tdev = Xs[0].device
+        if tdev.index != self._device:
+            raise ValueError(f"X lives on device {tdev.index}, the context on device {self._device}")
+        st = {(x.stride(0), x.stride(1)) for x in Xs}
+        if len(st) == 1 and all(x.shape[0] > 1 for x in Xs) and min(next(iter(st))) > 0:
+            rs, cs = next(iter(st))  # e.g. all row-major, all column-major (a .t() view), a slice of a wider tensor: no copy
+        else:  # a zero stride (expand), single rows, or blocks laid out differently: contiguous copies on the device
+            Xs = [x.contiguous() for x in Xs]
+            rs, cs = Xs[0].shape[1], 1
+        J, D = len(Xs), Xs[0].shape[1]
+        ptrs = (C.c_void_p * J)(*[x.data_ptr() if x.shape[0] else None for x in Xs])
+        Nj = (C.c_int64 * J)(*[x.shape[0] for x in Xs])
+        self._after_torch(tdev)
+        check(lib().lc_ctx_set_data_device(self._h, J, ptrs, Nj, D, rs, cs))  # (synchronises the context's stream)
+        self._X = None
+
+    def data_range(self):
+        """(min, n_nan) of the observations (lc_ctx_data_range): the smallest entry that is a number (+inf: none) and the
+        count of NaN entries."""
+        lo, nn = C.c_double(), C.c_int64()
+        check(lib().lc_ctx_data_range(self._h, C.byref(lo), C.byref(nn)))
+        return lo.value, nn.value
+
+    def get_qz_rows_device(self, j, row0, n, tdev=None):
+        """Rows [row0, row0 + n) of group j of qZ as a row-major (n, K) torch.float64 tensor on the context's device,
+        filled on the context's stream (lc_ctx_get_qz_rows_device): synchronize() before another stream reads it."""
+        import torch
+
+        tdev = torch.device("cuda", self._device) if tdev is None else tdev
+        K = self.dims()[3]
+        q = torch.empty((n, K), dtype=torch.float64, device=tdev)
+        if n and K:
+            self._after_torch(tdev)
+            check(lib().lc_ctx_get_qz_rows_device(self._h, j, row0, n, q.data_ptr(), K, 1))
+        return q
+
+    def get_predictions_device(self, j, row0, n, logp=True, tdev=None):
+        """get_predictions as torch tensors on the context's device (label int32, logZ, logp), copied on the context's
+        stream (lc_ctx_get_predictions_device): synchronize() before another stream reads them."""
+        import torch
+
+        tdev = torch.device("cuda", self._device) if tdev is None else tdev
+        label = torch.empty(n, dtype=torch.int32, device=tdev)
+        logZ = torch.empty(n, dtype=torch.float64, device=tdev)
+        lp = torch.empty(n, dtype=torch.float64, device=tdev) if logp else None
+        if n:
+            self._after_torch(tdev)
+            check(lib().lc_ctx_get_predictions_device(self._h, j, row0, n, label.data_ptr(), logZ.data_ptr(),
+                                                      lp.data_ptr() if logp else None))
+        return label, logZ, lp
 
     def synth(self, N, D, K, mu, L, seed, row_offset=0, hard=0.9):
         mu = np.ascontiguousarray(mu, dtype=np.float64)
@@ -987,11 +1102,14 @@ class Model:
     def __init__(self, handle, ctx=None):
         self._h = handle
         self._ctx = ctx  # keep a borrowed context alive
+        self._torch_device = None  # learn() on device tensors: where qZ is handed out (qz_all_device), and the context is ours
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib().lc_model_free(self._h)
             self._h = C.c_void_p()
+            if getattr(self, "_torch_device", None) is not None and self._ctx is not None:
+                self._ctx.close()  # (the context learn() made for the tensors: nobody else holds it)
 
     def __del__(self):
         try:
@@ -1023,6 +1141,13 @@ class Model:
         if allq.size:
             check(lib().lc_model_get_qz_all(self._h, dptr(allq)))
         return [allq[o - n:o] for n, o in zip(rows, np.cumsum(rows))]
+
+    def qz_all_device(self, rows):
+        """A model learned from device tensors: every group's qZ as a row-major (N_j, K) torch.float64 tensor on the
+        tensors' device, written there by the device (no host staging)."""
+        out = [self._ctx.get_qz_rows_device(j, 0, n, self._torch_device) for j, n in enumerate(rows)]
+        self._ctx.synchronize()  # (any stream may read them)
+        return out
 
     def qz(self, j, n):
         _, K, _ = self.dims()
@@ -1080,10 +1205,26 @@ class Model:
             g = garr.ctypes.data_as(C.POINTER(C.c_int))
         check(lib().lc_model_predict(self._h, ctx._h, g, int(keep_qz)))
 
-    def predict(self, X, groups=None, qz=False, device=0):
+    def predict(self, X, groups=None, qz=False, device=None):
         """Prediction(label, logZ, logp, qZ) for the host rows X ((N, D) array), or a list of them for a list of
-        blocks (block b scored with learned group groups[b], default 0).  qZ is None unless qz=True."""
+        blocks (block b scored with learned group groups[b], default 0).  qZ is None unless qz=True.
+        X may also be a 2-D CUDA torch.float64 tensor or a list of them (device_blocks): the rows are read where they are,
+        on torch's current stream of their device, and label (int32), logZ, logp and qZ come back as torch tensors on that
+        device, ready for any stream."""
         blocks = isinstance(X, (list, tuple))
+        Xd = device_blocks(X)
+        if Xd is not None:
+            tdev = Xd[0].device
+            if device is not None and device != tdev.index:
+                raise ValueError(f"device={device}, but X lives on device {tdev.index}")
+            with Context(tdev.index, _torch_stream(tdev)) as ctx:
+                ctx.set_data(Xd)
+                self.predict_context(ctx, groups, keep_qz=qz)
+                out = [Prediction(*ctx.get_predictions_device(j, 0, x.shape[0], tdev=tdev),
+                                  ctx.get_qz_rows_device(j, 0, x.shape[0], tdev) if qz else None) for j, x in enumerate(Xd)]
+                ctx.synchronize()
+            return out if blocks else out[0]
+        device = 0 if device is None else device
         Xs = list(X) if blocks else [X]
         Xs = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, self.dims()[2])) for x in Xs]
         with Context(device) as ctx:
@@ -1364,10 +1505,41 @@ class Model:
         check(lib().lc_model_release_data(self._h))
 
 
-def learn(algo, X, wprior=1.0, clusterprior=1.0, maxclusters=-1, sparse=False, verbose=False, nthreads=1, device=0,
+def _learn_device(algo, Xd, wprior, clusterprior, maxclusters, sparse, verbose, nthreads, device, wprior_j):
+    """learn() for device tensors: a context on the tensors' device and torch's current stream of it takes
+    the rows where they are, lc_learn_ctx learns on it.  The model keeps the context (its qZ: Model.qz_all_device)."""
+    tdev = Xd[0].device
+    if device is not None and device != tdev.index:
+        raise ValueError(f"device={device}, but X lives on device {tdev.index}")
+    J = len(Xd)
+    wj = None
+    if wprior_j is not None:
+        wj = np.ascontiguousarray(wprior_j, dtype=np.float64)
+        if wj.shape != (J,):
+            raise ValueError("wprior_j needs one value per group")
+    ctx = Context(tdev.index, _torch_stream(tdev))
+    try:
+        ctx.set_data(Xd)
+        mh, F = C.c_void_p(), C.c_double()
+        check(lib().lc_learn_ctx(algo, ctx._h, wprior, dptr(wj), clusterprior, maxclusters, int(sparse), int(verbose),
+                                 nthreads, C.byref(mh), C.byref(F)))
+    except BaseException:
+        ctx.close()
+        raise
+    m = Model(mh, ctx=ctx)
+    m._torch_device = tdev
+    return F.value, m, [x.shape[0] for x in Xd]
+
+
+def learn(algo, X, wprior=1.0, clusterprior=1.0, maxclusters=-1, sparse=False, verbose=False, nthreads=1, device=None,
           wprior_j=None):
     """wprior_j: one weight prior per group (the priors the caller's weight objects carry into the multi-group
-    learners: learnSGMC's Dirichlet alphas); None = defaults."""
+    learners: learnSGMC's Dirichlet alphas); None = defaults.  device: None = GPU 0 for host data, the tensors' own
+    device for CUDA torch.float64 tensors (device_blocks), which are read where they are."""
+    Xd = device_blocks(X)
+    if Xd is not None:
+        return _learn_device(algo, Xd, wprior, clusterprior, maxclusters, sparse, verbose, nthreads, device, wprior_j)
+    device = 0 if device is None else device
     Xs = [X] if isinstance(X, np.ndarray) else list(X)
     Xs = [np.ascontiguousarray(x, dtype=np.float64) for x in Xs]
     J, D = len(Xs), Xs[0].shape[1]

@@ -192,6 +192,26 @@ void algo_configure(int algo, lce::Model& model, bool verbose, bool sparse) {
   }
 }
 
+// lc_learn_w (one device) / lc_learn_ctx: model selection on the context m->ctx, which holds the observations
+double learn_on_context(int algo, lc_model* m, double wprior, const double* wprior_j, double clusterprior, int maxclusters,
+                        int sparse, int verbose, unsigned nthreads) {
+  lcc::Context& ctx = m->ctx->impl;
+  const bool single = algo_single(algo);
+  const int J = ctx.J();
+  algo_configure(algo, m->model, verbose != 0, sparse != 0);
+  if (single) m->model.weights.emplace_back(m->model.wkind, wprior);  // vecweights(1, weights), :653/:684/:715/:752
+  else if (wprior_j)  // the caller's weight objects keep their priors (weights.resize(J, W()), cluster.cpp:192)
+    for (int j = 0; j < J; ++j) m->model.weights.emplace_back(m->model.wkind, wprior_j[j]);
+  lce::ClusterOptions co;
+  co.clusterprior = clusterprior;
+  co.maxclusters = maxclusters;
+  co.sparse = !single && sparse;  // the single-matrix learners pass sparse=false, :657/:688/:719/:756
+  co.verbose = verbose != 0;
+  co.nthreads = nthreads;
+  co.trace = &m->rounds;
+  return lce::cluster(ctx, m->model, co);
+}
+
 // LIBCLUSTER_GPUS = N | "all": learn*() shard their observations over N GPUs of this node, one host thread and one
 // context per GPU, statistics summed with RCCL (SURVEY 5 "Config / flags": GPU selection cannot go into the frozen
 // learnBGMM / learnVDP / learnGMC signatures).  LIBCLUSTER_GPUS_SAME_DEVICE=1 places every shard on `device` with the
@@ -425,6 +445,23 @@ int lc_ctx_set_data(lc_ctx* ctx, int J, const double* const* Xj, const int64_t* 
   });
 }
 
+int lc_ctx_set_data_device(lc_ctx* ctx, int J, const double* const* Xj_dev, const int64_t* Nj, int D, int64_t rs,
+                           int64_t cs) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    need(Xj_dev, "Xj_dev");
+    need(Nj, "Nj");
+    ctx->impl.set_data_device(J, Xj_dev, Nj, D, rs, cs);
+  });
+}
+
+int lc_ctx_data_range(lc_ctx* ctx, double* min, int64_t* n_nan) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.data_range(min, n_nan);
+  });
+}
+
 int lc_ctx_synth(lc_ctx* ctx, int64_t N, int D, int K, const double* mu, const double* L, uint64_t seed,
                  int64_t row_offset, double hard) {
   return guarded([&] {
@@ -527,6 +564,14 @@ int lc_ctx_get_qz_rows(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* q, i
     need(ctx, "ctx");
     need(q, "q");
     ctx->impl.qz_get_rows(j, row0, n, q, rs, cs);
+  });
+}
+
+int lc_ctx_get_qz_rows_device(lc_ctx* ctx, int j, int64_t row0, int64_t n, double* q_dev, int64_t rs, int64_t cs) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    need(q_dev, "q_dev");
+    ctx->impl.qz_get_rows_device(j, row0, n, q_dev, rs, cs);
   });
 }
 
@@ -885,20 +930,34 @@ int lc_learn_w(int algo, int J, const double* const* Xj, const int64_t* Nj, int 
     }
     m->owned_ctx.reset(new lc_ctx(device, nullptr));
     m->ctx = m->owned_ctx.get();
-    lcc::Context& ctx = m->ctx->impl;
-    ctx.set_data(J, Xj, Nj, D, rs, cs);
-    algo_configure(algo, m->model, verbose != 0, sparse != 0);
-    if (single) m->model.weights.emplace_back(m->model.wkind, wprior);  // vecweights(1, weights), :653/:684/:715/:752
-    else if (wprior_j)  // the caller's weight objects keep their priors (weights.resize(J, W()), cluster.cpp:192)
-      for (int j = 0; j < J; ++j) m->model.weights.emplace_back(m->model.wkind, wprior_j[j]);
-    lce::ClusterOptions co;
-    co.clusterprior = clusterprior;
-    co.maxclusters = maxclusters;
-    co.sparse = !single && sparse;  // the single-matrix learners pass sparse=false, :657/:688/:719/:756
-    co.verbose = verbose != 0;
-    co.nthreads = nthreads;
-    co.trace = &m->rounds;
-    const double f = lce::cluster(ctx, m->model, co);
+    m->ctx->impl.set_data(J, Xj, Nj, D, rs, cs);
+    const double f = learn_on_context(algo, m.get(), wprior, wprior_j, clusterprior, maxclusters, sparse, verbose, nthreads);
+    if (F) *F = f;
+    *out = m.release();
+  });
+}
+
+int lc_learn_ctx(int algo, lc_ctx* ctx, double wprior, const double* wprior_j, double clusterprior, int maxclusters,
+                 int sparse, int verbose, unsigned nthreads, lc_model** out, double* F) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    need(out, "out");
+    if (algo < 0 || algo > LC_ALGO_EGMC) throw std::invalid_argument("unknown algorithm");
+    const bool single = algo_single(algo);
+    const int J = ctx->impl.J();
+    if (J < 1) throw std::invalid_argument("the context holds no observations (lc_ctx_set_data / lc_ctx_synth)");
+    if (single && J != 1) throw std::invalid_argument("this algorithm takes a single observation matrix");
+    if (nthreads < 1) throw std::invalid_argument("Must specify at least one thread for execution!");  // cluster.cpp:576-577
+    if (algo == LC_ALGO_BEMM || algo == LC_ALGO_EGMC) {  // cluster.cpp:742-743, 862-864 (before anything is printed)
+      double lo = 0.0;
+      ctx->impl.data_range(&lo, nullptr);
+      if (lo < 0) throw std::invalid_argument("X has to be in the range [0, inf)!");
+    }
+    std::unique_ptr<lc_model> m(new lc_model());
+    m->D = ctx->impl.D();
+    m->sparse = !single && sparse;
+    m->ctx = ctx;  // borrowed, as lc_cluster's
+    const double f = learn_on_context(algo, m.get(), wprior, wprior_j, clusterprior, maxclusters, sparse, verbose, nthreads);
     if (F) *F = f;
     *out = m.release();
   });
@@ -1141,6 +1200,14 @@ int lc_model_predict(lc_model* m, lc_ctx* ctx, const int* groups, int keep_qz) {
       if (j < 0 || j >= J) throw std::invalid_argument("group index out of range");
     }
     lcp::predict(ctx->impl, m->model, m->sparse, groups, keep_qz != 0);
+  });
+}
+
+int lc_ctx_get_predictions_device(lc_ctx* ctx, int j, int64_t row0, int64_t n, int32_t* label_dev, double* logZ_dev,
+                                  double* logp_dev) {
+  return guarded([&] {
+    need(ctx, "ctx");
+    ctx->impl.get_predictions_device(j, row0, n, label_dev, logZ_dev, logp_dev);
   });
 }
 

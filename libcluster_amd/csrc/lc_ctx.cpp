@@ -274,6 +274,7 @@ void Context::build_layout(int J, const int64_t* Nj, int D) {
   pred_loo_var_ = false;
   sampled_ = false;               // (the rows no longer come from sample(): it sets the flag after its launch)
   pred_docs_T_ = 0;               // (... and the per-document ones to the old documents)
+  range_ok_ = false;              // (... and what a pack left of the old rows' range)
   LC_HIP(hipSetDevice(device_));
   X_.reserve((size_t)std::max<int64_t>(NP_, 1) * DP_);
   goff_d_.reserve(J + 1);
@@ -366,6 +367,129 @@ void Context::set_data(int J, const double* const* Xj, const int64_t* Nj, int D,
   LC_HIP(hipStreamSynchronize(stream_));
 }
 
+// ---------------------------------------------------------------------------
+// device-resident data in, row results out
+// ---------------------------------------------------------------------------
+void Context::require_device_memory(const void* p, const std::string& what) const {
+  if (!p) throw std::invalid_argument(what + " is NULL");
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof at);
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();  // (an address the runtime does not know is an error of the caller, not of the device)
+    throw std::invalid_argument(what + " is not device memory (a host pointer? copy it with lc_ctx_set_data)");
+  }
+  if (at.isManaged) throw std::invalid_argument(what + " is managed memory: plain device memory (hipMalloc) is needed");
+  if (at.type != hipMemoryTypeDevice) throw std::invalid_argument(what + " is not device memory");
+  if (at.device != device_)
+    throw std::invalid_argument(what + " lives on device " + std::to_string(at.device) + ", the context on device " +
+                                std::to_string(device_));
+}
+
+// [range 2 | source pointers J | rows J] for a launch of lck::launch_pack_rows over this context's layout
+lck::PackRowsLaunch Context::pack_launch(const std::vector<int64_t>& tab, int64_t rs, int64_t cs, double* image) {
+  ingest_tab_.reserve(tab.size());
+  LC_HIP(hipMemcpyAsync(ingest_tab_.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+  lck::PackRowsLaunch a;
+  a.J = J_;
+  a.D = D_;
+  a.DP = DP_;
+  a.NP = NP_;
+  a.range = reinterpret_cast<unsigned long long*>(ingest_tab_.p);
+  a.src = reinterpret_cast<const double* const*>(ingest_tab_.p + 2);
+  a.Nj = ingest_tab_.p + 2 + J_;
+  a.goff = goff_d_.p;
+  a.rs = rs;
+  a.cs = cs;
+  a.X = image;
+  return a;
+}
+
+void Context::read_range() {
+  unsigned long long r[2] = {~0ull, 0};
+  if (NP_ > 0) {
+    LC_HIP(hipMemcpyAsync(r, ingest_tab_.p, sizeof r, hipMemcpyDeviceToHost, stream_));
+    LC_HIP(hipStreamSynchronize(stream_));
+  }
+  lck::data_range_decode(r, &range_min_, &range_nan_);
+  range_ok_ = true;
+}
+
+void Context::set_data_device(int J, const double* const* Xj, const int64_t* Nj, int D, int64_t rs, int64_t cs) {
+  use_device();
+  // everything that can be wrong with the arguments is found before the layout changes and before anything is launched:
+  // an address that is not this device's memory never reaches a kernel
+  if (J < 1) throw std::invalid_argument("need at least one group of observations");
+  if (D < 1) throw std::invalid_argument("observations must have at least one dimension");
+  if (rs < 1 || cs < 1) throw std::invalid_argument("lc_ctx_set_data_device: the strides must be positive");
+  for (int j = 0; j < J; ++j) {
+    if (Nj[j] < 0) throw std::invalid_argument("negative group size");
+    if (Nj[j] > 0) require_device_memory(Xj[j], "lc_ctx_set_data_device: Xj[" + std::to_string(j) + "]");
+  }
+  build_layout(J, Nj, D);
+  if (NP_ > 0) {
+    std::vector<int64_t> tab(2 + 2 * (size_t)J, 0);
+    for (int j = 0; j < J; ++j) {
+      tab[2 + (size_t)j] = Nj[j] > 0 ? (int64_t)reinterpret_cast<intptr_t>(Xj[j]) : 0;
+      tab[2 + (size_t)J + j] = Nj[j];
+    }
+    const lck::PackRowsLaunch a = pack_launch(tab, rs, cs, X_.p);
+    LC_HIP(lck::launch_pack_rows(a, stream_));
+  }
+  read_range();  // (synchronises the stream, as set_data does: the sources are free again)
+}
+
+void Context::data_range(double* min, int64_t* n_nan) {
+  use_device();
+  if (J_ < 1) throw std::invalid_argument("the context holds no observations (lc_ctx_set_data / lc_ctx_synth)");
+  if (!range_ok_) {
+    if (NP_ > 0) {  // the same reduction over the image that is there, nothing stored
+      std::vector<int64_t> tab(2 + 2 * (size_t)J_, 0);
+      for (int j = 0; j < J_; ++j) {
+        tab[2 + (size_t)j] = (int64_t)reinterpret_cast<intptr_t>(X_.p + (size_t)goff_[(size_t)j] * DP_);
+        tab[2 + (size_t)J_ + j] = Nj_[(size_t)j];
+      }
+      const lck::PackRowsLaunch a = pack_launch(tab, DP_, 1, nullptr);
+      LC_HIP(lck::launch_pack_rows(a, stream_));
+    }
+    read_range();
+  }
+  if (min) *min = range_min_;
+  if (n_nan) *n_nan = range_nan_;
+}
+
+void Context::qz_get_rows_device(int j, int64_t row0, int64_t n, double* q, int64_t rs, int64_t cs) const {
+  use_device();
+  if (j < 0 || j >= J_ || row0 < 0 || n < 0 || row0 + n > Nj_[j]) throw std::invalid_argument("row range out of bounds");
+  if (rs < 1 || cs < 1) throw std::invalid_argument("lc_ctx_get_qz_rows_device: the strides must be positive");
+  if (n == 0 || qz_[cur_].K < 1) return;
+  require_device_memory(q, "lc_ctx_get_qz_rows_device: q");
+  lck::UnpackQzLaunch a;
+  a.col = qz_[cur_].buf.p + goff_[(size_t)j] + row0;
+  a.ldq = NP_;
+  a.n = n;
+  a.K = qz_[cur_].K;
+  a.q = q;
+  a.rs = rs;
+  a.cs = cs;
+  LC_HIP(lck::launch_unpack_qz(a, stream_));
+}
+
+void Context::get_predictions_device(int j, int64_t row0, int64_t n, int32_t* label, double* logZ, double* logp) const {
+  use_device();
+  if (j < 0 || j >= J_ || row0 < 0 || n < 0 || row0 + n > Nj_[j]) throw std::invalid_argument("row range out of bounds");
+  if (!pred_vb_) throw std::invalid_argument("the context holds no prediction (lc_model_predict)");
+  if (logp && !pred_logp_) throw std::invalid_argument("the context's prediction has no log density");
+  if (n == 0) return;
+  if (label) require_device_memory(label, "lc_ctx_get_predictions_device: label");
+  if (logZ) require_device_memory(logZ, "lc_ctx_get_predictions_device: logZ");
+  if (logp) require_device_memory(logp, "lc_ctx_get_predictions_device: logp");
+  // the per-row outputs are plain arrays over the padded rows: a group's rows are one run of each
+  const size_t at = (size_t)(goff_[(size_t)j] + row0);
+  if (label) LC_HIP(hipMemcpyAsync(label, plabel_.p + at, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, stream_));
+  if (logZ) LC_HIP(hipMemcpyAsync(logZ, plogz_.p + at, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+  if (logp) LC_HIP(hipMemcpyAsync(logp, plogp_.p + at, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+}
+
 void Context::synth(int64_t N, int D, int K, const double* mu, const double* L, uint64_t seed, int64_t row_offset,
                     double hard) {
   synth_groups(1, &N, D, K, mu, L, nullptr, seed, nullptr, row_offset, hard);
@@ -427,6 +551,15 @@ void Context::get_rows(int j, int64_t row0, int64_t n, double* out) const {
   LC_HIP(hipStreamSynchronize(stream_));
   for (int64_t r = 0; r < n; ++r) std::memcpy(out + r * D_, tmp.data() + (size_t)r * DP_, D_ * sizeof(double));
 }
+
+#ifdef LC_TEST_HOOKS
+void Context::test_image(double* out) const {
+  use_device();
+  if (NP_ == 0) return;
+  LC_HIP(hipMemcpyAsync(out, X_.p, (size_t)NP_ * DP_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  LC_HIP(hipStreamSynchronize(stream_));
+}
+#endif
 
 // ---------------------------------------------------------------------------
 // qZ

@@ -125,6 +125,15 @@ class Context {
   // Host groups -> device (row-major, padded).  Element (n,d) of group j is at
   // Xj[j][n*row_stride + d*col_stride].
   void set_data(int J, const double* const* Xj, const int64_t* Nj, int D, int64_t row_stride, int64_t col_stride);
+  // Device groups -> the same image: Xj is a HOST array of J DEVICE pointers, strides >= 1.  Every pointer of a
+  // group with rows is checked (require_device_memory) before the layout changes or anything is launched; one launch packs
+  // all groups on the context's stream, which is synchronised before the call returns.  The image is a copy.
+  void set_data_device(int J, const double* const* Xj_dev, const int64_t* Nj, int D, int64_t row_stride, int64_t col_stride);
+  // The minimum over the valid entries that are numbers (+inf: none) and how many are NaN: what the pack of set_data_device
+  // left behind, or -- after anything else filled or changed the observations -- one reduction pass over the image.
+  void data_range(double* min, int64_t* n_nan);
+  // throws std::invalid_argument unless p is plain (not managed, not host) device memory of this context's device
+  void require_device_memory(const void* p, const std::string& what) const;
   // Single-group synthetic mixture generated on the device (+ initial qZ, K columns)
   void synth(int64_t N, int D, int K, const double* mu, const double* L, uint64_t seed, int64_t row_offset,
              double hard);
@@ -134,6 +143,10 @@ class Context {
                     uint64_t seed, const int64_t* group_ids, int64_t row_offset, double hard);
   // rows [row0, row0+n) of group j -> row-major n x D host buffer
   void get_rows(int j, int64_t row0, int64_t n, double* out) const;
+#ifdef LC_TEST_HOOKS
+  // tests (libcluster_hip_testhooks.so only): the whole padded image, pad rows and pad columns included -> [NP x DP] host buffer
+  void test_image(double* out) const;
+#endif
 
   int J() const { return J_; }
   int D() const { return D_; }
@@ -201,6 +214,9 @@ class Context {
   // group's rows are a block of a taller matrix (row-sharded learners), default N_j
   void qz_get_all_colmajor(double* const* out, const int64_t* ld = nullptr) const;
   void qz_get_rows(int j, int64_t row0, int64_t n, double* q, int64_t row_stride, int64_t col_stride) const;
+  // ... into DEVICE memory q_dev[r * row_stride + k * col_stride] (strides >= 1), enqueued on the context's stream: no
+  // synchronisation (synchronize())
+  void qz_get_rows_device(int j, int64_t row0, int64_t n, double* q_dev, int64_t row_stride, int64_t col_stride) const;
   void qz_get_column(int j, int k, double* out) const;  // N(j) doubles
   void qz_keep_columns(const std::vector<int>& keep);    // prune_clusters
   void qz_clone_to_alt();                                // alt <- copy of current (capacity K+1)
@@ -284,6 +300,8 @@ class Context {
   bool predict_diag(int mode, int Kp, const double* a, const double* w, const double* pc, const double* pe);
   // rows [row0, row0+n) of group j of the last prediction (any output may be null)
   void get_predictions(int j, int64_t row0, int64_t n, int32_t* label, double* logZ, double* logp) const;
+  // ... into DEVICE arrays, enqueued on the context's stream: no synchronisation (synchronize())
+  void get_predictions_device(int j, int64_t row0, int64_t n, int32_t* label_dev, double* logZ_dev, double* logp_dev) const;
   // no prediction is readable until the next one completes (a prediction that fails leaves none behind)
   void predict_clear() {
     pred_vb_ = pred_logp_ = false;
@@ -492,6 +510,14 @@ class Context {
   DevBuf<double> X_;
   DevBuf<int> rginfo_;      // only when J > 1
   DevBuf<int64_t> goff_d_;  // J+1
+  // set_data_device / data_range: [range 2 | source pointers J | rows J] of the last pack launch; range_ok_: range_min_ and
+  // range_nan_ describe the observations as they are (cleared by whatever replaces or rewrites them)
+  DevBuf<int64_t> ingest_tab_;
+  bool range_ok_ = false;
+  double range_min_ = 0.0;
+  int64_t range_nan_ = 0;
+  lck::PackRowsLaunch pack_launch(const std::vector<int64_t>& tab, int64_t rs, int64_t cs, double* image);
+  void read_range();
   DevBuf<unsigned char> ssitems_;  // sparse statistics: work items, and [klist | kptr | krec]
   DevBuf<int> ssints_;
   const int* sskptr_ = nullptr;

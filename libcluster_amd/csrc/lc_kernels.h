@@ -796,4 +796,36 @@ constexpr int TOPIC_LDS_BYTES = 40 * 1024;  // per workgroup at most: four workg
 size_t topic_infer_lds(int K, int T, int threads, const int64_t* nrows, int docs, int64_t* tile_cap, int* e_lds);
 hipError_t launch_topic_infer(const TopicInferLaunch& a, size_t lds_bytes, hipStream_t stream);
 
+// ---- device-resident data in, row results out (lc_kernels_ingest.hip) -----------------------------------------
+// The padded image X [NP x DP] of J groups from strided DEVICE sources, one launch for all groups: element (n, d) of group j
+// is src[j][n * rs + d * cs] (n < Nj[j], d < D), the columns D ... DP - 1 and every pad row become +0.0; every byte of the
+// image is written.  rs == 1 (column-major sources) goes through an LDS tile, everything else reads along the rows
+// (coalesced for cs == 1).  range[0] is left holding the key of the minimum over the valid entries that are numbers
+// (data_range_decode), range[1] the number of NaNs among them: integer atomics, the same bits on every run; the launcher
+// initialises both.  X == nullptr: the two values alone (over an image that exists: src[j] = image row goff[j], rs = DP, cs = 1).
+struct PackRowsLaunch {
+  int J = 0, D = 0, DP = 0;
+  int64_t NP = 0;                       // padded rows of the image (goff[J])
+  const double* const* src = nullptr;   // [J] device array of device pointers (a group without rows: never read)
+  const int64_t* Nj = nullptr;          // [J]
+  const int64_t* goff = nullptr;        // [J + 1] padded row offsets
+  int64_t rs = 0, cs = 0;               // >= 1
+  double* X = nullptr;
+  unsigned long long* range = nullptr;  // [2]
+};
+hipError_t launch_pack_rows(const PackRowsLaunch& a, hipStream_t stream);
+// host: the two words of PackRowsLaunch::range -> minimum (+inf: no valid entry is a number) and NaN count
+void data_range_decode(const unsigned long long* range_h, double* min, int64_t* n_nan);
+// q[r * rs + k * cs] = col[k * ldq + r], r < n, k < K: n rows of the column-major qZ (col points at the first of them) into a
+// strided device destination.  Row-major destinations (cs == 1) go through an LDS tile; nothing outside the n x K entries
+// is written.
+struct UnpackQzLaunch {
+  const double* col = nullptr;
+  int64_t ldq = 0, n = 0;
+  int K = 0;
+  double* q = nullptr;
+  int64_t rs = 0, cs = 0;  // >= 1
+};
+hipError_t launch_unpack_qz(const UnpackQzLaunch& a, hipStream_t stream);
+
 }  // namespace lck

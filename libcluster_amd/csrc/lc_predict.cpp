@@ -436,6 +436,7 @@ void Context::holes_fill(const double* fill) {
   LC_HIP(lck::launch_holes_fill(a, stream_));
   LC_HIP(hipStreamSynchronize(stream_));  // (hpack_ and ptab_ are free again)
   dcache_invalidate();                    // (the observations changed)
+  range_ok_ = false;
 }
 
 void Context::predict_holes(int Kp, const double* tt, const double* ps, const double* pe, const double* mean,
@@ -528,6 +529,7 @@ void Context::predict_holes(int Kp, const double* tt, const double* ps, const do
   qz_[cur_].hash_ok = false;
   qz_written(qz_[cur_]);
   dcache_invalidate();  // (the observations changed)
+  range_ok_ = false;
   pred_holes_ = true;
   pred_holes_var_ = gnu != nullptr;
   pred_holes_draws_ = ndraws;

@@ -13,10 +13,14 @@
 // lcx_test_holes_scan (launch_holes_scan, launch_holes_fill), lcx_test_predict_holes (launch_predict_holes / _var / _keep) and
 // lcx_test_holes_draws (launch_predict_holes_keep, launch_holes_draws), cases in tests/test_gpu_holes_kernels.py (inputs:
 // tests/holes_kernel_cases.py, held to their conditions without a device by tests/test_holes_kernels_refs_host.py).
+// The hooks of lc_kernels_ingest.hip follow them: lcx_test_pack_rows, lcx_test_unpack_qz and lcx_test_ctx_image
+// (tests/ingest_hooks.py; cases in tests/test_gpu_ingest_kernels.py and tests/test_gpu_device_io.py).
 #include <algorithm>
 #include <cstdio>
+#include <exception>
 #include <vector>
 
+#include "lc_ctx.hpp"
 #include "lc_device.hpp"
 #include "lc_predict.hpp"
 
@@ -1505,4 +1509,89 @@ LC_HOOK lcx_test_holes_draws(double* X, int DP, int D, int Kp, double* col, i64 
   }
   if (e == hipSuccess) e = lck::launch_holes_draws(v, nullptr);
   return s.finish(e);
+}
+
+// ---- device-resident data in, row results out (lc_kernels_ingest.hip; tests/ingest_hooks.py, tests/test_gpu_ingest_kernels.py) ----
+// launch_pack_rows over J host sources: src[j] is a buffer of src_elems[j] doubles in which element (n, d) of group j sits at
+// n * rs + d * cs (checked here for every group with rows).  image (io) is guard + NP * DP + guard doubles as the caller filled
+// them (NaN: every byte the kernel owes shows), NP = the groups' rows padded to 16 each, DP = padded_dim_wide(D); image_elems
+// must say exactly that.  range (out) [2]: the raw words; min / n_nan (out): what data_range_decode makes of them.
+LC_HOOK lcx_test_pack_rows(const double* const* src, const i64* src_elems, int J, const i64* Nj, int D, i64 rs, i64 cs, i64 guard,
+                           double* image, i64 image_elems, unsigned long long* range, double* min, i64* n_nan) {
+  if (!src || !src_elems || !Nj || !image || !range || !min || !n_nan) return -1;
+  if (J < 1 || J > (1 << 20) || D < 1 || D > 4096 || rs < 1 || cs < 1 || rs > ((i64)1 << 30) || cs > ((i64)1 << 30)) return -1;
+  if (guard < 0 || guard > (1 << 20)) return -1;
+  const int DP = lck::padded_dim_wide(D);
+  std::vector<int64_t> goff((size_t)J + 1, 0), tab(2 * (size_t)J, 0);
+  for (int j = 0; j < J; ++j) {
+    if (Nj[j] < 0 || Nj[j] > ((i64)1 << 30)) return -1;
+    if (Nj[j] > 0 && (!src[j] || (Nj[j] - 1) * rs + (i64)(D - 1) * cs >= src_elems[j])) return -1;
+    goff[(size_t)j + 1] = goff[(size_t)j] + (Nj[j] + RG - 1) / RG * RG;
+  }
+  const i64 NP = goff[(size_t)J];
+  const size_t G = (size_t)guard;
+  if (image_elems != NP * DP + 2 * guard) return -1;
+  Scope s;
+  for (int j = 0; j < J; ++j) {
+    tab[(size_t)j] = Nj[j] > 0 ? (int64_t)reinterpret_cast<intptr_t>(s.in(src[j], (size_t)src_elems[j])) : 0;
+    tab[(size_t)J + j] = Nj[j];
+  }
+  const int64_t* dtab = s.in(tab.data(), tab.size());
+  lck::PackRowsLaunch a;
+  a.J = J;
+  a.D = D;
+  a.DP = DP;
+  a.NP = NP;
+  a.src = reinterpret_cast<const double* const*>(dtab);
+  a.Nj = dtab + J;
+  a.goff = s.in(goff.data(), goff.size());
+  a.rs = rs;
+  a.cs = cs;
+  a.X = s.io(image, (size_t)image_elems) + G;
+  a.range = s.out(range, 2);
+  if (!s.ok()) return s.finish(hipSuccess);
+  const int rc = s.finish(lck::launch_pack_rows(a, nullptr));
+  if (rc == 0) {
+    int64_t nn = 0;
+    lck::data_range_decode(range, min, &nn);
+    *n_nan = nn;
+  }
+  return rc;
+}
+
+// launch_unpack_qz: rows [off, off + n) of the K columns of col [K x ldq] into q (io: guard + q_elems + guard doubles as the
+// caller filled them), entry (r, k) at guard + r * rs + k * cs, which must lie inside the q_elems for every r < n, k < K.
+LC_HOOK lcx_test_unpack_qz(const double* col, i64 ldq, int K, i64 off, i64 n, double* q, i64 q_elems, i64 guard, i64 rs, i64 cs) {
+  if (!col || !q) return -1;
+  if (K < 1 || K > 4096 || ldq < 1 || ldq > ((i64)1 << 30) || off < 0 || n < 0 || off > ldq - n) return -1;
+  if (rs < 1 || cs < 1 || rs > ((i64)1 << 30) || cs > ((i64)1 << 30) || guard < 0 || guard > (1 << 20) || q_elems < 0) return -1;
+  if (n > 0 && (n - 1) * rs + (i64)(K - 1) * cs >= q_elems) return -1;
+  Scope s;
+  lck::UnpackQzLaunch a;
+  a.col = s.in(col, (size_t)K * (size_t)ldq) + off;
+  a.ldq = ldq;
+  a.n = n;
+  a.K = K;
+  a.q = s.io(q, (size_t)(q_elems + 2 * guard)) + guard;
+  a.rs = rs;
+  a.cs = cs;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_unpack_qz(a, nullptr));
+}
+
+// the whole padded image of a context (an lc_ctx*: the handle holds its lcc::Context first) -> out [NP x DP]; out_elems must
+// say exactly that (np / dp, when given, report the two sizes either way)
+LC_HOOK lcx_test_ctx_image(void* ctx, double* out, i64 out_elems, i64* np, int* dp) {
+  if (!ctx) return -1;
+  const lcc::Context* c = reinterpret_cast<const lcc::Context*>(ctx);
+  if (np) *np = c->NP();
+  if (dp) *dp = c->DP();
+  if (!out) return out_elems == 0 ? 0 : -1;
+  if (c->J() < 1 || out_elems != c->NP() * c->DP()) return -1;
+  try {
+    c->test_image(out);
+  } catch (const std::exception&) {
+    return (int)hipErrorUnknown;
+  }
+  return 0;
 }

@@ -342,6 +342,32 @@ void hammer_capi() {
     CHECK(std::strstr(lc_last_error(), "HIP") != nullptr);
     CHECK(cnt[2] == 0 && grp[(size_t)3 * 64 - 1] == -1 && row[(size_t)3 * 64 - 1] == -1 && std::isnan(sc[(size_t)3 * 64 - 1]));
   }
+  // device-resident data (lc_ctx_set_data_device and its neighbours): the argument checks answer before the layout changes
+  // or anything is launched; a valid call builds the layout and the pointer table and fails in its one launch
+  {
+    int Jc = 0;
+    CHECK(lc_ctx_set_data_device(ctx, J, ptr, Nj, D, 0, 1) == LC_EINVAL);
+    const double* holed[3] = {ptr[0], nullptr, ptr[2]};
+    CHECK(lc_ctx_set_data_device(ctx, J, holed, Nj, D, D, 1) == LC_EINVAL);
+    CHECK(std::strstr(lc_last_error(), "Xj[1]") != nullptr);
+    CHECK(lc_ctx_dims(ctx, &Jc, nullptr, nullptr, nullptr) == LC_OK && Jc == J);
+    CHECK(lc_ctx_get_rows(ctx, 2, 2460, 40, back.data()) == LC_OK && back[0] == X[2][(size_t)2460 * D]);  // (untouched)
+    std::vector<double> q((size_t)37 * 3);
+    CHECK(lc_ctx_get_qz_rows_device(ctx, 1, 30, 8, q.data(), 3, 1) == LC_EINVAL);
+    CHECK(lc_ctx_get_qz_rows_device(ctx, 1, 0, 37, q.data(), 3, 0) == LC_EINVAL);
+    CHECK(lc_ctx_get_predictions_device(ctx, 1, 0, 37, nullptr, q.data(), nullptr) == LC_EINVAL);
+    lc_model* model = nullptr;
+    CHECK(lc_learn_ctx(99, ctx, 1.0, nullptr, 1.0, -1, 0, 0, 1, &model, nullptr) == LC_EINVAL);
+    CHECK(lc_learn_ctx(LC_ALGO_BGMM, ctx, 1.0, nullptr, 1.0, -1, 0, 0, 1, &model, nullptr) == LC_EINVAL && model == nullptr);
+    double lo = 0;
+    int64_t nn = 0;
+    CHECK(lc_ctx_data_range(ctx, &lo, &nn) == LC_EHIP);  // (the reduction is a launch)
+    const int64_t Ne[3] = {0, 0, 0};
+    CHECK(lc_ctx_set_data_device(ctx, J, holed, Ne, D, D, 1) == LC_OK);  // no rows: nothing to check, nothing to launch
+    CHECK(lc_ctx_data_range(ctx, &lo, &nn) == LC_OK && std::isinf(lo) && nn == 0);
+    CHECK(lc_ctx_set_data_device(ctx, J, ptr, Nj, D, D, 1) == LC_EHIP);
+    CHECK(std::strstr(lc_last_error(), "HIP") != nullptr);
+  }
   lc_ctx_destroy(ctx);
 
   // sharded learners: every shard thread fails in its first launch -- the abort / release / rethrow path of

@@ -2,7 +2,7 @@
 # Host code under sanitizers (CPU build, no GPU needed).   tools/sanitize_host.sh [asan|tsan|all]
 #
 # Builds every HOST translation unit of the library -- lc_ctx.cpp, lc_comm.cpp, lc_engine.cpp, lc_topic.cpp,
-# lc_topic_predict.cpp, lc_predict.cpp, lc_capi.cpp and the host halves of the nine .hip files (--cuda-host-only: launch planners, grids, LDS grants) --
+# lc_topic_predict.cpp, lc_predict.cpp, lc_capi.cpp and the host halves of the thirteen .hip files (--cuda-host-only: launch planners, grids, LDS grants) --
 # twice, with -fsanitize=address,undefined and with -fsanitize=thread, against tools/sanitize/hip_host_stub.cpp (a
 # host-memory stand-in for the HIP runtime: kernels do not run, launches fail), and runs
 #   * tools/sanitize/host_hammer.cpp: M-step pool, block cache / cache_release_thread, heap and shared-memory all-reduce
@@ -26,7 +26,7 @@ build() {  # $1 = tag, $2 = sanitizer flags
   mkdir -p "$d"
   local common="-O1 -g -fno-omit-frame-pointer -std=c++17 -fPIC -I$ROOT/include -I$CSRC $san"
   local pids=()
-  for f in lc_kernels_estep lc_kernels_suffstat lc_kernels_diag lc_kernels_aux lc_kernels_fused lc_kernels_predict lc_kernels_holes lc_kernels_topic lc_kernels_rank; do
+  for f in lc_kernels_estep lc_kernels_suffstat lc_kernels_diag lc_kernels_aux lc_kernels_fused lc_kernels_predict lc_kernels_holes lc_kernels_topic lc_kernels_rank lc_kernels_sample lc_kernels_loo lc_kernels_select lc_kernels_ingest; do
     $HIPCC --offload-arch=gfx950 --cuda-host-only $common -c "$CSRC/$f.hip" -o "$d/$f.o" 2>>"$d/build.log" & pids+=($!)
   done
   local cxx="/opt/rocm/lib/llvm/bin/clang++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include"  # (plain C++: these are host sources)
@@ -40,7 +40,7 @@ build() {  # $1 = tag, $2 = sanitizer flags
   nm -u "$d"/lc_kernels_*.o | grep -o '__hip_fatbin_[0-9a-f]*' | sort -u |
     awk '{print "const char " $1 "[8] __attribute__((section(\".hip_fatbin\"))) = {0};"}' > "$d/fatbin_syms.c"
   gcc -c "$d/fatbin_syms.c" -o "$d/fatbin_syms.o" || return 1
-  local objs="$d/lc_kernels_estep.o $d/lc_kernels_suffstat.o $d/lc_kernels_diag.o $d/lc_kernels_aux.o $d/lc_kernels_fused.o $d/lc_kernels_predict.o $d/lc_kernels_holes.o $d/lc_kernels_topic.o $d/lc_kernels_rank.o \
+  local objs="$d/lc_kernels_estep.o $d/lc_kernels_suffstat.o $d/lc_kernels_diag.o $d/lc_kernels_aux.o $d/lc_kernels_fused.o $d/lc_kernels_predict.o $d/lc_kernels_holes.o $d/lc_kernels_topic.o $d/lc_kernels_rank.o $d/lc_kernels_sample.o $d/lc_kernels_loo.o $d/lc_kernels_select.o $d/lc_kernels_ingest.o \
     $d/lc_ctx.o $d/lc_predict.o $d/lc_comm.o $d/lc_engine.o $d/lc_topic.o $d/lc_topic_predict.o $d/lc_capi.o $d/hip_host_stub.o $d/fatbin_syms.o"
   # (clang++ directly: hipcc would add the real libamdhip64 to the link)
   /opt/rocm/lib/llvm/bin/clang++ $san -shared-libsan -shared -o "$d/libcluster_hip.so" $objs -lpthread -ldl -lrt -Wl,-rpath,"$CLANG_RT" 2>>"$d/build.log" || { tail -20 "$d/build.log"; return 1; }
