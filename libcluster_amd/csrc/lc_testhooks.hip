@@ -14,7 +14,10 @@
 // lcx_test_holes_draws (launch_predict_holes_keep, launch_holes_draws), cases in tests/test_gpu_holes_kernels.py (inputs:
 // tests/holes_kernel_cases.py, held to their conditions without a device by tests/test_holes_kernels_refs_host.py).
 // The hooks of lc_kernels_ingest.hip follow them: lcx_test_pack_rows, lcx_test_unpack_qz and lcx_test_ctx_image
-// (tests/ingest_hooks.py; cases in tests/test_gpu_ingest_kernels.py and tests/test_gpu_device_io.py).
+// (tests/ingest_hooks.py; cases in tests/test_gpu_ingest_kernels.py and tests/test_gpu_device_io.py).  Last come the launchers
+// of lc_kernels_sample.hip (lcx_test_sample, lcx_test_cond_draws; tests/test_gpu_sample_kernels.py), lc_kernels_rank.hip
+// (lcx_test_top_rows) and lc_kernels_select.hip (lcx_test_score_select, lcx_test_score_counts, lcx_test_rows_beyond;
+// tests/test_gpu_rank_select_kernels.py).
 #include <algorithm>
 #include <cstdio>
 #include <exception>
@@ -1594,4 +1597,261 @@ LC_HOOK lcx_test_ctx_image(void* ctx, double* out, i64 out_elems, i64* np, int* 
     return (int)hipErrorUnknown;
   }
   return 0;
+}
+
+// ---- the samplers, ranking and threshold queries (lc_kernels_sample.hip, lc_kernels_rank.hip, lc_kernels_select.hip) -----------
+// Bound by tests/test_gpu_sample_kernels.py and tests/test_gpu_rank_select_kernels.py.  Every hook: host arrays in, ONE launcher,
+// host arrays out.  Outputs are guard + payload + guard elements as the caller filled them (a canary): the kernels see the middle
+// part.  A combination the launcher refuses by its own conditions (restated here) goes to the launcher with the caller's host
+// pointers, none of which is then used: nothing is launched, and its refusal is what the test asks for.
+namespace {
+
+bool guard_ok(i64 guard) { return guard >= 0 && guard <= (1 << 20); }
+
+// the score columns of a ranking or threshold launch as the kernels address them: C columns of ld >= NP elements, NP a multiple
+// of 16, rginfo [NP / 16] with counts 0 ... 16 or (null) 0 <= nrows <= NP, label [NP] or null
+bool score_columns_ok(const double* col, i64 ld, int C, i64 NP, const int* rginfo, i64 nrows) {
+  if (C < 1 || C > 4096 || NP < 0 || NP % RG != 0 || NP > ((i64)1 << 24) || ld < NP || ld > ((i64)1 << 25)) return false;
+  if ((i64)C * ld > ((i64)1 << 26) || (ld > 0 && !col)) return false;
+  return rginfo ? rginfo_ok(rginfo, NP / RG, (i64)1 << 26) : (nrows >= 0 && nrows <= NP);
+}
+void score_columns_upload(Scope& s, lck::ScoreColumns& c, const double* col, i64 ld, int C, i64 NP, const int* rginfo, i64 nrows,
+                          const int* label, int label0) {
+  c.col = s.in(col, (size_t)C * (size_t)ld);
+  c.ld = ld;
+  c.C = C;
+  c.NP = NP;
+  c.rginfo = rginfo ? s.in(rginfo, (size_t)(NP / RG)) : nullptr;
+  c.nrows = nrows;
+  c.label = label ? s.in(label, (size_t)NP) : nullptr;
+  c.label0 = label0;
+}
+void score_columns_numbers(lck::ScoreColumns& c, const double* col, i64 ld, int C, i64 NP, const int* rginfo, i64 nrows,
+                           const int* label, int label0) {
+  c.col = col;
+  c.ld = ld;
+  c.C = C;
+  c.NP = NP;
+  c.rginfo = rginfo;
+  c.nrows = nrows;
+  c.label = label;
+  c.label0 = label0;
+}
+// columns_ok of lc_kernels_select.hip, restated
+bool select_columns_refused(int C, i64 NP, i64 ld) { return C < 1 || C > 65535 || NP < 0 || NP % RG != 0 || ld < NP; }
+
+}  // namespace
+
+// launch_sample.  rginfo [ceil(NP / 16)] with goff [J + 1], or both null (J = 1, the first nrows rows valid); cdf [J x Kp]; klast
+// [J]; loc [Kp x D] (null in mode 2); fac [Kp x D x D] (mode 0) or [Kp x D]; shape [Kp].  X (io) guard + NP * DP + guard doubles,
+// label (io) guard + NP + guard ints.
+LC_HOOK lcx_test_sample(int mode, int D, int DP, int Kp, i64 NP, i64 nrows, i64 row_offset, unsigned long long seed, const int* rginfo,
+                        const i64* goff, int J, const double* cdf, const int* klast, const double* loc, const double* fac,
+                        const double* shape, i64 guard, double* X, int* label) {
+  if (!X || !label || !guard_ok(guard) || NP < 1 || NP > ((i64)1 << 24) || J < 1 || J > (1 << 20)) return -1;
+  lck::SampleLaunch a;
+  a.mode = mode;
+  a.DP = DP;
+  a.D = D;
+  a.Kp = Kp;
+  a.nrows = nrows;
+  a.NP = NP;
+  a.row_offset = row_offset;
+  a.seed = seed;
+  if (Kp < 1 || D < 1 || DP < D || DP % 2 != 0 || !cdf || !klast || !fac || !shape || mode < 0 || mode > 2 || (mode != 2 && !loc)) {
+    a.X = X;
+    a.label = label;
+    a.cdf = cdf;
+    a.klast = klast;
+    a.loc = loc;
+    a.fac = fac;
+    a.shape = shape;
+    return (int)lck::launch_sample(a, nullptr);
+  }
+  if (Kp > 4096 || D > 1024 || DP > 1024 || row_offset < 0 || row_offset > ((i64)1 << 39)) return -1;
+  const i64 nrg = (NP + RG - 1) / RG;
+  if ((rginfo != nullptr) != (goff != nullptr) || (!rginfo && J != 1)) return -1;
+  if (rginfo ? !rginfo_ok(rginfo, nrg, J) : (nrows < 0 || nrows > NP)) return -1;
+  for (int j = 0; j < J; ++j)
+    if (klast[j] < 0 || klast[j] >= Kp) return -1;
+  const size_t G = (size_t)guard, nfac = mode == 0 ? (size_t)Kp * D * D : (size_t)Kp * D;
+  Scope s;
+  a.X = s.io(X, (size_t)NP * DP + 2 * G) + G;
+  a.label = s.io(label, (size_t)NP + 2 * G) + G;
+  a.rginfo = rginfo ? s.in(rginfo, (size_t)nrg) : nullptr;
+  a.goff = goff ? reinterpret_cast<const int64_t*>(s.in(goff, (size_t)J + 1)) : nullptr;
+  a.cdf = s.in(cdf, (size_t)J * Kp);
+  a.klast = s.in(klast, (size_t)J);
+  a.loc = loc ? s.in(loc, (size_t)Kp * D) : nullptr;
+  a.fac = s.in(fac, nfac);
+  a.shape = s.in(shape, (size_t)Kp);
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_sample(a, nullptr));
+}
+
+// launch_predict_cond_draws alone, on what predict_cond_kernel would have left: col [Kp x ldq] holds t_k and logp [nrg * 16] the
+// row's log density, both the caller's.  X [nrg * 16 x DP]; ttab [J x Kp]; pexp / cq [Kp]; mext [Kp x Dae]; T [Kp x Dae x Dbp];
+// Lt [Kp x Dbp x Dbp]; goff [J + 1] or null.  draws (io) guard + nrg * 16 * ndraws * Db + guard doubles, label (io) guard +
+// nrg * 16 * ndraws + guard ints (ndraws counted as at least 1).
+LC_HOOK lcx_test_cond_draws(const double* X, int DP, int Da, int Dae, int Db, int Dbp, int Kp, const double* col, i64 ldq, i64 nrg,
+                            const int* rginfo, i64 nrows, int J, const double* ttab, const double* pexp, const double* mext,
+                            const double* T, const double* logp, const i64* goff, const double* Lt, const double* cq, int ndraws,
+                            unsigned long long seed, i64 guard, double* draws, int* label) {
+  if (!X || !col || !ttab || !pexp || !mext || !T || !logp || !Lt || !cq || !draws || !label || !guard_ok(guard)) return -1;
+  if (!pred_rows_ok(nrg, ldq, rginfo, nrows, J) || (!rginfo && J != 1) || (goff && !rginfo) || nrg > (1 << 16)) return -1;
+  lck::PredictCondDrawsLaunch v;
+  lck::PredictCondLaunch& a = v.c;
+  a.DP = DP;
+  a.Da = Da;
+  a.Dae = Dae;
+  a.Db = Db;
+  a.Dbp = Dbp;
+  a.Kp = Kp;
+  a.ldq = ldq;
+  a.nrg = nrg;
+  a.nrows = nrows;
+  v.ndraws = ndraws;
+  v.seed = seed;
+  if (Kp < 1 || Da < 1 || Db < 1 || DP < Da || Dae < Da + 1 || Dae % 4 != 0 || Dbp < Db || Dbp % 4 != 0 || ndraws < 1 ||
+      ndraws > lck::DRAWS_MAX) {
+    v.Lt = Lt;
+    v.cq = cq;
+    v.draws = draws;
+    v.label = label;
+    return (int)lck::launch_predict_cond_draws(v, nullptr);
+  }
+  if (Kp > 4096 || DP > 4096 || Dae > 4096 || Dbp > 4096) return -1;
+  const size_t NP = (size_t)(nrg * RG), G = (size_t)guard;
+  Scope s;
+  a.X = s.in(X, NP * DP);
+  a.col = const_cast<double*>(s.in(col, (size_t)Kp * (size_t)ldq));
+  a.rginfo = rginfo ? s.in(rginfo, (size_t)nrg) : nullptr;
+  a.ttab = s.in(ttab, (size_t)J * Kp);
+  a.pexp = s.in(pexp, (size_t)Kp);
+  a.mext = s.in(mext, (size_t)Kp * Dae);
+  a.T = s.in(T, (size_t)Kp * Dae * Dbp);
+  a.logp = const_cast<double*>(s.in(logp, NP));
+  v.goff = goff ? reinterpret_cast<const int64_t*>(s.in(goff, (size_t)J + 1)) : nullptr;
+  v.Lt = s.in(Lt, (size_t)Kp * Dbp * Dbp);
+  v.cq = s.in(cq, (size_t)Kp);
+  v.draws = s.io(draws, NP * ndraws * Db + 2 * G) + G;
+  v.label = s.io(label, NP * ndraws + 2 * G) + G;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_predict_cond_draws(v, nullptr));
+}
+
+// launch_top_rows.  col [C x ld]; rginfo [NP / 16] or null (then nrows); label [NP] or null.  pkey / ppos (io) guard +
+// top_rows_chunks(NP) * C * m + guard, out_score / out_pos (io) guard + C * m + guard.
+LC_HOOK lcx_test_top_rows(const double* col, i64 ld, int C, i64 NP, const int* rginfo, i64 nrows, const int* label, int m, int largest,
+                          int nchunks, i64 guard, double* pkey, long long* ppos, double* out_score, long long* out_pos) {
+  if (!pkey || !ppos || !out_score || !out_pos || !guard_ok(guard)) return -1;
+  lck::TopRowsLaunch a;
+  a.ld = ld;
+  a.C = C;
+  a.NP = NP;
+  a.nrows = nrows;
+  a.m = m;
+  a.largest = largest;
+  a.nchunks = nchunks;
+  if (m < 1 || m > lck::TOP_MAX_M || C < 1 || C > 65535 || NP < 0 || NP % RG != 0 || ld < NP || nchunks != lck::top_rows_chunks(NP)) {
+    a.col = col;
+    a.rginfo = rginfo;
+    a.label = label;
+    a.pkey = pkey;
+    a.ppos = ppos;
+    a.out_score = out_score;
+    a.out_pos = out_pos;
+    return (int)lck::launch_top_rows(a, nullptr);
+  }
+  if (!score_columns_ok(col, ld, C, NP, rginfo, nrows)) return -1;
+  const size_t G = (size_t)guard, np = (size_t)nchunks * C * m;
+  Scope s;
+  a.col = s.in(col, (size_t)C * (size_t)ld);
+  a.rginfo = rginfo ? s.in(rginfo, (size_t)(NP / RG)) : nullptr;
+  a.label = label ? s.in(label, (size_t)NP) : nullptr;
+  a.pkey = s.io(pkey, np + 2 * G) + G;
+  a.ppos = s.io(ppos, np + 2 * G) + G;
+  a.out_score = s.io(out_score, (size_t)C * m + 2 * G) + G;
+  a.out_pos = s.io(out_pos, (size_t)C * m + 2 * G) + G;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_top_rows(a, nullptr));
+}
+
+// launch_score_select.  The columns of lcx_test_top_rows with label0; probs [nprobs].  hist (io) [C x SEL_HIST_WORDS] and state
+// (io) [C x SEL_STATE_WORDS] go up as the caller filled them and come back whole; out (io) guard + C + 2 C nprobs + guard.
+LC_HOOK lcx_test_score_select(const double* col, i64 ld, int C, i64 NP, const int* rginfo, i64 nrows, const int* label, int label0,
+                              int nprobs, const double* probs, i64 guard, unsigned long long* hist, long long* state,
+                              long long* out) {
+  if (!probs || !out || !guard_ok(guard) || nprobs < 0 || nprobs > 64) return -1;
+  lck::ScoreSelectLaunch a;
+  a.nprobs = nprobs;
+  for (int i = 0; i < nprobs && i < lck::SEL_MAX; ++i) a.probs[i] = probs[i];
+  if (select_columns_refused(C, NP, ld) || NP == 0 || nprobs < 1 || nprobs > lck::SEL_MAX || !hist || !state) {
+    score_columns_numbers(a.s, col, ld, C, NP, rginfo, nrows, label, label0);
+    a.hist = hist;
+    a.state = state;
+    a.out = out;
+    return (int)lck::launch_score_select(a, nullptr);
+  }
+  if (!score_columns_ok(col, ld, C, NP, rginfo, nrows)) return -1;
+  const size_t G = (size_t)guard;
+  Scope s;
+  score_columns_upload(s, a.s, col, ld, C, NP, rginfo, nrows, label, label0);
+  a.hist = s.io(hist, (size_t)C * lck::SEL_HIST_WORDS);
+  a.state = s.io(state, (size_t)C * lck::SEL_STATE_WORDS);
+  a.out = s.io(out, (size_t)C + 2 * (size_t)C * nprobs + 2 * G) + G;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_score_select(a, nullptr));
+}
+
+// launch_score_counts.  thr [nthr]; out (io) guard + C * (1 + nthr) + guard raw words, as the caller filled them.
+LC_HOOK lcx_test_score_counts(const double* col, i64 ld, int C, i64 NP, const int* rginfo, i64 nrows, const int* label, int label0,
+                              int nthr, const double* thr, i64 guard, unsigned long long* out) {
+  if (!thr || !out || !guard_ok(guard) || nthr < 0 || nthr > 64) return -1;
+  lck::ScoreCountsLaunch a;
+  a.nthr = nthr;
+  for (int i = 0; i < nthr && i < lck::SEL_MAX; ++i) a.thr[i] = thr[i];
+  if (select_columns_refused(C, NP, ld) || nthr < 1 || nthr > lck::SEL_MAX) {
+    score_columns_numbers(a.s, col, ld, C, NP, rginfo, nrows, label, label0);
+    a.out = out;
+    return (int)lck::launch_score_counts(a, nullptr);
+  }
+  if (!score_columns_ok(col, ld, C, NP, rginfo, nrows)) return -1;
+  const size_t G = (size_t)guard;
+  Scope s;
+  score_columns_upload(s, a.s, col, ld, C, NP, rginfo, nrows, label, label0);
+  a.out = s.io(out, (size_t)C * (1 + (size_t)nthr) + 2 * G) + G;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_score_counts(a, nullptr));
+}
+
+// launch_rows_beyond.  One column [ld]; chunkoff (io) guard + top_rows_chunks(NP) + guard, total (io) [1], pos / score (io) guard
+// + capacity + guard each (or null).
+LC_HOOK lcx_test_rows_beyond(const double* col, i64 ld, int C, i64 NP, const int* rginfo, i64 nrows, const int* label, int label0,
+                             double thr, int above, i64 capacity, int nchunks, i64 guard, long long* chunkoff, long long* total,
+                             long long* pos, double* score) {
+  if (!chunkoff || !total || !guard_ok(guard) || capacity < 0 || capacity > ((i64)1 << 24)) return -1;
+  lck::RowsBeyondLaunch a;
+  a.thr = thr;
+  a.above = above;
+  a.capacity = capacity;
+  a.nchunks = nchunks;
+  if (select_columns_refused(C, NP, ld) || C != 1 || nchunks != lck::top_rows_chunks(NP) || (capacity > 0 && (!pos || !score))) {
+    score_columns_numbers(a.s, col, ld, C, NP, rginfo, nrows, label, label0);
+    a.chunkoff = chunkoff;
+    a.total = total;
+    a.pos = pos;
+    a.score = score;
+    return (int)lck::launch_rows_beyond(a, nullptr);
+  }
+  if (!score_columns_ok(col, ld, C, NP, rginfo, nrows)) return -1;
+  const size_t G = (size_t)guard;
+  Scope s;
+  score_columns_upload(s, a.s, col, ld, C, NP, rginfo, nrows, label, label0);
+  a.chunkoff = s.io(chunkoff, (size_t)nchunks + 2 * G) + G;
+  a.total = s.io(total, 1);
+  a.pos = pos ? s.io(pos, (size_t)capacity + 2 * G) + G : nullptr;
+  a.score = score ? s.io(score, (size_t)capacity + 2 * G) + G : nullptr;
+  if (!s.ok()) return s.finish(hipSuccess);
+  return s.finish(lck::launch_rows_beyond(a, nullptr));
 }

@@ -240,3 +240,235 @@ def ks_whitened_pooled(parts):
     for d in range(Db):
         out.append(stats.kstest(np.concatenate([stats.t(eta).cdf(w[:, d]) for w, eta in parts]), "uniform"))
     return out
+
+
+# ---- exact values on the documented streams (include/libcluster_hip.h; tests/test_gpu_sample_kernels.py) ---------------------
+# Everything below is written from the counter table of the header and DESIGN 4.16.  `xp` is the arithmetic the values are
+# formed in: F64 (numpy) or MP (40-digit mpmath on object arrays, tests/test_sample_exact_refs_host.py); the Philox words,
+# the uniforms (exact in float64 by construction) and every DECISION (which attempt is accepted, which component is chosen)
+# are float64's either way, so the two evaluations differ by rounding alone.
+TAG_GAMMA_N, TAG_GAMMA_U, TAG_GAMMA_B, TAG_LOMAX = 0x12, 0x13, 0x14, 0x15
+GAMMA_ATTEMPTS = 64  # RNG_GAMMA_ATTEMPTS
+NEAR = 1e-9          # a decision closer than this to its boundary is left out of a comparison (cap: EXCLUDED_SHARE)
+EXCLUDED_SHARE = 1e-3
+
+
+class F64:
+    log, exp, expm1, sqrt, cos, sin = np.log, np.exp, np.expm1, np.sqrt, np.cos, np.sin
+    two_pi = 6.283185307179586476925
+
+    @staticmethod
+    def lift(x):
+        return np.asarray(x, dtype=np.float64)
+
+    @staticmethod
+    def zeros(shape):
+        return np.zeros(shape)
+
+
+def mp_backend(digits=40):
+    """the same operations at `digits` decimal digits: object arrays of mpmath.mpf"""
+    import mpmath
+
+    mpmath.mp.dps = digits
+    f = lambda fn: np.frompyfunc(fn, 1, 1)  # noqa: E731
+
+    class MP:
+        log, exp, expm1, sqrt, cos, sin = f(mpmath.log), f(mpmath.exp), f(mpmath.expm1), f(mpmath.sqrt), f(mpmath.cos), f(mpmath.sin)
+        two_pi = 2 * mpmath.pi
+
+        @staticmethod
+        def lift(x):
+            return np.frompyfunc(lambda v: mpmath.mpf(float(v)), 1, 1)(np.asarray(x, dtype=np.float64))
+
+        @staticmethod
+        def zeros(shape):
+            z = np.empty(shape, dtype=object)
+            z.fill(mpmath.mpf(0))
+            return z
+
+    return MP
+
+
+def _words(seed, c0, c1, c2, tag, sub=0):
+    return philox4x32_10(c0, c1, c2, tag | (sub << 8), seed & 0xFFFFFFFF, seed >> 32)
+
+
+def box_muller_xp(o, xp=F64):
+    u1, u2 = xp.lift(u01(o[0], o[1])), xp.lift(u01(o[2], o[3]))
+    rad = xp.sqrt(-2 * xp.log(u1))
+    return rad * xp.cos(xp.two_pi * u2), rad * xp.sin(xp.two_pi * u2)
+
+
+def normals_xp(seed, c0, c1, c2, ncols, xp=F64):
+    """z (n, ncols): tag 0x11, sub = pair p -> z[2p] (cos), z[2p + 1] (sin)"""
+    z = xp.zeros((len(c0), ncols))
+    for p in range((ncols + 1) // 2):
+        z0, z1 = box_muller_xp(_words(seed, c0, c1, c2, TAG_NORMAL, p), xp)
+        z[:, 2 * p] = z0
+        if 2 * p + 1 < ncols:
+            z[:, 2 * p + 1] = z1
+    return z
+
+
+def gamma_draw_counters(seed, c0, c1, c2, shape, xp=F64):
+    """Marsaglia-Tsang on the streams of (c0, c1, c2): attempt t takes its normal x (the cos value) from block (0x12, t) and its
+    uniform u from (0x13, t); with d = a - 1/3, c = 1 / sqrt(9 d), w = 1 + c x, v = w^3 it is accepted when w > 0 and
+    log u < x^2 / 2 + d - d v + d log v, and gives d v; a = shape + 1 and a factor U^(1 / shape) (block (0x14, 0)) for a
+    shape below 1.  -> (G, attempts, margin): margin = the smallest distance of a decision of the row from its boundary."""
+    c0, c1 = np.asarray(c0, dtype=np.uint64), np.asarray(c1, dtype=np.uint64)
+    n = c0.size
+    shape = np.broadcast_to(np.asarray(shape, dtype=np.float64), (n,))
+    c2 = np.broadcast_to(np.asarray(c2, dtype=np.uint64), (n,))
+    a = np.where(shape < 1.0, shape + 1.0, shape)
+    d = a - 1.0 / 3.0
+    c = 1.0 / np.sqrt(9.0 * d)
+    attempts, margin, taken = np.zeros(n, dtype=np.int64), np.full(n, np.inf), np.zeros(n, dtype=np.int64)
+    live = np.arange(n)
+    for t in range(GAMMA_ATTEMPTS):
+        if live.size == 0:
+            break
+        x = box_muller(_words(seed, c0[live], c1[live], c2[live], TAG_GAMMA_N, t))[0]
+        w = 1.0 + c[live] * x
+        pos = w > 0.0
+        v = w * w * w
+        u = u01(*_words(seed, c0[live], c1[live], c2[live], TAG_GAMMA_U, t)[:2])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            gap = np.log(u) - (0.5 * x * x + d[live] - d[live] * v + d[live] * np.log(v))
+        margin[live] = np.minimum(margin[live], np.where(pos, np.minimum(np.abs(w), np.abs(gap)), np.abs(w)))
+        acc = pos & (gap < 0.0)
+        attempts[live], taken[live] = t + 1, t
+        live = live[~acc]
+    assert live.size == 0, "a rejection run of 64 attempts (probability below 1e-80)"
+    # the value, from the accepted attempt's words, in xp
+    G = xp.zeros(n)
+    for t in np.unique(taken):
+        m = taken == t
+        x = box_muller_xp(_words(seed, c0[m], c1[m], c2[m], TAG_GAMMA_N, int(t)), xp)[0]
+        dx = xp.lift(a[m]) - xp.lift(np.ones(m.sum())) / 3
+        cx = 1 / xp.sqrt(9 * dx)
+        w = 1 + cx * x
+        G[m] = dx * w * w * w
+    low = shape < 1.0
+    if low.any():
+        ub = xp.lift(u01(*_words(seed, c0[low], c1[low], c2[low], TAG_GAMMA_B)[:2]))
+        G[low] = G[low] * xp.exp(xp.log(ub) / xp.lift(shape[low]))
+    return G, attempts, margin
+
+
+def gamma_draw(seed, block, rows, c2, shape, row_offset=0, xp=F64):
+    c0, c1 = row_counters(block, rows, row_offset)
+    return gamma_draw_counters(seed, c0, c1, c2, shape, xp)
+
+
+def choose_cdf(u, cdf, klast):
+    """the component of u under running sums cdf (Kp,): the first k with cdf[k] > u, else klast -> (k, far)"""
+    over = cdf[None, :] > u[:, None]
+    k = np.where(over.any(axis=1), over.argmax(axis=1), klast)
+    return k.astype(np.int32), np.all(np.abs(cdf[None, :] - u[:, None]) > NEAR, axis=1)
+
+
+class Exact:
+    """values with what a comparison needs: mag = the magnitude of each entry's summed terms, nsum = the length of its sum,
+    label_far / value_far = the row's decisions are farther than NEAR from their boundaries"""
+
+    def __init__(self, x, mag, nsum, label, label_far, value_far):
+        self.x, self.mag, self.nsum, self.label, self.label_far, self.value_far = x, mag, nsum, label, label_far, value_far
+
+
+def sample_rows(mode, seed, block, rows, cdf, klast, loc, fac, shape, row_offset=0, xp=F64):
+    """lc_model_sample's rows of one block (i = 0): mode 0 Gauss-Wishart loc + F eps / sqrt(G) (one gamma per row, slot 0), mode
+    1 NormGamma loc_d + fac_d eps_d / sqrt(G_d) (slot = column), mode 2 ExpGamma fac_d expm1(-log u_d / shape) (c2 = pair)"""
+    rows = np.asarray(rows)
+    c0, c1 = row_counters(block, rows, row_offset)
+    k, lfar = choose_cdf(choice_u(seed, block, rows, 0, row_offset), np.asarray(cdf, dtype=np.float64), klast)
+    fac = np.asarray(fac, dtype=np.float64)
+    D = fac.shape[1]
+    n = rows.size
+    sh = np.asarray(shape, dtype=np.float64)[k]
+    x, mag = xp.zeros((n, D)), xp.zeros((n, D))
+    vfar = np.ones(n, dtype=bool)
+    if mode == 0:
+        G, _, margin = gamma_draw_counters(seed, c0, c1, 0, sh, xp)
+        vfar = margin > NEAR
+        eps = normals_xp(seed, c0, c1, 0, D, xp)
+        rs = 1 / xp.sqrt(G)
+        L, Fk = xp.lift(np.asarray(loc, dtype=np.float64)[k]), fac[k]
+        for i in range(D):
+            nz = np.flatnonzero(np.any(Fk[:, i, : i + 1] != 0, axis=0))  # (a product with an exact zero adds nothing)
+            terms = xp.lift(Fk[:, i, nz]) * eps[:, nz]
+            x[:, i] = L[:, i] + rs * terms.sum(axis=1)
+            mag[:, i] = abs(L[:, i]) + rs * abs(terms).sum(axis=1)
+        nsum = np.broadcast_to(np.arange(D) + 2, (n, D))
+    elif mode == 1:
+        eps = normals_xp(seed, c0, c1, 0, D, xp)
+        L, F = xp.lift(np.asarray(loc, dtype=np.float64)[k]), xp.lift(fac[k])
+        for d in range(D):
+            G, _, margin = gamma_draw_counters(seed, c0, c1, d, sh, xp)
+            vfar &= margin > NEAR
+            t = F[:, d] * eps[:, d] / xp.sqrt(G)
+            x[:, d], mag[:, d] = L[:, d] + t, abs(L[:, d]) + abs(t)
+        nsum = np.full((n, D), 2)
+    else:
+        F = xp.lift(fac[k])
+        for p in range((D + 1) // 2):
+            o = _words(seed, c0, c1, p, TAG_LOMAX)
+            for h, u in enumerate((u01(o[0], o[1]), u01(o[2], o[3]))):
+                d = 2 * p + h
+                if d < D:
+                    x[:, d] = F[:, d] * xp.expm1(-xp.log(xp.lift(u)) / xp.lift(sh))
+                    mag[:, d] = abs(x[:, d])
+        nsum = np.full((n, D), 1)
+    return Exact(x, mag, nsum, k, lfar, vfar)
+
+
+def cond_draws(seed, block, rows, ndraws, Xa, t, logp, ttab, pexp, mext, T, Lt, cq, Db, xp=F64):
+    """lc_model_predict_conditional_draws' rows of one block from the launch's own tables: per (row, draw i) the component k by
+    inverse CDF over r_k = exp(t_k - logp) (the sum short: the last k with r_k > 0), then
+      x_b = M_k(x_a) + sqrt(cq_k exp((ttab_k - t_k) / e_k) / G) L_k z,  M_k = [x_a - m_a,k, 1] T_k,  G ~ Gamma(e_k)  (c2 = i)
+    Xa (n, Da); t (n, Kp); logp (n,); ttab (Kp,) of the block; mext (Kp, Dae); T (Kp, Dae, Dbp); Lt (Kp, Dbp, Dbp) with
+    Lt[k][j][c] = L_k[c][j].  -> Exact with x, mag, nsum (n, ndraws, Db) and label, label_far, value_far (n, ndraws)"""
+    rows = np.asarray(rows)
+    n, Da = Xa.shape
+    c0, c1 = row_counters(block, rows)
+    r = np.exp(t - logp[:, None])
+    cum = np.cumsum(r, axis=1)
+    last = r.shape[1] - 1 - (r[:, ::-1] > 0).argmax(axis=1)
+    x, mag = xp.zeros((n, ndraws, Db)), xp.zeros((n, ndraws, Db))
+    label = np.zeros((n, ndraws), dtype=np.int32)
+    lfar, vfar = np.zeros((n, ndraws), dtype=bool), np.zeros((n, ndraws), dtype=bool)
+    Xl, ml, Tl, Ll = xp.lift(Xa), xp.lift(mext), xp.lift(T), xp.lift(Lt)
+    for i in range(ndraws):
+        u = choice_u(seed, block, rows, i)
+        over = (cum > u[:, None]) & (r > 0)
+        k = np.where(over.any(axis=1), over.argmax(axis=1), last)
+        label[:, i], lfar[:, i] = k, np.all(np.abs(cum - u[:, None]) > NEAR, axis=1)
+        e = pexp[k]
+        G, _, margin = gamma_draw_counters(seed, c0, c1, i, e, xp)
+        vfar[:, i] = margin > NEAR
+        z = normals_xp(seed, c0, c1, i, Db, xp)
+        tk = t[np.arange(n), k]
+        f = xp.sqrt(xp.lift(cq[k]) * xp.exp((xp.lift(ttab[k]) - xp.lift(tk)) / xp.lift(e)) / G)
+        dv = Xl - ml[k][:, :Da]
+        for c in range(Db):
+            mt = dv * Tl[k][:, :Da, c]
+            lt = Ll[k][:, : c + 1, c] * z[:, : c + 1]
+            x[:, i, c] = mt.sum(axis=1) + Tl[k][:, Da, c] + f * lt.sum(axis=1)
+            mag[:, i, c] = abs(mt).sum(axis=1) + abs(Tl[k][:, Da, c]) + f * abs(lt).sum(axis=1)
+    nsum = np.broadcast_to(Da + 1 + np.arange(Db) + 1, (n, ndraws, Db))
+    return Exact(x, mag, nsum, label, lfar, vfar)
+
+
+def scaled_error(got, want, mag):
+    """|got - want| / mag per entry as float64 (0 where both the error and the magnitude are 0)"""
+    err = np.abs(got - want)
+    out = np.zeros(np.shape(err))
+    nz = np.asarray(mag != 0, dtype=bool)
+    out[nz] = np.asarray(err[nz] / mag[nz], dtype=np.float64)
+    out[~nz & np.asarray(err != 0, dtype=bool)] = np.inf
+    return out
+
+
+def value_bar(nsum, e_ref):
+    """the bar of a drawn value: the forward bound of a recursive sum of nsum products plus 8 times the reference's own error"""
+    return (np.asarray(nsum) + 2) * 2.0 ** -53 + 8 * e_ref

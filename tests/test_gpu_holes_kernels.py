@@ -331,6 +331,30 @@ def _draws(name):
     return inp, o
 
 
+def _recovered_g_bar(comp, Xa, x, z, D, t, S):
+    """The bar of |G_recovered / gamma_draw - 1| per draw, G_recovered = 1 / mean_i(ratio_i)^2 over the holes i with
+    |z_i| >= 1e-3, ratio_i = v_i / (sqrt(cqnu h) z_i), v_i = sum_c (x_c - M_c) L_ci.  First order, every term relative to ratio_i:
+      * the device's x_c carries the value bar of the samplers, (n + 2) 2^-53 + 8 E_REF (n = D + 2 nb: a row of P times y, two
+        triangular solves), of |x_c| + |M_c|, and the subtraction x_c - M_c cancels: (|x| + |M|) |L| over |v_i|;
+      * the reference's location M_c is the direct route's, which this file holds to BAR_FILL S_n: BAR_FILL S_n |L| over |v_i|;
+      * the scale's h_k = exp((... - t_k) / e) inherits the error of t_k, which this file holds to BAR_T max(1, |t_k|): half of
+        that over e for the square root;
+      * a normal is wrong by at most rad (2 pi + 2) 2^-53, rad <= 8.65 (the angle's rounding times 2 pi, a sincos of an ulp),
+        on the device and in the reference, each allowed twice that: 4 * 8.65 (2 pi + 2) 2^-53 over |z_i|.
+    G takes twice the largest of these over its holes, plus 8 E_REF for the two gamma values themselves."""
+    import sample_kernel_cases as sc
+
+    nb = x.shape[1]
+    M = comp.location(Xa)
+    v = np.abs((x - M) @ comp.L)
+    aL = np.abs(comp.L)
+    e = comp.eta / 2
+    per = (sr.value_bar(D + 2 * nb, sc.E_REF["gamma"]) * ((np.abs(x) + np.abs(M)) @ aL) + hc.BAR_FILL * S[:, None] * aL.sum(axis=0)) / v
+    per = per + (0.5 * hc.BAR_T * np.maximum(1.0, np.abs(t)) / e)[:, None] + 4 * 8.65 * (2 * np.pi + 2) * 2.0 ** -53 / np.abs(z)
+    per[np.abs(z) < 1e-3] = np.nan
+    return 2 * np.nanmax(per, axis=1) + 8 * sc.E_REF["gamma"]
+
+
 @pytest.mark.parametrize("name", sorted(hc.DRAW_CASES))
 def test_draws(name):
     build, nd = hc.DRAW_CASES[name]
@@ -348,19 +372,32 @@ def test_draws(name):
         assert o.label.max() >= 64  # the second chunk of clusters is drawn from
     # the structure of a draw: L^T (x_b - M_k) / sqrt(cqnu_k h_k) over z is one positive scalar 1 / sqrt(G) over its holes
     worst, G, at = 0.0, {}, 0
+    gworst, gleft, gtotal = 0.0, 0, 0
     for j, (Xh, _) in enumerate(c.blocks):
         s = slice(at, at + Xh.shape[0])
         for comp, pat, rows, di, Xa in c.ref.mixes[j].each(Xh, o.label[s]):
             nb = len(pat)
             z = dr.normals(hc.DRAW_SEED, j, rows, di, (nb + 1) // 2)[:, :nb]
-            ratio = comp.inv_sqrt_g(Xa, o.draws[s][rows, di, :nb], z)
+            x = o.draws[s][rows, di, :nb]
+            ratio = comp.inv_sqrt_g(Xa, x, z)
             ratio[np.abs(z) < 1e-3] = np.nan
             ok = np.sum(~np.isnan(ratio), axis=1) >= 1
             lo, hi = np.nanmin(ratio[ok], axis=1), np.nanmax(ratio[ok], axis=1)
             assert np.all(lo > 0), (name, pat)
             worst = max(worst, float(np.max(hi / lo - 1, initial=0.0)))
-            G.setdefault((comp.eta, nb), []).append(1 / np.nanmean(ratio[ok], axis=1) ** 2)
+            g = 1 / np.nanmean(ratio[ok], axis=1) ** 2
+            G.setdefault((comp.eta, nb), []).append(g)
+            # the recovered G against the restated gamma draw on the draw's own stream (c2 = draw, shape e_k(nb))
+            want, _, margin = sr.gamma_draw(hc.DRAW_SEED, j, rows[ok], di[ok], comp.eta / 2)
+            k = o.label[s][rows[ok], di[ok]]
+            bar = _recovered_g_bar(comp, Xa[ok], x[ok], z[ok], c.Xh.shape[1], o.t[s][rows[ok], k], c.ref.S[at + rows[ok]])
+            far = margin > sr.NEAR
+            gleft, gtotal = gleft + int((~far).sum()), gtotal + far.size
+            gworst = max(gworst, float(np.max((np.abs(g / want - 1) / bar)[far], initial=0.0)))
         at += Xh.shape[0]
+    print(f"{name}: largest error of the recovered G against gamma_draw over its bar {gworst:.3e}; {gleft} of {gtotal} draws left out")
+    assert gleft <= (1 if gtotal < 1000 else sr.EXCLUDED_SHARE * gtotal)
+    assert gworst <= 1.0, name
     print(f"{name}: largest relative spread of 1 / sqrt(G) over the holes of a draw: {worst:.3e} (bar 1e-9)")
     assert worst <= 1e-9
     if build == "d5_k1_n120":  # Kp = 1: the recovered G, pooled per hole count, is Gamma(e(nb))

@@ -10,6 +10,7 @@ import pytest
 
 import lc_oracle as o
 from libcluster_amd import capi
+from rank_select_cases import top_rows_ref as _ref
 
 pytestmark = pytest.mark.gpu
 
@@ -18,25 +19,7 @@ BIG_N = 3 * TOP_CHUNK_ROWS + 17
 
 
 # ---- the reference --------------------------------------------------------------------------------------------------
-def _ref(cols, sizes, m, largest, labels=None):
-    """cols: (N, C) scores of the rows of all groups in order; -> TopRows of numpy"""
-    N, Cn = cols.shape
-    grp = np.repeat(np.arange(len(sizes)), sizes)
-    row = np.concatenate([np.arange(n) for n in sizes]) if N else np.zeros(0, dtype=np.int64)
-    count = np.zeros(Cn, dtype=np.int32)
-    group, rows = np.full((Cn, m), -1, dtype=np.int32), np.full((Cn, m), -1, dtype=np.int64)
-    score = np.full((Cn, m), np.nan)
-    for c in range(Cn):
-        s = cols[:, c]
-        ok = ~np.isnan(s)
-        if labels is not None:
-            ok &= labels == c
-        idx = np.flatnonzero(ok)
-        key = -s[idx] if largest else s[idx]  # (-0.0 and +0.0 compare equal in the sort: the position decides)
-        best = idx[np.lexsort((idx, key))[:m]]
-        n = best.size
-        count[c], group[c, :n], rows[c, :n], score[c, :n] = n, grp[best], row[best], s[best]
-    return capi.TopRows(count, group, rows, score)
+# (the reference itself lives in tests/rank_select_cases.py: the launcher-level tests rank with it too)
 
 
 def _same(got, want):
